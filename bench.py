@@ -174,6 +174,8 @@ def parse():
     ap.add_argument("--dry-launch", action="store_true", help="launcher check without a GPU: start the ranks, rendezvous over gloo, print one line with each rank's environment")
     ap.add_argument("--master-port", type=int, default=0, help="rendezvous port when bench.py starts the ranks itself (0: pick a free one)")
     ap.add_argument("--cpu-size", type=str, default="auto", help="WxH of the CPU-baseline view (auto: scaled to the core count)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the maps the last timed step computed (rank 0's view) "
+                    "as DIR/<name>.npy: a fixed, seeded sample of at most DUMP_MAX_PIXELS pixels (all of a smaller view) with their indices")
     return ap.parse_args()
 
 
@@ -420,6 +422,32 @@ def per_iteration_ms(ctx, iters, view_index, weak):
     return res
 
 
+DUMP_MAX_PIXELS = 1 << 20   # 40 B a pixel over the files below: at most 40 MB
+DUMP_SEED = 20251015
+
+
+def dump_outputs(ctx, out_dir):
+    """--dump-outputs: what a caller of RunPatchMatch receives for the view — depth, normal, selected views, states and radius
+    as dvp_download_maps hands them (the driver's result files) — at a fixed, seeded sample of pixels, as float32 / float64
+    .npy files.  The matching costs stay out: like the reference's costs_cuda they are engine-internal state, and pixels left
+    UNKNOWN carry NaN there.  Must run before anything else touches the context's state after the timed steps."""
+    depth, normal, views, weak, radius = ctx.download_maps()
+    L = depth.shape[0]
+    if L <= DUMP_MAX_PIXELS:
+        idx = np.arange(L, dtype=np.int64)
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(L, DUMP_MAX_PIXELS, replace=False))
+    arrays = {"pixel_index": idx.astype(np.float64), "depth": depth[idx], "normal": normal[idx],
+              "selected_views": views[idx].astype(np.float64), "states": weak[idx].astype(np.float32),
+              "radius": radius[idx].astype(np.float32)}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= 64 << 20, total
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+    sys.stderr.write("bench.py: wrote %d arrays (%d of %d pixels, %.1f MB) to %s\n" % (len(arrays), idx.size, L, total / 1e6, out_dir))
+
+
 def measure(env, args, cfg_name, W, H, S, iters, weak_frac_arg, steps, warmup, primary):
     """one workload on this rank's GPU: scene, context, (untimed FIRST_INIT + hand-over), warm-up, timed steps -> the line's dict (rank 0)"""
     torch, dist, dev = env["torch"], env["dist"], env["dev"]
@@ -557,6 +585,9 @@ def measure(env, args, cfg_name, W, H, S, iters, weak_frac_arg, steps, warmup, p
         bt = [torch.zeros(1, dtype=torch.float64, device=dev) for _ in range(world)]
         dist.all_gather(bt, torch.tensor([busy], dtype=torch.float64, device=dev))
         busy_all = [float(b.item()) for b in bt]
+
+    if rank == 0 and primary and args.dump_outputs:
+        dump_outputs(ctx, args.dump_outputs)
 
     if rank == 0:
         total_px_iter = float(W) * H * iters * steps * world

@@ -544,7 +544,7 @@ def random_normal_yzl(cams, x, y, depth, selected, uniforms, depth_maps=None):
         v = (d[0], d[1], d[0])                                              # {x, y, x} (APD.cu:543)
         f = (Rc[0] * v[0] + Rc[1] * v[1] + Rc[2] * v[2], Rc[3] * v[0] + Rc[4] * v[1] + Rc[5] * v[2], Rc[6] * v[0] + Rc[7] * v[1] + Rc[7] * v[2])   # A[7] twice (APD.cu:17)
         nrm = math.sqrt(f[0] ** 2 + f[1] ** 2 + f[2] ** 2)
-        if len(dirs) < 20:
+        if len(dirs) < 20:      # float4 view_direction[20] (APD.cu:511): the reference and at most 19 sources, as the oracle keeps them (ora_kernels.cpp: `if (index < 20)`)
             dirs.append((f[0] / nrm, f[1] / nrm, f[2] / nrm))
     k = 0
     fragile = False

@@ -275,7 +275,7 @@ def test_launch_geometry_covers_every_pixel_once():
 
 
 @pytest.mark.parametrize("form", ["split", "split_lockstep_refine", "monolithic"])
-@pytest.mark.parametrize("S", [3, 5, 9, 12])
+@pytest.mark.parametrize("S", [3, 5, 8, 9, 12, 16])   # dvp_strong_decide_v4 / v6 / v8 / v10 / v12 / v16
 def test_strong_update_forms_equal_the_oracle(form, S, monkeypatch):
     """split: evaluation of the bitwise-distinct planes of a pixel's 17 slots ((pixel, slot) items over the lanes on the
     engine, dvp_strong_eval_items), decisions through the slot -> source-slot table, refinement with every lane on its own

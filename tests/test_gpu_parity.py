@@ -221,7 +221,7 @@ def test_ransac_fit_plane_forms_equal_the_oracle(form, monkeypatch):
 
 
 @pytest.mark.parametrize("form", ["split", "split_lockstep_refine", "monolithic"])
-@pytest.mark.parametrize("S", [3, 5, 9, 12])
+@pytest.mark.parametrize("S", [3, 5, 8, 9, 12, 16])   # dvp_strong_decide_v4 / v6 / v8 / v10 / v12 / v16
 def test_strong_update_forms_equal_the_oracle(form, S, monkeypatch):
     """the three launches with dvp_strong_refine_lanes (every lane on its own (hypothesis, view) sequence) or
     dvp_strong_refine (the wave in lock step), and the monolithic kernel: see test_emul_parity"""

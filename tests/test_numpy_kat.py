@@ -125,7 +125,8 @@ def test_geom_cost_rotated_cameras_with_skew_vs_numpy():
     assert np.median(d) < 1e-4 and d.max() < 5e-3
 
 
-def _two_pass(sc, S, sampler):
+def _two_pass(sc, S, sampler, make=O.from_scene, **over):
+    """pass 1 on the oracle; pass 2 (REFINE_ITER, ready to run) on `make`: the oracle, or the HIP engine in the gpu twins"""
     W, H = sc["width"], sc["height"]
     p1 = make_params(S + 1, max_iterations=2, state=synth.FIRST_INIT, use_APD=0)
     o1 = O.from_scene(sc, p1, seed=777, sampler=sampler)
@@ -136,8 +137,8 @@ def _two_pass(sc, S, sampler):
     weak[sc["flat"] & (weak == synth.STRONG)] = synth.WEAK
     st["weak"] = weak.reshape(-1)
     p2 = make_params(S + 1, max_iterations=1, state=synth.REFINE_ITER, use_APD=1, geom_consistency=1,
-                     weak_peak_radius=4, rotate_time=2, ransac_threshold=0.01)
-    o2 = O.from_scene(sc, p2, seed=778, sampler=sampler, depths=sc["depth_gt"])
+                     weak_peak_radius=4, rotate_time=2, ransac_threshold=0.01, **over)
+    o2 = make(sc, p2, seed=778, sampler=sampler, depths=sc["depth_gt"])
     o2.upload_state(**st)
     return o2, p2
 
@@ -296,19 +297,42 @@ def test_filter_get_depth_normal_nearest_strong_vs_numpy():
         assert checked > 100
 
 
+def hip_engine(*a, **kw):
+    return pkg("capi").from_scene(*a, **kw)
+
+
+# S > 8: the view-selection CDF over more than 8 candidates, top-k over more than 4 costs, several five-view candidate groups
+LARGE_S = [10, 16, 20]
+
+
 def test_strong_propagation_and_view_selection_vs_numpy():
+    strong_propagation_case(3, O.from_scene)
+
+
+@pytest.mark.parametrize("S", LARGE_S)
+def test_strong_propagation_and_view_selection_vs_numpy_many_views(S):
+    strong_propagation_case(S, O.from_scene)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("S", [3, 20])
+def test_strong_propagation_and_view_selection_hip_vs_numpy(S):
+    """the same buffers from the HIP engine's launch, against the float64 model directly"""
+    strong_propagation_case(S, hip_engine)
+
+
+def strong_propagation_case(S, make):
     """The decision half of CheckerboardPropagationStrong (APD.cu:2010-2141, 2462-2567) read from the source into numpy — the
     edge-adaptive and the fixed sample scan with their quirks (`!edge_pt.x == -1`, `dir_index > 4`, `= { 2.0f }`), the
     replacement rule, the joint view selection from the 8 cost vectors and the neighbours' priors, the 15 draws against the
     CDF, FindMinCostIndex' tie rule, the adoption test — against what the oracle's launch leaves in view_weight and
     selected_views.  The random numbers are the contract's (ora_rand_u32 at the documented site); the costs are the float64
     model's, so pixels where a comparison sits within 2e-4 of flipping are skipped."""
-    S = 3
     sc, cams, imgs, _ = _scene(112, 80, S)
     W, H = sc["width"], sc["height"]
     p = make_params(S + 1, max_iterations=2, state=synth.FIRST_INIT, use_APD=0)
     seed = 4242
-    o = O.from_scene(sc, p, seed=seed, sampler=1)
+    o = make(sc, p, seed=seed, sampler=1)
     o.upload_state(**first_pass_state(sc))
     for st in ("gen_edge_inform", "random_init"):
         o.run_stage(st)
@@ -365,18 +389,35 @@ def test_strong_propagation_and_view_selection_vs_numpy():
         got = planes_after[c].astype(np.float64)
         assert np.max(np.abs(got - np.array(pl)) / np.maximum(1e-2, np.abs(pl))) < 2e-4, (x, y, got, pl)
         assert abs(float(costs_after[c]) - cost) < 5e-4, (x, y, costs_after[c], cost)
-    print("strong propagation oracle vs numpy: %d pixels checked (%d fragile skipped), %d adoptions, %d edge pixels; refinement: %d checked (%d fragile), %d changed the plane"
-          % (checked, fragile, adopted, on_edge, refined, fragile2, improved))
+    print("S=%d strong propagation vs numpy: %d pixels checked (%d fragile skipped), %d adoptions, %d edge pixels; refinement: %d checked (%d fragile), %d changed the plane"
+          % (S, checked, fragile, adopted, on_edge, refined, fragile2, improved))
     assert checked >= 40 and adopted >= 5 and on_edge >= 5
     assert refined >= 30 and improved >= 3
 
 
 def test_gen_edge_inform_vs_numpy():
+    gen_edge_inform_case(4, 5, O.from_scene)
+
+
+@pytest.mark.parametrize("S,weak_radius", [(S, 5) for S in LARGE_S] + [(4, 3), (4, 8)])
+def test_gen_edge_inform_vs_numpy_many_views_and_radii(S, weak_radius):
+    """several five-view candidate groups; the sector table of a weak_radius other than 5"""
+    gen_edge_inform_case(S, weak_radius, O.from_scene)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("S,weak_radius", [(4, 5), (20, 5), (4, 3), (4, 8)])
+def test_gen_edge_inform_hip_vs_numpy(S, weak_radius):
+    """the HIP engine's launch against the float64 model directly: the five-view candidate kernel (weak_radius 5) and the
+    per-view kernel with the sector table of another radius"""
+    gen_edge_inform_case(S, weak_radius, hip_engine)
+
+
+def gen_edge_inform_case(S, weak_radius, make):
     """GenEdgeInform (APD.cu:3731-3890) read into numpy: visibility-prior offsets (sector winners ranked by colour weight: exact
     integers), nearest edge pixels (exact), the edge-density sigmoid of WEAK pixels, label boundaries (exact)."""
-    S = 4
     sc, cams, imgs, _ = _scene(128, 96, S)
-    o, p = _two_pass(sc, S, 1)
+    o, p = _two_pass(sc, S, 1, make, weak_radius=weak_radius)
     W, H = sc["width"], sc["height"]
     views, edge, label, weak = o.get("selected_views").copy(), o.get("edge").copy(), o.get("label").copy(), o.get("weak_info").copy()
     o.run_stage("gen_edge_inform")
@@ -405,8 +446,8 @@ def test_gen_edge_inform_vs_numpy():
             if m["label_boundary"] is not None:
                 n_lab += 1
                 assert [tuple(int(t) for t in q) for q in lb[nmap[c]]] == m["label_boundary"], (x, y)
-    print("gen_edge_inform oracle vs numpy: %d candidate lists exact (%d fragile skipped), complex max diff %.1e on %d WEAK pixels, %d label boundaries exact"
-          % (n_c, n_f, max(dc), len(dc), n_lab))
+    print("S=%d weak_radius=%d gen_edge_inform vs numpy: %d candidate lists exact (%d fragile skipped), complex max diff %.1e on %d WEAK pixels, %d label boundaries exact"
+          % (S, weak_radius, n_c, n_f, max(dc), len(dc), n_lab))
     assert n_c > 250 and len(dc) >= 40 and max(dc) < 1e-5 and n_lab >= 10
 
 
@@ -476,14 +517,29 @@ def test_ransac_fit_plane_vs_numpy():
 
 
 def test_weak_update_vs_numpy():
+    weak_update_case(3, O.from_scene)
+
+
+@pytest.mark.parametrize("S", LARGE_S)
+def test_weak_update_vs_numpy_many_views(S):
+    weak_update_case(S, O.from_scene)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("S", [3, 20])
+def test_weak_update_hip_vs_numpy(S):
+    """the HIP engine's launch against the float64 model directly"""
+    weak_update_case(S, hip_engine)
+
+
+def weak_update_case(S, make):
     """CheckerboardPropagationWeak + PlaneHypothesisRefinementWeak (APD.cu:2739-3089, 1897-2008) read into numpy on top of the
     NCCNew model: the anchors' planes as candidates, the priors from the anchors' selected views, view selection, the geometric
     term in the weighted costs (3.0 for an absent anchor), adoption, the fit-plane test (and its early return), the six
     refinement hypotheses with GenerateRandomNormal_YZL reading the source depth maps, and the launch's final plain-NCC cost —
     against the view weights, selected views, planes and costs the oracle's launch leaves."""
-    S = 3
     sc, cams, imgs, deps = _scene(128, 96, S)
-    o, p = _two_pass(sc, S, 1)
+    o, p = _two_pass(sc, S, 1, make)
     W, H = sc["width"], sc["height"]
     for st in ("gen_edge_inform", "find_nearest_strong", "gen_neighbours", "neighbour_update", "random_init"):
         o.run_stage(st)
@@ -529,7 +585,7 @@ def test_weak_update_vs_numpy():
         inc = max(2, int(2.0 * sr / 5.0)) if int(p["use_radius"]) else int(p["strong_increment"])
         want = sum(m["view_weight"][j] * M.ncc_old(imgs, cams, x, y, j + 1, m["plane"], sr, inc) for j in range(S)) / m["wn"]
         assert abs(float(costs_after[c]) - want) < 1e-3, (x, y, costs_after[c], want)
-    print("weak update oracle vs numpy: %d WEAK pixels checked (%d fragile skipped), %d adoptions, %d planes changed" % (checked, frag, adopted, moved))
+    print("S=%d weak update vs numpy: %d WEAK pixels checked (%d fragile skipped), %d adoptions, %d planes changed" % (S, checked, frag, adopted, moved))
     assert checked >= 25 and moved >= 5
 
 
@@ -582,10 +638,25 @@ def test_gen_neighbours_vs_numpy():
 
 
 def test_random_initialization_vs_numpy():
+    random_initialization_case(4, O.from_scene)
+
+
+@pytest.mark.parametrize("S", LARGE_S)
+def test_random_initialization_vs_numpy_many_views(S):
+    random_initialization_case(S, O.from_scene)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("S", [4, 20])
+def test_random_initialization_hip_vs_numpy(S):
+    """the HIP engine's launch against the float64 model directly"""
+    random_initialization_case(S, hip_engine)
+
+
+def random_initialization_case(S, make):
     """RandomInitialization (APD.cu:1273-1309), both branches, against the oracle's launch: the random hypothesis of a first
     pass (depth + GenerateRandomNormal_YZL from the contract's streams), the kept prior plane, the top-k cost / view rule;
     and the conversion + selected-view pruning (unSetBit clears bits 0..n) of a later pass."""
-    S = 4
     sc, cams, imgs, _ = _scene(112, 80, S)
     W, H = sc["width"], sc["height"]
     L = O.lib()
@@ -593,7 +664,7 @@ def test_random_initialization_vs_numpy():
     # --- FIRST_INIT: zero planes (out of range -> random) with a band of prior planes
     p1 = make_params(S + 1, max_iterations=1, state=synth.FIRST_INIT, use_APD=0)
     seed = 909
-    o = O.from_scene(sc, p1, seed=seed, sampler=1)
+    o = make(sc, p1, seed=seed, sampler=1)
     st = first_pass_state(sc)
     prior = np.zeros((H * W, 4), np.float32)
     band = np.arange(H * W) % W < 30
@@ -621,7 +692,7 @@ def test_random_initialization_vs_numpy():
             assert np.max(np.abs(planes[c] - np.array(pl)) / np.maximum(1e-2, np.abs(pl))) < 2e-4, (x, y, planes[c], pl)
         assert abs(float(costs[c]) - cost) < 5e-4 and int(views[c]) == sel, (x, y, costs[c], cost, int(views[c]), sel)
     # --- a later pass
-    o2, p2 = _two_pass(sc, S, 1)
+    o2, p2 = _two_pass(sc, S, 1, make)
     before, vb = o2.get("planes").copy(), o2.get("selected_views").copy()
     o2.run_stage("gen_edge_inform")
     o2.run_stage("random_init")
@@ -635,5 +706,5 @@ def test_random_initialization_vs_numpy():
         assert np.max(np.abs(planes2[c] - np.array(pl)) / np.maximum(1e-2, np.abs(pl))) < 2e-5, (x, y)
         assert abs(float(costs2[c]) - cost) < 5e-4 and int(views2[c]) == sel, (x, y, costs2[c], cost, int(views2[c]), sel)
         pruned += int(sel != int(vb[c]))
-    print("random_initialization oracle vs numpy: first pass %d random + %d prior pixels (%d fragile skipped); later pass 100 pixels, %d with pruned views" % (n_rand, n_prior, frag, pruned))
+    print("S=%d random_initialization vs numpy: first pass %d random + %d prior pixels (%d fragile skipped); later pass 100 pixels, %d with pruned views" % (S, n_rand, n_prior, frag, pruned))
     assert n_rand >= 50 and n_prior >= 15

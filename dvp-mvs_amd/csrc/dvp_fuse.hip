@@ -630,13 +630,15 @@ static int fuse_reserve(dvp_fuse* f, size_t L, int ns) {
 #endif
 
 // Fuse view slot `v` against the source slots `src` (pair.txt order; slots without maps must have been left out by the caller,
-// as RunFusion skips them): the accepted points are appended to the cloud in scan order.
+// as RunFusion skips them): the accepted points are appended to the cloud in scan order.  `src` may list `v` itself, as a pair.txt
+// can: the reference then compares every pixel with itself (APD.cpp:1894-1925) — its own lift lands back on the pixel, which is
+// a witness and is claimed with the point.  Nothing here needs to know: the pixel is the only lister of that candidate.
 int dvp_fuse_view(dvp_fuse* f, int v, const int* src, int num_src) {
 	if (!f) return 1;
 	if (v < 0 || v >= f->num_views || !f->have[v] || num_src < 0 || (num_src > 0 && !src)) { f->error = "dvp_fuse_view: bad arguments"; return 1; }
 	if (num_src > 64) { f->error = "dvp_fuse_view: more than 64 source views"; return 1; }
 	for (int j = 0; j < num_src; ++j)
-		if (src[j] < 0 || src[j] >= f->num_views || !f->have[src[j]] || src[j] == v) { f->error = "dvp_fuse_view: bad source slot"; return 1; }
+		if (src[j] < 0 || src[j] >= f->num_views || !f->have[src[j]]) { f->error = "dvp_fuse_view: bad source slot"; return 1; }
 	FUSE_TRY(f, hipSetDevice(f->device));
 	if (f->views_dirty) {
 		FUSE_TRY(f, hipMemcpyAsync(f->views_dev, f->views.data(), sizeof(FuseView) * f->num_views, hipMemcpyHostToDevice, f->stream));
@@ -674,9 +676,10 @@ int dvp_fuse_view(dvp_fuse* f, int v, const int* src, int num_src) {
 		if (rounds >= DVP_FUSE_MAX_ROUNDS || (rounds > 0 && n_list <= DVP_FUSE_REST)) {
 			// a long dependency chain (many pixels in a row sharing witnesses pairwise): the rest in index order by one lane
 			std::vector<unsigned> rest(n_list);
-			FUSE_TRY(f, hipMemcpy(rest.data(), cur, (size_t)n_list * 4, hipMemcpyDeviceToHost));
+			FUSE_TRY(f, hipMemcpyAsync(rest.data(), cur, (size_t)n_list * 4, hipMemcpyDeviceToHost, f->stream));
+			FUSE_TRY(f, hipStreamSynchronize(f->stream));
 			std::sort(rest.begin(), rest.end());
-			FUSE_TRY(f, hipMemcpy(cur, rest.data(), (size_t)n_list * 4, hipMemcpyHostToDevice));
+			FUSE_TRY(f, hipMemcpyAsync(cur, rest.data(), (size_t)n_list * 4, hipMemcpyHostToDevice, f->stream));
 			ra.list = cur; ra.n_list = n_list; ra.next = nullptr; ra.n_next = nullptr; ra.round_hi = 0;
 			hipLaunchKernelGGL(fuse_decide_rest, dim3(1), dim3(64), 0, f->stream, ra);
 			FUSE_TRY(f, hipGetLastError());
@@ -734,7 +737,7 @@ int dvp_fuse_view_graded(dvp_fuse* f, int v, const int* src, int num_src, int ad
 	if (v < 0 || v >= f->num_views || !f->have[v] || num_src < 0 || (num_src > 0 && !src)) { f->error = "dvp_fuse_view_graded: bad arguments"; return 1; }
 	if (num_src > 64) { f->error = "dvp_fuse_view_graded: more than 64 source views"; return 1; }
 	for (int j = 0; j < num_src; ++j)
-		if (src[j] >= f->num_views || (src[j] >= 0 && (!f->have[src[j]] || src[j] == v))) { f->error = "dvp_fuse_view_graded: bad source slot"; return 1; }
+		if (src[j] >= f->num_views || (src[j] >= 0 && !f->have[src[j]])) { f->error = "dvp_fuse_view_graded: bad source slot"; return 1; }
 	FUSE_TRY(f, hipSetDevice(f->device));
 	if (f->views_dirty) {
 		FUSE_TRY(f, hipMemcpyAsync(f->views_dev, f->views.data(), sizeof(FuseView) * f->num_views, hipMemcpyHostToDevice, f->stream));

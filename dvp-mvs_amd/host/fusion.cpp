@@ -509,7 +509,7 @@ void RunFusionGraded(const path& dense_folder, const std::vector<Problem>& probl
 						const int sx = int(q.x + 0.5f), sy = int(q.y + 0.5f);
 						if (sx < 0 || sx >= S.cols() || sy < 0 || sy >= S.rows()) continue;
 						const float zs = S.depth.at<float>(sy, sx);
-						if (S.claimed.at<uint8_t>(sy, sx) == 1 || zs <= 0.0) continue;   // (S's flags are final or still untouched: S is not the view being scanned)
+						if (S.claimed.at<uint8_t>(sy, sx) == 1 || zs <= 0.0) continue;   // (S's flags are final or still untouched; a view listed as its own source meets its pixel's own flag, set only after the pixel)
 						float2 back;
 						float z_seen;
 						ProjectCamera(S.lift(sx, sy, zs), R.cam, back, z_seen);

@@ -3,8 +3,11 @@
 #include <thread>
 #include <chrono>
 #include "../../dvp-mvs_amd/host/APD.h"
+#include "../../dvp-mvs_amd/csrc/dvp_fuse_math.hpp"
 #include <cassert>
+#include <cmath>
 #include <cstdio>
+#include <omp.h>
 
 #define CHECK(c) do { if (!(c)) { fprintf(stderr, "CHECK failed: %s (%s:%d)\n", #c, __FILE__, __LINE__); return 1; } } while (0)
 
@@ -93,6 +96,65 @@ static int fuse_folder(const path& folder) {
 	return 0;
 }
 
+// `test_host --acos`: the engine's own dvp::fuse_acosf (csrc/dvp_fuse_math.hpp, compiled here as the host library compiles it)
+// at every binary32 value in [-1, 1] against acos in double; prints the largest error in units of the last place of the true
+// value's binary32 binade, and checks fuse_angle's "rounded past 1 -> 0" and the NaN outside [-1, 1].  Exit 0 = checks passed.
+static int acos_contract() {
+	const uint32_t top = 0x3f800000u;   // bits of 1.0f: [0, top] are the values 0 .. 1, the same with the sign bit set 0 .. -1
+	const int threads = std::max(1, std::min(16, omp_get_num_procs()));
+	double worst = 0.0;
+	float worst_x = 0.0f;
+	long long nan_inside = 0;
+#pragma omp parallel num_threads(threads)
+	{
+		double w = 0.0;
+		float wx = 0.0f;
+		long long bad = 0;
+#pragma omp for schedule(static)
+		for (long long i = 0; i <= 2ll * top + 1; ++i) {
+			const uint32_t b = i <= top ? (uint32_t)i : 0x80000000u | (uint32_t)(i - top - 1);
+			const float x = __builtin_bit_cast(float, b);
+			const float r = dvp::fuse_acosf(x);
+			const double t = std::acos((double)x);
+			if (r != r) { ++bad; continue; }
+			int e;
+			std::frexp(t, &e);                                  // t in [2^(e-1), 2^e): binary32 ulp there is 2^(e-24)
+			const double err = std::fabs((double)r - t) / std::ldexp(1.0, e - 24);
+			if (err > w) { w = err; wx = x; }
+		}
+#pragma omp critical
+		{
+			if (w > worst) { worst = w; worst_x = wx; }
+			nan_inside += bad;
+		}
+	}
+	printf("acos max_ulp %.6f at %.9g (%d threads)\n", worst, worst_x, threads);
+	CHECK(nan_inside == 0);
+	// NaN outside [-1, 1] and for NaN
+	for (float x : { std::nextafter(1.0f, 2.0f), std::nextafter(-1.0f, -2.0f), 2.0f, -3.5f, INFINITY, -INFINITY, NAN }) {
+		const float r = dvp::fuse_acosf(x);
+		CHECK(r != r);
+	}
+	CHECK(dvp::fuse_acosf(1.0f) == 0.0f);
+	// GetAngle (APD.cpp:1797-1806): a dot product of unit normals that rounds past 1 gives acos = NaN, the angle is 0
+	int past_one = 0;
+	for (int k = 0; k < 100000; ++k) {
+		float v[3] = { std::sin(0.001f * k), std::cos(0.0013f * k), 0.3f + 0.0001f * k };
+		const float n = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+		for (float& c : v) c /= n;
+		const float dot = v[0] * v[0] + v[1] * v[1] + v[2] * v[2];
+		if (dot > 1.0f) {
+			++past_one;
+			CHECK(dvp::fuse_angle(v, v) == 0.0f);
+		} else {
+			CHECK(dvp::fuse_angle(v, v) == dvp::fuse_acosf(dot));
+		}
+	}
+	printf("acos dot_past_one %d\n", past_one);
+	CHECK(past_one > 0);
+	return 0;
+}
+
 // `test_host --jpeg in.jpg out.bin channels`: DecodeJpeg -> raw bytes preceded by int32 rows, cols, channels
 static int dump_jpeg(const path& in, const path& out, int channels) {
 	const Mat m = DecodeJpeg(in, channels);
@@ -148,6 +210,7 @@ static int dump_prior(const path& folder, int id, int W, int H, const path& out)
 
 int main(int argc, char** argv) {
 	if (argc > 2 && std::string(argv[1]) == "--fuse") return fuse_folder(argv[2]);
+	if (argc > 1 && std::string(argv[1]) == "--acos") return acos_contract();
 	if (argc > 6 && std::string(argv[1]) == "--depth-cloud") {   // --depth-cloud depths.dmb image cam out.ply dmin dmax
 		Mat depth;
 		if (!ReadBinMat(argv[2], depth)) return 2;

@@ -195,7 +195,8 @@ class Context:
         self._ck(self.L.dvp_reset_state(self.h))
 
     def image_format(self):
-        """0: float planes, 1: byte planes (8-bit exact image set) — include/dvp_mvs.h dvp_image_format"""
+        """0: float planes, 1: byte planes (8-bit exact image set), 2: binary16 planes (every texel a binary16 value in
+        [0, 255], not all integers: down-sampled levels of 8-bit images) — include/dvp_mvs.h dvp_image_format"""
         return int(self.L.dvp_image_format(self.h))
 
     def save_state(self):

@@ -91,6 +91,13 @@ struct Dev {
 	const uint8_t* images8;
 	int img8_tiles_x;            // tiles per tile row
 	size_t img8_plane_bytes;     // bytes of one image
+	// the same images as BINARY16 pairs {I(x,y), I(x,y+1)} in 128-byte tiles of 4 rows x 8 elements (7 pixels + the next
+	// tile's first again), or null: kept when the set is not 8-bit exact but every texel is a binary16 value in [0, 255] —
+	// the power-of-two down-sampled levels of 8-bit images (multiples of 0.25).  A footprint is 8 bytes instead of 16; same
+	// values, so same results.  Format 2 is chosen by this pointer alone (images8 is null then).
+	const uint32_t* images16;
+	int img16_tiles_x;
+	size_t img16_plane_bytes;
 	const float* depths;       // same layout (geom_consistency only)
 	const DvpCamera* cameras;  // [num_images]
 	const ViewConst* views;    // [num_images] (index 0 unused)
@@ -246,7 +253,7 @@ DVP_HD void load_quad(const float* base, unsigned byte_off, float* a, float* b, 
 #endif
 }
 // Image format of a kernel instantiation: FMT 0 = float row pairs (Dev::images), FMT 1 = tiled byte pairs
-// (Dev::images8).
+// (Dev::images8), FMT 2 = tiled binary16 pairs (Dev::images16, below).
 #ifndef DVP_IMG8_TW
 #define DVP_IMG8_TW 7
 #endif
@@ -280,9 +287,93 @@ DVP_HD unsigned img8_offset(int tiles_x, int i0, int j0) {
 #endif
 	return (tile << 7) + ey * (unsigned)(kT8B * kT8E) + ex * (unsigned)kT8B;
 }
+// FMT 2 = tiled binary16 pairs (Dev::images16): elements {h(x,y), h(x,y+1)} of 4 bytes, tile rows of kT16W pixels + one
+// repeated, so that a footprint is one 8-byte load inside one tile row.  (7 + 1) x 4 B = 32 B per row, 4 rows per tile: the
+// same 7-pixel rows as the default byte tiles (the divide by 7 is a 24-bit multiply) and the row index is a shift.
+constexpr int kT16W = 7;
+constexpr int kT16E = kT16W + 1;
+constexpr int kT16B = 4;
+constexpr int kT16H = 128 / (kT16E * kT16B);
+DVP_HD int img16_tiles_x(int W) { return (W + 2 * kImgPad + kT16W - 1) / kT16W; }
+DVP_HD int img16_tiles_y(int H) { return (H + 2 * kImgPad + kT16H - 1) / kT16H; }
+// byte offset of the footprint {I(i0,j0), I(i0,j0+1), I(i0+1,j0), I(i0+1,j0+1)} inside a tiled binary16 plane; i0, j0 >= -PAD.
+// The plane is smaller than a row-pair plane (4 * 8/7 against 8 bytes per pixel), which dvp_ctx_create keeps below 4 GiB.
+DVP_HD unsigned img16_offset(int tiles_x, int i0, int j0) {
+	const unsigned px = (unsigned)(i0 + kImgPad), py = (unsigned)(j0 + kImgPad);
+	constexpr unsigned kMul = 74899u;   // x / 7 == (x * kMul) >> 19 for x < 70000
+#if defined(__HIP_DEVICE_COMPILE__)
+	const unsigned tx = __umul24(px, kMul) >> 19;
+	const unsigned ex = px - __umul24((unsigned)kT16W, tx);
+	const unsigned tile = __umul24(py / (unsigned)kT16H, (unsigned)tiles_x) + tx;
+#else
+	const unsigned tx = (px * kMul) >> 19;
+	const unsigned ex = px - (unsigned)kT16W * tx;
+	const unsigned tile = (py / (unsigned)kT16H) * (unsigned)tiles_x + tx;
+#endif
+	return (tile << 7) + (py % (unsigned)kT16H) * (unsigned)(kT16B * kT16E) + ex * (unsigned)kT16B;
+}
+// binary16 bits -> binary32, integer operations only (the host build has no _Float16; also the test's reference decoder)
+DVP_HD float half_bits_to_float(uint32_t h) {
+	const uint32_t s = (h & 0x8000u) << 16, e = (h >> 10) & 31u, m = h & 1023u;
+	uint32_t b;
+	if (e == 31u) b = s | 0x7F800000u | (m << 13);
+	else if (e != 0u) b = s | ((e + 112u) << 23) | (m << 13);
+	else if (m == 0u) b = s;
+	else {   // subnormal: m * 2^-24, normalised
+		int k = 0;
+		uint32_t mm = m;
+		while (!(mm & 1024u)) { mm <<= 1; ++k; }
+		b = s | ((uint32_t)(113 - k) << 23) | ((mm & 1023u) << 13);
+	}
+	float f;
+	memcpy(&f, &b, 4);
+	return f;
+}
+DVP_HD float half_lo(uint32_t t) {
+#if defined(__HIP_DEVICE_COMPILE__)
+	return (float)__builtin_bit_cast(_Float16, (unsigned short)(t & 0xFFFFu));   // v_cvt_f32_f16
+#else
+	return half_bits_to_float(t & 0xFFFFu);
+#endif
+}
+DVP_HD float half_hi(uint32_t t) {
+#if defined(__HIP_DEVICE_COMPILE__)
+	return (float)__builtin_bit_cast(_Float16, (unsigned short)(t >> 16));       // v_cvt_f32_f16 with SDWA WORD_1
+#else
+	return half_bits_to_float(t >> 16);
+#endif
+}
+// The upload rule for one tile element {a, b} = {I(x,y), I(x,y+1)} (dvp_pairs_to_tiles, the format test of the upload):
+// returns bit 0 when a texel is not an integer in [0, 255] (the set cannot be format 1) and bit 1 when a texel is not a binary16
+// value in [0, 255] — NaN, out of range, or not representable (the set cannot be format 2); *h = the binary16 pair (low half a)
+// whenever bit 1 is clear.  Integer operations on the binary32 bits, the same on the device and the host.
+DVP_HD uint32_t half_encode(float v, bool* exact) {
+	uint32_t b;
+	memcpy(&b, &v, 4);
+	const uint32_t s = (b >> 16) & 0x8000u, mag = b & 0x7FFFFFFFu;
+	*exact = !(v < 0.0f) && v <= 255.0f;    // (NaN fails the second test)
+	if (mag == 0u) return s;
+	const int e = (int)(mag >> 23) - 127;    // > 7 is out of range, -127 is a binary32 subnormal (below 2^-24)
+	const uint32_t sig = (mag & 0x7FFFFFu) | 0x800000u;
+	if (e >= -14) {                          // binary16 normal: 10 of the 23 fraction bits survive
+		if (mag & 0x1FFFu) *exact = false;
+		return s | ((uint32_t)(e + 15) << 10) | ((mag >> 13) & 1023u);
+	}
+	const int sh = -e - 1;                   // binary16 subnormal: m = sig * 2^(e + 1)
+	if (sh >= 24 || (sig & ((1u << sh) - 1u))) { *exact = false; return s; }
+	return s | (sig >> sh);
+}
+DVP_HD unsigned tile_pair_rule(float a, float b, uint32_t* h) {
+	const bool int_ok = a >= 0.0f && a <= 255.0f && b >= 0.0f && b <= 255.0f && a == floorf(a) && b == floorf(b);
+	bool ea, eb;
+	const uint32_t ha = half_encode(a, &ea), hb = half_encode(b, &eb);
+	*h = ha | (hb << 16);
+	return (int_ok ? 0u : 1u) | (ea && eb ? 0u : 2u);
+}
 template <int FMT> DVP_HD const void* img_plane(const Dev& d, int v);
 template <> DVP_HD const void* img_plane<0>(const Dev& d, int v) { return d.images + (size_t)v * d.plane_stride * 2; }
 template <> DVP_HD const void* img_plane<1>(const Dev& d, int v) { return d.images8 + (size_t)v * d.img8_plane_bytes; }
+template <> DVP_HD const void* img_plane<2>(const Dev& d, int v) { return reinterpret_cast<const char*>(d.images16) + (size_t)v * d.img16_plane_bytes; }
 // `off`: byte offset of the footprint inside the plane of the format (tex_coord_t)
 template <int FMT> DVP_HD void load_quad_t(const void* base, unsigned off, float* a, float* b, float* c, float* e);
 template <> DVP_HD void load_quad_t<0>(const void* base, unsigned off, float* a, float* b, float* c, float* e) {
@@ -299,11 +390,27 @@ template <> DVP_HD void load_quad_t<1>(const void* base, unsigned off, float* a,
 #endif
 	*a = (float)(t & 255u); *b = (float)((t >> 8) & 255u); *c = (float)((t >> 16) & 255u); *e = (float)(t >> 24);
 }
+template <> DVP_HD void load_quad_t<2>(const void* base, unsigned off, float* a, float* b, float* c, float* e) {
+	// one 8-byte load at a 4-byte aligned address, four v_cvt_f32_f16 (two of them on the high halves)
+	uint32_t t[2];
+#if defined(__HIP_DEVICE_COMPILE__)
+	typedef uint32_t u32x2_a4 __attribute__((ext_vector_type(2), aligned(4)));
+	const u32x2_a4 v = *reinterpret_cast<const u32x2_a4*>(static_cast<const char*>(base) + off);
+	t[0] = v.x; t[1] = v.y;
+#else
+	memcpy(t, static_cast<const char*>(base) + off, 8);
+#endif
+	*a = half_lo(t[0]); *b = half_hi(t[0]); *c = half_lo(t[1]); *e = half_hi(t[1]);
+}
 // texel (ix, iy) of the reference image (plane 0), clamp-to-edge
 template <int FMT> DVP_HD float ref_texel_t(const Dev& d, int ix, int iy);
 template <> DVP_HD float ref_texel_t<0>(const Dev& d, int ix, int iy) { return img_texel(d.images, d.org, d.pitch, d.width, d.height, ix, iy); }
 template <> DVP_HD float ref_texel_t<1>(const Dev& d, int ix, int iy) {
 	return (float)d.images8[img8_offset(d.img8_tiles_x, clampi(ix, 0, d.width - 1), clampi(iy, 0, d.height - 1))];
+}
+template <> DVP_HD float ref_texel_t<2>(const Dev& d, int ix, int iy) {
+	const unsigned off = img16_offset(d.img16_tiles_x, clampi(ix, 0, d.width - 1), clampi(iy, 0, d.height - 1));
+	return half_lo(d.images16[off >> 2]);
 }
 // clamp(v, lo, hi) with NaN -> lo: fminf(fmaxf(v, lo), hi).  One v_med3_f32 on the device (with a
 // NaN operand the instruction returns min3 of the other two == lo).
@@ -398,7 +505,7 @@ template <int FMT, int SMP>
 DVP_HD void tex_coord_t(const Dev& d, float x, float y, unsigned* off, TapW<SMP>* w) {
 	int i0, j0;
 	tex_origin(d.width, d.height, x, y, &i0, &j0, w);
-	*off = FMT ? img8_offset(d.img8_tiles_x, i0, j0) : tex_offset(d.pitch, i0, j0);
+	*off = FMT == 1 ? img8_offset(d.img8_tiles_x, i0, j0) : (FMT == 2 ? img16_offset(d.img16_tiles_x, i0, j0) : tex_offset(d.pitch, i0, j0));
 }
 // q = {I(i,j), I(i,j+1), I(i+1,j), I(i+1,j+1)}
 DVP_HD float tex_lerp(float a, float b, float t00, float t01, float t10, float t11) {

@@ -439,6 +439,11 @@ extern "C" __global__ void __launch_bounds__(64, DVP_LB_WEAK) dvp_weak_update_wa
 extern "C" __global__ void __launch_bounds__(64, DVP_LB_WEAK) dvp_weak_update_wave_exact_u8(const Dev d, const ListArgs a) { weak_wave_body<1, 1, 1>(d, a); }
 extern "C" __global__ void __launch_bounds__(64, DVP_LB_WEAK) dvp_weak_update_wave_u8_notab(const Dev d, const ListArgs a) { weak_wave_body<0, 1, 0>(d, a); }
 extern "C" __global__ void __launch_bounds__(64, DVP_LB_WEAK) dvp_weak_update_wave_exact_u8_notab(const Dev d, const ListArgs a) { weak_wave_body<1, 1, 0>(d, a); }
+// ... and the binary16 planes (Dev::images16: down-sampled levels of 8-bit images)
+extern "C" __global__ void __launch_bounds__(64, DVP_LB_WEAK) dvp_weak_update_wave_f16(const Dev d, const ListArgs a) { weak_wave_body<0, 2, 1>(d, a); }
+extern "C" __global__ void __launch_bounds__(64, DVP_LB_WEAK) dvp_weak_update_wave_exact_f16(const Dev d, const ListArgs a) { weak_wave_body<1, 2, 1>(d, a); }
+extern "C" __global__ void __launch_bounds__(64, DVP_LB_WEAK) dvp_weak_update_wave_f16_notab(const Dev d, const ListArgs a) { weak_wave_body<0, 2, 0>(d, a); }
+extern "C" __global__ void __launch_bounds__(64, DVP_LB_WEAK) dvp_weak_update_wave_exact_f16_notab(const Dev d, const ListArgs a) { weak_wave_body<1, 2, 0>(d, a); }
 // The same launch site as EIGHT launches (dvp_weak_phased.hpp): the evaluation launches E0 / E1 / E2a / E2b take one wave per
 // GROUP of a.group consecutive WEAK pixels of the list, the per-pixel decisions D1 / D2 / D3 and the final plain-NCC cost E3
 // run one LANE per WEAK pixel.
@@ -469,7 +474,9 @@ __device__ __forceinline__ void weak_group_body(const Dev& d, const ListArgs& a)
 	extern "C" __global__ void __launch_bounds__(64, DVP_LB_WEAK) NAME(const Dev d, const ListArgs a) { weak_group_body<0, 0, MODE>(d, a); }           \
 	extern "C" __global__ void __launch_bounds__(64, DVP_LB_WEAK) NAME##_exact(const Dev d, const ListArgs a) { weak_group_body<1, 0, MODE>(d, a); }   \
 	extern "C" __global__ void __launch_bounds__(64, DVP_LB_WEAK) NAME##_u8(const Dev d, const ListArgs a) { weak_group_body<0, 1, MODE>(d, a); }      \
-	extern "C" __global__ void __launch_bounds__(64, DVP_LB_WEAK) NAME##_exact_u8(const Dev d, const ListArgs a) { weak_group_body<1, 1, MODE>(d, a); }
+	extern "C" __global__ void __launch_bounds__(64, DVP_LB_WEAK) NAME##_exact_u8(const Dev d, const ListArgs a) { weak_group_body<1, 1, MODE>(d, a); }    \
+	extern "C" __global__ void __launch_bounds__(64, DVP_LB_WEAK) NAME##_f16(const Dev d, const ListArgs a) { weak_group_body<0, 2, MODE>(d, a); }     \
+	extern "C" __global__ void __launch_bounds__(64, DVP_LB_WEAK) NAME##_exact_f16(const Dev d, const ListArgs a) { weak_group_body<1, 2, MODE>(d, a); }
 DVP_WEAK_PHASE_KERNELS(dvp_weak_eval_candidates, 0)
 DVP_WEAK_PHASE_KERNELS(dvp_weak_eval_planes, 1)
 DVP_WEAK_PHASE_KERNELS(dvp_weak_eval_first_view, 2)
@@ -523,6 +530,7 @@ extern "C" __global__ void __launch_bounds__(256) dvp_weak_anchor_table(const De
 	// (the records written through an LDS transpose — eight whole records per store instruction instead of 16 bytes into each of
 	// 64 lines — measure the same 19 ms per cfg3 pass: the launch does not wait for its stores)
 	if (d.images8) build_anchor_record<1>(d, d.weak_list[a.base + t], v0, k);
+	else if (d.images16) build_anchor_record<2>(d, d.weak_list[a.base + t], v0, k);
 	else build_anchor_record<0>(d, d.weak_list[a.base + t], v0, k);
 }
 
@@ -563,7 +571,9 @@ extern "C" __global__ void dvp_interleave_rows(const float* __restrict__ in, flo
 	reinterpret_cast<float2*>(out + (size_t)pl * plane_stride * 2)[(size_t)y * pitch + x] = v;
 }
 
-// row-pair float planes -> tiled byte planes (Dev::images8); *inexact is raised when a texel is not an integer in [0, 255].
+// row-pair float planes -> tiled byte planes (Dev::images8), and the format probe of the upload: *inexact collects the bits of
+// tile_pair_rule (dvp_dev.hpp) over every element — bit 0: some texel is not an integer in [0, 255] (no byte planes), bit 1: some
+// texel is not a binary16 value in [0, 255] (no binary16 planes either).
 // One thread per tile element: tile (tx, ty), element (ex, ey) = padded pixel (tx*7 + ex, ty*8 + ey), clamped to the
 // padded plane (the right-most column of a tile repeats the first pixel of the next tile).
 extern "C" __global__ void dvp_pairs_to_tiles(const float* __restrict__ pairs, uint8_t* __restrict__ out, int PW, int PH, int pitch, size_t plane_stride,
@@ -580,12 +590,35 @@ extern "C" __global__ void dvp_pairs_to_tiles(const float* __restrict__ pairs, u
 	const float* plane = pairs + (size_t)pl * plane_stride * 2;
 	const float2 v = reinterpret_cast<const float2*>(plane)[(size_t)sy * pitch + sx];
 	const float2 u = reinterpret_cast<const float2*>(plane)[(size_t)sy * pitch + min(sx + 1, PW - 1)];
-	const bool ok = v.x >= 0.0f && v.x <= 255.0f && v.y >= 0.0f && v.y <= 255.0f && v.x == floorf(v.x) && v.y == floorf(v.y);
-	if (!ok) { if (*inexact == 0) atomicOr(inexact, 1); return; }
+	uint32_t h;
+	const unsigned bad = tile_pair_rule(v.x, v.y, &h);
+	if (bad) {
+		if ((*inexact & bad) != bad) atomicOr(inexact, (int)bad);
+		if (bad & 1u) return;
+	}
 	uint8_t* dst = out + ((size_t)pl * tiles_x * tiles_y + tile) * 128 + (size_t)e * kT8B;
 	dst[0] = (uint8_t)v.x;
 	dst[1] = (uint8_t)v.y;
 	if (kT8Quad) { dst[2] = (uint8_t)u.x; dst[3] = (uint8_t)u.y; }
+}
+
+// row-pair float planes -> tiled binary16 planes (Dev::images16), after dvp_pairs_to_tiles found every texel binary16-exact.
+// One thread per tile element: tile (tx, ty), element (ex, ey) = padded pixel (tx*7 + ex, ty*4 + ey), clamped to the padded plane.
+extern "C" __global__ void dvp_pairs_to_tiles16(const float* __restrict__ pairs, uint32_t* __restrict__ out, int PW, int PH, int pitch, size_t plane_stride,
+                                                int tiles_x, int tiles_y, int n_planes) {
+	constexpr int kPer = kT16E * kT16H;   // 32 elements per tile
+	const size_t per_plane = (size_t)tiles_x * tiles_y * kPer;
+	const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= per_plane * n_planes) return;
+	const int pl = (int)(i / per_plane);
+	const size_t r = i - (size_t)pl * per_plane;
+	const int tile = (int)(r / kPer), e = (int)(r % kPer);
+	const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
+	const int sx = min(tx * kT16W + (e % kT16E), PW - 1), sy = min(ty * kT16H + (e / kT16E), PH - 1);
+	const float2 v = reinterpret_cast<const float2*>(pairs + (size_t)pl * plane_stride * 2)[(size_t)sy * pitch + sx];
+	uint32_t h;
+	(void)tile_pair_rule(v.x, v.y, &h);
+	out[((size_t)pl * tiles_x * tiles_y + tile) * (128 / 4) + e] = h;
 }
 
 // byte edge map -> 32x32 bit tiles (one thread per 32-bit word)
@@ -1100,6 +1133,9 @@ struct dvp_ctx {
 	int* images8_flag = nullptr;
 	bool images8_ok = false;
 	bool no_images8 = false;        // DVP_NO_IMAGES8 in the environment: keep the float planes for every kernel (A/B measurements)
+	uint32_t* images16 = nullptr;   // the same as binary16 pairs (Dev::images16), allocated at the first upload (or dvp_ctx_reserve) that wants them
+	bool images16_ok = false;       // the last upload is binary16-exact and not 8-bit exact: the weak update reads images16
+	bool no_images16 = false;       // DVP_NO_IMAGES16 in the environment: such sets keep the float planes (A/B measurements)
 	float* image_stage = nullptr;   // plain padded planes the uploads land in before dvp_interleave_rows
 	float* depths = nullptr;
 	uint32_t* edge_bits = nullptr;  // bit-tiled copy of `edge`, rebuilt before the launches that walk lines
@@ -1200,12 +1236,16 @@ static void dfree(dvp_ctx* c, T** p) {
 	*p = nullptr;
 }
 
+static size_t img16_plane_bytes(int W, int H) { return (size_t)img16_tiles_x(W) * img16_tiles_y(H) * 128; }
+
 static void sync_dev_struct(dvp_ctx* c) {
 	Dev& d = c->d;
 	d.width = c->W; d.height = c->H; d.num_images = c->NI; d.pitch = c->pitch;
 	d.org = kImgPad * c->pitch + kImgPad;
 	d.plane_stride = (size_t)c->pitch * (c->H + 2 * kImgPad);
-	d.images = c->images; d.images8 = c->images8_ok ? c->images8 : nullptr; d.img8_tiles_x = img8_tiles_x(c->W); d.img8_plane_bytes = (size_t)img8_tiles_x(c->W) * img8_tiles_y(c->H) * 128; d.depths = c->depths; d.cameras = c->cameras; d.views = c->views; d.sector_taps = c->sector_taps; d.sector_start = c->sector_start;
+	d.images = c->images; d.images8 = c->images8_ok ? c->images8 : nullptr; d.img8_tiles_x = img8_tiles_x(c->W); d.img8_plane_bytes = (size_t)img8_tiles_x(c->W) * img8_tiles_y(c->H) * 128;
+	d.images16 = c->images16_ok ? c->images16 : nullptr; d.img16_tiles_x = img16_tiles_x(c->W); d.img16_plane_bytes = img16_plane_bytes(c->W, c->H);
+	d.depths = c->depths; d.cameras = c->cameras; d.views = c->views; d.sector_taps = c->sector_taps; d.sector_start = c->sector_start;
 	d.search_pos = c->search_pos;
 	d.sweep_px0 = 0; d.sweep_row0 = 0; d.sweep_row1 = 0;   // (set per band by the sweep passes' launches)
 	d.sweep_rec = c->sweep_rec; d.sweep_cost = c->sweep_cost; d.sweep_pc = c->sweep_pc; d.slot_costs = c->slot_costs; d.strong_rec = c->strong_rec; d.half_w = (c->W + 1) / 2;
@@ -1218,6 +1258,12 @@ static void sync_dev_struct(dvp_ctx* c) {
 	d.weak_list = c->weak_list;
 	d.weak_rec = c->weak_rec; d.weak_ctab = c->weak_ctab; d.weak_ev = c->weak_ev;
 	d.eval_counter = c->profiling ? c->eval_counter : nullptr;
+}
+
+// the binary16 planes, allocated once per context and only by the contexts that see such image sets (or are told to expect them)
+static int ensure_images16(dvp_ctx* c) {
+	if (c->images16) return 0;
+	return dalloc(c, &c->images16, img16_plane_bytes(c->W, c->H) / 4 * c->NI, false);
 }
 
 static int set_device(dvp_ctx* c) {
@@ -1244,6 +1290,7 @@ int dvp_ctx_create(int device, int width, int height, int num_images, dvp_ctx** 
 	dvp_ctx* c = new dvp_ctx();
 	c->device = device; c->W = width; c->H = height; c->NI = num_images;
 	c->no_images8 = getenv("DVP_NO_IMAGES8") != nullptr;
+	c->no_images16 = getenv("DVP_NO_IMAGES16") != nullptr;
 	if (const char* e = getenv("DVP_STRONG_SPLIT")) c->strong_split = atoi(e) != 0;
 	if (const char* e = getenv("DVP_REFINE_LANES")) c->refine_lanes = atoi(e) != 0;
 	if (const char* e = getenv("DVP_EVAL_ITEMS")) c->eval_items = atoi(e) != 0;
@@ -1387,17 +1434,26 @@ static int upload_planes(dvp_ctx* c, float* dst, const float* const* src, int pi
 		hipLaunchKernelGGL(dvp_interleave_rows, dim3((unsigned)((c->pitch + 255) / 256), (unsigned)PH, (unsigned)c->NI), dim3(256), 0, c->stream,
 		                   dst, pairs, PH, c->pitch, stride, c->NI);
 		HIP_TRY(c, hipGetLastError());
-		// byte planes for 8-bit exact image sets (Dev::images8)
+		// byte planes for 8-bit exact image sets (Dev::images8), binary16 planes for binary16-exact ones (Dev::images16)
 		HIP_TRY(c, hipMemsetAsync(c->images8_flag, 0, sizeof(int), c->stream));
 		const int t8x = img8_tiles_x(c->W), t8y = img8_tiles_y(c->H);
 		const size_t n = (size_t)t8x * t8y * 64 * c->NI;
 		hipLaunchKernelGGL(dvp_pairs_to_tiles, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, pairs, c->images8, c->W + 2 * kImgPad, PH, c->pitch, stride,
 		                   t8x, t8y, c->NI, c->images8_flag);
 		HIP_TRY(c, hipGetLastError());
-		int inexact = 1;
+		int inexact = 3;
 		HIP_TRY(c, hipMemcpyAsync(&inexact, c->images8_flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
 		HIP_TRY(c, hipStreamSynchronize(c->stream));
 		c->images8_ok = inexact == 0 && !c->no_images8;
+		c->images16_ok = inexact == 1 && !c->no_images8 && !c->no_images16;
+		if (c->images16_ok) {
+			if (ensure_images16(c)) { c->images16_ok = false; sync_dev_struct(c); return 1; }
+			const int t16x = img16_tiles_x(c->W), t16y = img16_tiles_y(c->H);
+			const size_t n16 = (size_t)t16x * t16y * (kT16E * kT16H) * c->NI;
+			hipLaunchKernelGGL(dvp_pairs_to_tiles16, dim3((unsigned)((n16 + 255) / 256)), dim3(256), 0, c->stream, pairs, c->images16, c->W + 2 * kImgPad, PH, c->pitch, stride,
+			                   t16x, t16y, c->NI);
+			HIP_TRY(c, hipGetLastError());
+		}
 		sync_dev_struct(c);
 	}
 	HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -1583,7 +1639,7 @@ int dvp_reset_state(dvp_ctx* c) {
 // weak_info stay valid because the same weak map comes back) and its restore, which also returns the
 // pass-internal buffers to their freshly-uploaded content.  Lets a caller run the same pass again
 // from identical inputs (bench steps, A/B checks) without a host round trip.
-int dvp_image_format(const dvp_ctx* c) { return (c && c->images8_ok) ? 1 : 0; }
+int dvp_image_format(const dvp_ctx* c) { return !c ? 0 : (c->images8_ok ? 1 : (c->images16_ok ? 2 : 0)); }
 int dvp_save_state(dvp_ctx* c) {
 	if (set_device(c)) return 1;
 	const size_t L = c->L;
@@ -1867,9 +1923,9 @@ static int launch_stage(dvp_ctx* c, int stage, int iter, int colour, bool fused 
 				// (a few thousand WEAK pixels do not fill the machine in any form: the eight launches then cost more than they save —
 				// 4.4 against 1.7 ms for the weak updates of a 3104x2064 view with 0.2 % WEAK pixels — and the one-wave kernel takes them)
 				if (c->d.anchor_tab && c->weak_phased && (la.count >= c->weak_phased_min || c->weak_phased_min <= 0)) {
-					const bool u8 = c->images8_ok;
+					const int fmt = dvp_image_format(c);
 					const dim3 w64(64), lg64((la.count + 63) / 64);
-#define DVP_PICK(NAME) (ex ? (u8 ? NAME##_exact_u8 : NAME##_exact) : (u8 ? NAME##_u8 : NAME))
+#define DVP_PICK(NAME) (ex ? (fmt == 1 ? NAME##_exact_u8 : (fmt == 2 ? NAME##_exact_f16 : NAME##_exact)) : (fmt == 1 ? NAME##_u8 : (fmt == 2 ? NAME##_f16 : NAME)))
 #define DVP_GROUP_LAUNCH(NAME, PHASE) { la.group = std::min(c->weak_group[PHASE], PHASE == 0 ? kGrpWide : kGrp); la.run = c->weak_run[PHASE]; hipLaunchKernelGGL(DVP_PICK(NAME), dim3((la.count + la.group - 1) / la.group), w64, 0, c->stream, c->d, la); }
 					DVP_GROUP_LAUNCH(dvp_weak_eval_candidates, 0)
 					hipLaunchKernelGGL(dvp_weak_select_views, lg, block, 0, c->stream, c->d, la);
@@ -1883,9 +1939,11 @@ static int launch_stage(dvp_ctx* c, int stage, int iter, int colour, bool fused 
 #undef DVP_PICK
 				} else if (c->d.anchor_tab) {
 					if (c->images8_ok) hipLaunchKernelGGL(ex ? dvp_weak_update_wave_exact_u8 : dvp_weak_update_wave_u8, dim3(la.count), dim3(64), 0, c->stream, c->d, la);
+					else if (c->images16_ok) hipLaunchKernelGGL(ex ? dvp_weak_update_wave_exact_f16 : dvp_weak_update_wave_f16, dim3(la.count), dim3(64), 0, c->stream, c->d, la);
 					else hipLaunchKernelGGL(ex ? dvp_weak_update_wave_exact : dvp_weak_update_wave, dim3(la.count), dim3(64), 0, c->stream, c->d, la);
 				} else {
 					if (c->images8_ok) hipLaunchKernelGGL(ex ? dvp_weak_update_wave_exact_u8_notab : dvp_weak_update_wave_u8_notab, dim3(la.count), dim3(64), 0, c->stream, c->d, la);
+					else if (c->images16_ok) hipLaunchKernelGGL(ex ? dvp_weak_update_wave_exact_f16_notab : dvp_weak_update_wave_f16_notab, dim3(la.count), dim3(64), 0, c->stream, c->d, la);
 					else hipLaunchKernelGGL(ex ? dvp_weak_update_wave_exact_notab : dvp_weak_update_wave_notab, dim3(la.count), dim3(64), 0, c->stream, c->d, la);
 				}
 				break;
@@ -2013,6 +2071,7 @@ int dvp_ctx_reserve(dvp_ctx* c, int weak_pixels, int flags) {
 	if (set_device(c)) return 1;
 	if (flags & 1) ensure_strong_split_buffers(c);
 	if (flags & 2) ensure_sweep_buffers(c);
+	if ((flags & 4) && !c->no_images8 && !c->no_images16 && ensure_images16(c)) return 1;
 	if (weak_pixels > 0) {
 		const size_t wc = std::min<size_t>((size_t)weak_pixels, c->L);
 		if (grow_anchor_table(c, wc)) return 1;

@@ -155,13 +155,13 @@ dvp_ctx* take_prewarmed(int device, int w, int h, int ni) {   // nullptr when th
 	return c;
 }
 }
-void APD::PrewarmContext(int w, int h, int ni) {
+void APD::PrewarmContext(int w, int h, int ni, int scale_size) {
 	std::lock_guard<std::mutex> lock(g_ctx_mutex);
 	if (g_prewarm.active || w <= 0 || h <= 0) return;
 	g_prewarm.active = true;
 	g_prewarm.device = g_device; g_prewarm.w = w; g_prewarm.h = h; g_prewarm.ni = ni;
 	const int device = g_device;
-	g_prewarm.worker = std::thread([device, w, h, ni]() {
+	g_prewarm.worker = std::thread([device, w, h, ni, scale_size]() {
 		dvp_ctx* c = nullptr;
 		if (dvp_ctx_create(device, w, h, ni, &c) != 0) c = nullptr;   // (the view that needs it will try again and report)
 		// ... with its optional buffers: the next level's first views would otherwise allocate them inside their launches (the split
@@ -171,11 +171,12 @@ void APD::PrewarmContext(int w, int h, int ni) {
 		// what the levels of a coarse-to-fine schedule hold, at most 90 % of the view: 48 GB below 8 Mpx — all of a 1552x1032 level
 		// (its passes are 83-97 % WEAK), 55 % at 3104x2064 (17-38 %) — and 24 GB above — 7 % of a 25-Mpx view with 9 sources (1-6 %).
 		// A view with more grows the table once, inside its weak update (1.1-1.7 s with the 16 GB of the first version at 3104x2064).
+		// A down-sampled level (scale_size > 1) also gets the binary16 image planes its images will take (dvp_image_format 2).
 		if (c) {
 			const long long per_px = 1408ll * (ni - 1) + 544 + 32ll * (ni - 1);
 			const long long budget = (long long)w * h <= 8000000ll ? 48000000000ll : 24000000000ll;
 			const long long room = std::min<long long>((long long)w * h * 9 / 10, budget / per_px);
-			(void)dvp_ctx_reserve(c, (int)std::min<long long>(room, 2000000000ll), 3);
+			(void)dvp_ctx_reserve(c, (int)std::min<long long>(room, 2000000000ll), scale_size > 1 ? 7 : 3);
 		}
 		g_prewarm.ctx = c;
 	});
@@ -710,6 +711,7 @@ void APD::CudaSpaceInitialization() {
 		for (int i = 0; i < num_images; ++i) ptrs[i] = images[i].ptr<float>(0);
 		DVP_SAFE_CALL(ctx, dvp_upload_images(ctx, ptrs.data(), width));
 	}
+	image_format = dvp_image_format(ctx);
 	lap("images upload");
 	if (params_host.geom_consistency) {
 		if (!depths_device.empty()) {

@@ -125,7 +125,7 @@ public:
 	static void InsertCachedImage(const Problem& problem, int image_id, const Mat& image, int orig_cols, int orig_rows);
 	static Mat DecodedGray(const path& image_file);   // cv::imread(GRAYSCALE) through a per-file cache (read-only result)
 	static void PrefetchDecoded(const std::vector<path>& image_files);   // decode in the background (detached worker threads)
-	static void PrewarmContext(int width, int height, int num_images);   // the next level's engine context, made by a helper thread
+	static void PrewarmContext(int width, int height, int num_images, int scale_size = 1);   // the next level's engine context, made by a helper thread
 	static bool LevelSize(const Problem& problem, int scale, int* width, int* height);
 	static void PrefetchLevelImages(std::vector<Problem> views, int scale);   // float images of a level ahead of its first pass
 	static void ReserveImageCache(size_t views);   // the cache holds at least this many images before it evicts
@@ -143,6 +143,7 @@ public:
 	static void ClearResidentDepths();
 	static void SetResidentDownloader(void (*copy)(float* host, const float* device, size_t count));   // device -> host copy used when a resident map of another size has to be rescaled on the host
 	const DvpTimings& GetTimings() const { return timings; }
+	int GetImageFormat() const { return image_format; }   // dvp_image_format after the view's image upload
 
 private:
 	int num_images = 0;
@@ -166,5 +167,6 @@ private:
 	dvp_ctx* ctx = nullptr;
 	int ctx_device = 0;
 	DvpTimings timings{};
+	int image_format = 0;
 };
 #endif

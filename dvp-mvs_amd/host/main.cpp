@@ -286,7 +286,9 @@ ViewResult ProcessProblem(const Problem& problem, const std::function<float*(int
 		ViewLog() << "  [gpu]";
 		for (int i = 0; i < DVP_ST_COUNT; ++i)
 			if (t.stage_ms[i] > 0.0) { ViewLog() << " " << names[i] << " " << t.stage_ms[i]; sum += t.stage_ms[i]; }
-		ViewLog() << " | sites " << sum << " of total " << t.total_ms << " ms" << std::endl;
+		static const char* formats[3] = { "f32", "u8", "f16" };   // the image planes the weak update read (dvp_image_format)
+		const int fmt = APD.GetImageFormat();
+		ViewLog() << " | sites " << sum << " of total " << t.total_ms << " ms | images " << formats[fmt >= 0 && fmt <= 2 ? fmt : 0] << std::endl;
 	}
 	ViewLog() << "Cost time: " << std::chrono::duration_cast<std::chrono::milliseconds>(end - start).count() << " ms (GPU RunPatchMatch "
 	          << t.total_ms << " ms, " << (double)width * height * problem.params.max_iterations / (t.total_ms * 1e3) << " Mpx/s/iter)" << std::endl;
@@ -583,7 +585,7 @@ int main(int argc, char** argv) {
 		// last pass of a level: the next level's context and float images are made by helper threads while the GPU works
 		if (!opt.sync_io && it + 1 < plan.size() && plan[it + 1].scale != pass.scale && !owned.empty()) {
 			int nw = 0, nh = 0;
-			if (APD::LevelSize(*owned[0], plan[it + 1].scale, &nw, &nh)) APD::PrewarmContext(nw, nh, (int)owned[0]->src_image_ids.size() + 1);
+			if (APD::LevelSize(*owned[0], plan[it + 1].scale, &nw, &nh)) APD::PrewarmContext(nw, nh, (int)owned[0]->src_image_ids.size() + 1, plan[it + 1].scale);
 			std::vector<Problem> mine_next;
 			for (const Problem* p : owned) mine_next.push_back(*p);
 			APD::PrefetchLevelImages(mine_next, plan[it + 1].scale);

@@ -95,3 +95,68 @@ def weak_tiles(W, H, frac, flat=None, seed=0, tile=32, border=8):
     mask[:, :border] = False
     mask[:, -border:] = False
     return mask
+
+
+def box2x2(images):
+    """[NI, H, W] float32 (numpy or torch) -> the float32 mean of I(x,y), I(x+1,y), I(x,y+1), I(x+1,y+1) (the last column / row
+    repeated): from 8-bit grey levels every texel is a multiple of 0.25 in [0, 255], as at a power-of-two down-sampled pyramid
+    level (ResizeLinear of the decoded image), and the geometry stays within half a pixel of the scene's."""
+    if hasattr(images, "clone"):
+        import torch
+        right = torch.cat([images[:, :, 1:], images[:, :, -1:]], 2)
+        below = torch.cat([images[:, 1:, :], images[:, -1:, :]], 1)
+        diag = torch.cat([right[:, 1:, :], right[:, -1:, :]], 1)
+        return (((images + right) + below) + diag) * 0.25
+    images = np.asarray(images, np.float32)
+    right = np.concatenate([images[:, :, 1:], images[:, :, -1:]], 2)
+    below = np.concatenate([images[:, 1:, :], images[:, -1:, :]], 1)
+    diag = np.concatenate([right[:, 1:, :], right[:, -1:, :]], 1)
+    return ((((images + right) + below) + diag) * np.float32(0.25)).astype(np.float32)
+
+
+def quarter_level_pass(W, H, S, iters, weak_frac, images="box", env=None, seed=77):
+    """The weak-update regime of the default schedule's last level: a REFINE_ITER pass with geometric consistency at W x H on the
+    GPU, ~weak_frac of the view WEAK, inputs uploaded and saved (dvp_save_state), not run.  images: "box" = the scene's 8-bit
+    images box-filtered 2x2 (box2x2: dvp_image_format 2), "int" = the 8-bit images themselves (format 1).  env: engine switches
+    set while the context is created (None = unset).  Returns dict(g, sc, W, H, S, iters, params, edge, label, refine=True)."""
+    import os
+    import torch
+    from . import capi as _capi
+    dev = torch.device("cuda", 0)
+    sc = synth.make_scene_torch(W, H, S, dev)
+    if images == "box":
+        sc["images"] = box2x2(sc["images"]).contiguous()
+    edge_t, label_t = synth.view_priors_torch(sc["sids"][0], sc["flats"][0])
+    edge, label, flat = edge_t.cpu().numpy(), label_t.cpu().numpy(), sc["flats"][0].cpu().numpy()
+    old = {}
+    for k, v in (env or {}).items():
+        old[k] = os.environ.get(k)
+        if v is None:
+            os.environ.pop(k, None)
+        else:
+            os.environ[k] = v
+    try:
+        g = _capi.Context(W, H, S + 1)
+    finally:
+        for k, v in old.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+    L = W * H
+    g.set_images_device([sc["images"][i].data_ptr() for i in range(S + 1)], W)
+    g.set_cameras(sc["cameras"])
+    p1 = first_init_params(S, iters)
+    g.set_params(p1)
+    g.set_seed(seed)
+    g.upload_state(planes=np.zeros((L, 4), np.float32), views=np.zeros(L, np.uint32), weak=np.full(L, synth.STRONG, np.uint8),
+                   edge=edge, label=label, radius=np.full(L, 5, np.int32))
+    g.run_patchmatch()
+    st = hand_over(g.get("planes"), g.get("selected_views"), g.get("weak_info"), g.get("radius"), p1, W, H,
+                   extra_weak=weak_tiles(W, H, weak_frac, flat))
+    params = refine_iter_params(S, iters, round_index=2)
+    g.set_params(params)
+    g.set_depths_device([sc["depth_gt"][i].data_ptr() for i in range(S + 1)], W)
+    g.upload_state(planes=st[0], views=st[1], weak=st[2], radius=st[3])
+    g.save_state()
+    return dict(g=g, sc=sc, W=W, H=H, S=S, iters=iters, params=params, edge=edge, label=label, refine=True)

@@ -174,8 +174,9 @@ int dvp_restore_state(dvp_ctx* ctx);
 /* Optional buffers of the context ahead of their first use — what a driver's helper thread calls on the context it prepares
  * for the next pyramid level, so that no multi-GB allocation lands inside a view's launches (the reference allocates everything in
  * CudaSpaceInitialization, APD.cpp:1497-1613).  flags: bit 0 = the split strong update's cost block, bit 1 = the view-compacted
- * DepthToWeak / LocalRefine passes' buffers; weak_pixels > 0: the weak update's anchor table and hand-over buffers for that many
- * WEAK pixels.  Never required: every launch site allocates what it lacks. */
+ * DepthToWeak / LocalRefine passes' buffers, bit 2 = the binary16 image planes of format 2 (dvp_image_format: a context for a
+ * down-sampled pyramid level); weak_pixels > 0: the weak update's anchor table and hand-over buffers for that many
+ * WEAK pixels.  Never required: every launch site (and dvp_upload_images*) allocates what it lacks. */
 int dvp_ctx_reserve(dvp_ctx* ctx, int weak_pixels, int flags);
 int dvp_set_params(dvp_ctx* ctx, const DvpParams* params);                     /* APD.cpp:1607-1608 */
 /* The reference seeds cuRAND with clock64() (APD.cu:1270); here the seed is explicit. */
@@ -185,8 +186,11 @@ int dvp_set_sampler(dvp_ctx* ctx, int sampler);
 int dvp_set_profiling(dvp_ctx* ctx, int count_evals);
 /* Image planes the gather-bound kernels read after the last dvp_upload_images*: 0 = the float planes,
  * 1 = byte planes (kept besides the float planes when every texel of every image is an integer in
- * [0, 255]: images decoded from 8-bit files at their native size, APD.cpp:1057-1069).  Same values
- * either way, so results do not depend on it; DVP_NO_IMAGES8 in the environment forces 0. */
+ * [0, 255]: images decoded from 8-bit files at their native size, APD.cpp:1057-1069), 2 = binary16
+ * planes (kept when the set is not 8-bit exact but every texel is finite, in [0, 255] and exact in
+ * binary16: power-of-two down-sampled levels of 8-bit images, whose texels are multiples of 0.25).
+ * Same values in every format, so results do not depend on it.  DVP_NO_IMAGES8 in the environment
+ * forces 0 for every set; DVP_NO_IMAGES16 turns 2 into 0 and leaves 1 alone. */
 int dvp_image_format(const dvp_ctx* ctx);
 
 /* ---- run (APD::RunPatchMatch, APD.cu:4406-4532) ---------------------------------------------- */

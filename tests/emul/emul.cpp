@@ -18,8 +18,12 @@ namespace {
 struct Emu {
 	int W, H, NI, pitch;
 	std::vector<float> images, depths;
-	std::vector<uint8_t> images8;       // byte row pairs (Dev::images8), valid when every image set so far is 8-bit exact
-	std::vector<char> image_exact;
+	std::vector<uint8_t> images8;       // tiled byte pairs (Dev::images8), read when the set is format 1
+	std::vector<uint32_t> images16;     // tiled binary16 pairs (Dev::images16), read when the set is format 2
+	std::vector<unsigned> image_bits;   // per image: the bits of tile_pair_rule over its plane (3 until it is uploaded)
+	bool no_images8 = false, no_images16 = false;   // DVP_NO_IMAGES8 / DVP_NO_IMAGES16 when the context was created (dvp_ctx_create)
+	int format = 0;                     // the set's image format, the engine's rule (dvp_engine.hip: upload_planes)
+	std::vector<float> nan_plane;       // what the anchor table reads as float planes where the set is format 1 or 2
 	std::vector<DvpCamera> cameras;
 	std::vector<ViewConst> views;
 	std::vector<int> sector_taps, sector_start;
@@ -54,10 +58,14 @@ void refresh(Emu& e) {
 	d.images = e.images.data();
 	d.img8_tiles_x = img8_tiles_x(e.W);
 	d.img8_plane_bytes = (size_t)img8_tiles_x(e.W) * img8_tiles_y(e.H) * 128;
-	{
-		bool all = !e.image_exact.empty();
-		for (char ok : e.image_exact) all = all && ok;
-		d.images8 = all ? e.images8.data() : nullptr;
+	d.img16_tiles_x = img16_tiles_x(e.W);
+	d.img16_plane_bytes = (size_t)img16_tiles_x(e.W) * img16_tiles_y(e.H) * 128;
+	{   // the whole set takes one format: 1 if every texel is 8-bit exact, 2 if not but every texel is binary16-exact
+		unsigned bits = 0;
+		for (unsigned b : e.image_bits) bits |= b;
+		e.format = (bits == 0 && !e.no_images8) ? 1 : ((bits == 1 && !e.no_images8 && !e.no_images16) ? 2 : 0);
+		d.images8 = e.format == 1 ? e.images8.data() : nullptr;
+		d.images16 = e.format == 2 ? e.images16.data() : nullptr;
 	}
 	d.depths = e.depths.data();
 	d.cameras = e.cameras.data();
@@ -133,7 +141,11 @@ void* emu_create(int W, int H, int NI) {
 	const int S = NI - 1;
 	e->images.assign((size_t)e->pitch * (H + 2 * kImgPad) * NI * 2, 0.0f);   // row-pair planes
 	e->images8.assign((size_t)img8_tiles_x(W) * img8_tiles_y(H) * 128 * NI, 0);
-	e->image_exact.assign(NI, 0);
+	e->images16.assign((size_t)img16_tiles_x(W) * img16_tiles_y(H) * 32 * NI, 0u);
+	e->image_bits.assign(NI, 3u);
+	e->no_images8 = getenv("DVP_NO_IMAGES8") != nullptr;
+	e->no_images16 = getenv("DVP_NO_IMAGES16") != nullptr;
+	e->nan_plane.assign((size_t)e->pitch * (H + 2 * kImgPad) * 2, std::nanf(""));
 	e->depths.assign((size_t)e->pitch * (H + 2 * kImgPad) * NI, 0.0f);
 	e->cameras.resize(NI);
 	e->views.resize(NI);
@@ -190,24 +202,38 @@ void emu_set_image(void* c, int idx, const float* data) {
 			out[((size_t)y * e.pitch + x) * 2] = plain[(size_t)y * e.pitch + x];
 			out[((size_t)y * e.pitch + x) * 2 + 1] = plain[(size_t)(y + 1 < PH ? y + 1 : y) * e.pitch + x];
 		}
-	// tiled byte planes (dvp_pairs_to_tiles)
+	// tiled byte planes and the format probe (dvp_pairs_to_tiles): tile_pair_rule over every tile element, which covers the padded
+	// plane (clamped at the last tile)
 	const int t8x = img8_tiles_x(e.W), t8y = img8_tiles_y(e.H), PW = e.W + 2 * kImgPad;
+	auto pair_at = [&](int sx, int sy, int c) { return out[((size_t)sy * e.pitch + sx) * 2 + c]; };
 	uint8_t* out8 = &e.images8[(size_t)idx * t8x * t8y * 128];
-	bool exact = true;
-	for (int ty = 0; ty < t8y && exact; ++ty)
-		for (int tx = 0; tx < t8x && exact; ++tx)
+	unsigned bits = 0;
+	for (int ty = 0; ty < t8y; ++ty)
+		for (int tx = 0; tx < t8x; ++tx)
 			for (int el = 0; el < kT8E * kT8H; ++el) {
 				const int sx = std::min(tx * kT8W + (el % kT8E), PW - 1), sy = std::min(ty * kT8H + (el / kT8E), PH - 1);
 				const int sx1 = std::min(sx + 1, PW - 1);
+				uint32_t h;
+				const unsigned bad = tile_pair_rule(pair_at(sx, sy, 0), pair_at(sx, sy, 1), &h);
+				bits |= bad;
+				if (bad & 1u) continue;
 				uint8_t* dst = &out8[(size_t)(ty * t8x + tx) * 128 + (size_t)el * kT8B];
-				for (int c2 = 0; c2 < kT8B; ++c2) {
-					const float v = out[((size_t)sy * e.pitch + (c2 < 2 ? sx : sx1)) * 2 + (c2 & 1)];
-					if (!(v >= 0.0f && v <= 255.0f && v == floorf(v))) { exact = false; break; }
-					dst[c2] = (uint8_t)v;
-				}
-				if (!exact) break;
+				dst[0] = (uint8_t)pair_at(sx, sy, 0);
+				dst[1] = (uint8_t)pair_at(sx, sy, 1);
+				if (kT8Quad) { dst[2] = (uint8_t)pair_at(sx1, sy, 0); dst[3] = (uint8_t)pair_at(sx1, sy, 1); }
 			}
-	e.image_exact[idx] = exact ? 1 : 0;
+	// tiled binary16 planes (dvp_pairs_to_tiles16)
+	const int t16x = img16_tiles_x(e.W), t16y = img16_tiles_y(e.H);
+	uint32_t* out16 = &e.images16[(size_t)idx * t16x * t16y * 32];
+	for (int ty = 0; ty < t16y; ++ty)
+		for (int tx = 0; tx < t16x; ++tx)
+			for (int el = 0; el < kT16E * kT16H; ++el) {
+				const int sx = std::min(tx * kT16W + (el % kT16E), PW - 1), sy = std::min(ty * kT16H + (el / kT16E), PH - 1);
+				uint32_t h;
+				(void)tile_pair_rule(pair_at(sx, sy, 0), pair_at(sx, sy, 1), &h);
+				out16[(size_t)(ty * t16x + tx) * 32 + el] = h;
+			}
+	e.image_bits[idx] = bits;
 	refresh(e);
 }
 void emu_set_depth(void* c, int idx, const float* data) {
@@ -302,6 +328,8 @@ int emu_set_buffer(void* c, int id, const void* src) {
 	return 0;
 }
 int emu_weak_count(void* c) { return ((Emu*)c)->d.weak_count; }
+// dvp_image_format: the format the weak update reads (0 float row pairs, 1 byte tiles, 2 binary16 tiles)
+int emu_image_format(void* c) { return ((Emu*)c)->format; }
 
 // Launch-geometry property: the block -> tile -> pixel map of a launch visits every pixel it is meant
 // to cover exactly once.  Returns 0 when it does; otherwise 1 + the first offending pixel index.
@@ -354,12 +382,20 @@ int emu_run_stage(void* c, int stage, int iter, int colour) {
 			e.anchor_tab.assign((size_t)std::max(e.d.weak_count, 1) * S * kAnchors, AnchorRec{});
 			e.anchor_tab_valid = true;
 			refresh(e);
+			// the records of the active format (dvp_build_anchor_table); where that is 1 or 2 the table must not depend on the float
+			// planes: this build sees NaN there
+			Dev dt = e.d;
+			if (e.format != 0) dt.images = e.nan_plane.data();
 			const long long L = (long long)e.W * e.H;
 #pragma omp parallel for schedule(dynamic, 64)
 			for (long long center = 0; center < L; ++center)
 				if (e.weak_info[(size_t)center] == DVP_WEAK)
 					for (int v0 = 0; v0 < S; ++v0)
-						for (int k = 0; k < kAnchors; ++k) build_anchor_record(e.d, (int)center, v0, k);
+						for (int k = 0; k < kAnchors; ++k) {
+							if (e.format == 1) build_anchor_record<1>(dt, (int)center, v0, k);
+							else if (e.format == 2) build_anchor_record<2>(dt, (int)center, v0, k);
+							else build_anchor_record<0>(dt, (int)center, v0, k);
+						}
 		} else refresh(e);
 	}
 	switch (stage) {
@@ -472,7 +508,8 @@ int emu_run_stage(void* c, int stage, int iter, int colour) {
 			if (sscanf(gs, "%d,%d,%d,%d", &q[0], &q[1], &q[2], &q[3]) == 4)
 				for (int i = 0; i < 4; ++i) group[i] = q[i] < 1 ? 1 : (q[i] > kGrp ? kGrp : q[i]);
 		}
-		const bool ex = e.d.sampler != 0, u8 = e.d.images8 != nullptr;
+		const bool ex = e.d.sampler != 0;
+		const int fmt = e.format;
 		const long long n_px = (long long)list.size();
 		unsigned long long total = 0;
 		auto eval = [&](int mode) {
@@ -482,7 +519,8 @@ int emu_run_stage(void* c, int stage, int iter, int colour) {
 				unsigned long long k = 0;
 				unsigned long long* kp = e.count ? &k : nullptr;
 #define EMU_GROUP(M, GRP) { WeakGroupSharedT<GRP> sh; for (int i = 0; i < GRP; ++i) sh.center[i] = (i < G && t0 + i < n_px) ? list[(size_t)(t0 + i)] : -1; \
-	if (ex) { if (u8) weak_group_eval<1, 1, M, GRP>(e.d, G, kp, sh); else weak_group_eval<1, 0, M, GRP>(e.d, G, kp, sh); } else { if (u8) weak_group_eval<0, 1, M, GRP>(e.d, G, kp, sh); else weak_group_eval<0, 0, M, GRP>(e.d, G, kp, sh); } }
+	if (ex) { if (fmt == 1) weak_group_eval<1, 1, M, GRP>(e.d, G, kp, sh); else if (fmt == 2) weak_group_eval<1, 2, M, GRP>(e.d, G, kp, sh); else weak_group_eval<1, 0, M, GRP>(e.d, G, kp, sh); } \
+	else { if (fmt == 1) weak_group_eval<0, 1, M, GRP>(e.d, G, kp, sh); else if (fmt == 2) weak_group_eval<0, 2, M, GRP>(e.d, G, kp, sh); else weak_group_eval<0, 0, M, GRP>(e.d, G, kp, sh); } }
 				switch (mode) { case 0: EMU_GROUP(0, kGrpWide) break; case 1: EMU_GROUP(1, kGrp) break; case 2: EMU_GROUP(2, kGrp) break; default: EMU_GROUP(3, kGrp) break; }
 #undef EMU_GROUP
 				total += k;

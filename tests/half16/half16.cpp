@@ -6,7 +6,8 @@ using namespace dvp;
 
 namespace {
 // one image as the engine holds it: the padded row-pair float plane (Dev::images) and the binary16 tiles (Dev::images16),
-// both built from `img` ([H][W]) as upload_planes / dvp_pairs_to_tiles16 build them
+// both built from `img` ([H][W]) as upload_planes / dvp_pairs_to_tiles16 build them.  img == nullptr: a padded plane whose
+// texels all differ (binary16 value k + 1 at padded texel k), frame included — what no replicated border can hide
 struct Planes {
 	Dev d{};
 	std::vector<float> pairs;
@@ -15,7 +16,9 @@ struct Planes {
 		const int pitch = (W + 2 * kImgPad + 63) / 64 * 64, PW = W + 2 * kImgPad, PH = H + 2 * kImgPad;
 		std::vector<float> plain((size_t)pitch * PH, 0.0f);
 		for (int y = 0; y < PH; ++y)
-			for (int x = 0; x < PW; ++x) plain[(size_t)y * pitch + x] = img[(size_t)clampi(y - kImgPad, 0, H - 1) * W + clampi(x - kImgPad, 0, W - 1)];
+			for (int x = 0; x < PW; ++x)
+				plain[(size_t)y * pitch + x] = img ? img[(size_t)clampi(y - kImgPad, 0, H - 1) * W + clampi(x - kImgPad, 0, W - 1)]
+				                                   : half_bits_to_float((uint32_t)(1 + y * PW + x));
 		pairs.assign((size_t)pitch * PH * 2, 0.0f);
 		for (int y = 0; y < PH; ++y)
 			for (int x = 0; x < pitch; ++x) {
@@ -66,6 +69,22 @@ int h16_footprints(const float* img, int W, int H, int sampler, const float* xs,
 	const Planes p(img, W, H);
 	int bad = 0;
 	for (int i = 0; i < n; ++i) bad += sampler ? !same_footprint<1>(p.d, xs[i], ys[i]) : !same_footprint<0>(p.d, xs[i], ys[i]);
+	return bad;
+}
+// every footprint origin (i0, j0) of the padded plane, i0 in [-PAD, W + PAD - 2], j0 in [-PAD, H + PAD - 2], on the plane of
+// distinct texels: how many img16_offset footprints differ from tex_offset's in the float planes (-1: an offset leaves the plane)
+int h16_offsets(int W, int H) {
+	const Planes p(nullptr, W, H);
+	int bad = 0;
+	for (int j0 = -kImgPad; j0 <= H + kImgPad - 2; ++j0)
+		for (int i0 = -kImgPad; i0 <= W + kImgPad - 2; ++i0) {
+			const unsigned o0 = tex_offset(p.d.pitch, i0, j0), o2 = img16_offset(p.d.img16_tiles_x, i0, j0);
+			if (o2 + 8 > p.d.img16_plane_bytes) return -1;
+			float q0[4], q2[4];
+			load_quad_t<0>(img_plane<0>(p.d, 0), o0, &q0[0], &q0[1], &q0[2], &q0[3]);
+			load_quad_t<2>(img_plane<2>(p.d, 0), o2, &q2[0], &q2[1], &q2[2], &q2[3]);
+			bad += memcmp(q0, q2, sizeof q0) != 0;
+		}
 	return bad;
 }
 // n integer pixels: how many of them give ref_texel_t<2> != ref_texel_t<0> (clamp-to-edge)

@@ -226,6 +226,11 @@ int main(int argc, char** argv) {
 		printf("%d %d\n", w, h);
 		return 0;
 	}
+	if (argc > 5 && std::string(argv[1]) == "--resize") {   // --resize in.dmb new_cols new_rows out.dmb: ResizeLinear of a float image
+		Mat src;
+		if (!ReadBinMat(argv[2], src) || src.type() != CV_32FC1) return 2;
+		return WriteBinMat(argv[5], ResizeLinear(src, std::atoi(argv[3]), std::atoi(argv[4]))) ? 0 : 3;
+	}
 	if (argc > 4 && std::string(argv[1]) == "--labels") return dump_labels(argv[2], std::atoi(argv[3]), argv[4]);
 	if (argc > 4 && std::string(argv[1]) == "--label-stages") return dump_label_stages(argv[2], std::atoi(argv[3]), argv[4]);
 	path tmp = argc > 1 ? path(argv[1]) : std::filesystem::temp_directory_path();

@@ -40,6 +40,40 @@ def scene_with_views(W, H, S, seed=7):
     return out
 
 
+# Image sets for each format the weak update reads (dvp_engine.hip: upload_planes; capi.Context.image_format()):
+# name -> (the format the engine must report, environment before the context is created)
+IMAGE_SETS = {
+    "int": (1, {}),                              # as rendered: integer grey levels, byte tiles
+    "box": (2, {}),                              # workloads.box2x2: multiples of 0.25, binary16 tiles
+    "box_no16": (0, {"DVP_NO_IMAGES16": "1"}),   # the same images on the float planes (the oracle run is shared with "box")
+    "scaled": (0, {}),                           # x 0.97 + 1.3: float planes
+}
+
+
+def image_env(name, monkeypatch):
+    """the environment of image set `name` for the contexts created after it (the oracle reads none); -> the format the engine
+    must report"""
+    fmt, env = IMAGE_SETS[name]
+    for k in ("DVP_NO_IMAGES8", "DVP_NO_IMAGES16"):
+        monkeypatch.delenv(k, raising=False)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    return fmt
+
+
+def image_set(sc, name, monkeypatch=None):
+    """`sc` with the images of image set `name`, and the format the engine must report; with `monkeypatch`, image_env too"""
+    fmt = IMAGE_SETS[name][0] if monkeypatch is None else image_env(name, monkeypatch)
+    imgs = np.asarray(sc["images"], np.float32)
+    assert (imgs == np.floor(imgs)).all() and imgs.min() >= 0 and imgs.max() <= 255
+    if name in ("box", "box_no16"):
+        imgs = pkg("workloads").box2x2(imgs)
+        assert not (imgs == np.floor(imgs)).all()   # not an 8-bit exact set in disguise
+    elif name == "scaled":
+        imgs = (imgs * np.float32(0.97) + np.float32(1.3)).astype(np.float32)
+    return dict(sc, images=imgs), fmt
+
+
 def cases():
     out = []
     # (name, W, H, S, params overrides, state mutator)
@@ -74,10 +108,13 @@ def cases():
     return out
 
 
-def run_case(case, make_b):
+def run_case(case, make_b, images=None, monkeypatch=None):
     name, W, H, S, over, mutate = case
     sc = scene_with_views(W, H, S)
     sc["images"] = sc["images"].copy()
+    fmt = None
+    if images is not None:
+        sc, fmt = image_set(sc, images, monkeypatch)
     p = make_params(S + 1, **dict(dict(state=synth.FIRST_INIT, use_APD=0), **over))
     st = first_pass_state(sc)
     if mutate:
@@ -85,6 +122,8 @@ def run_case(case, make_b):
     depths = sc["depth_gt"] if p["geom_consistency"] else None
     a = O.from_scene(sc, p, seed=99, depths=depths)
     b = make_b(sc, p, 99, depths)
+    if fmt is not None:
+        assert b.image_format() == fmt, (name, images)
     a.upload_state(**st)
     b.upload_state(**st)
     a.run_patchmatch()
@@ -107,6 +146,22 @@ def test_edge_cases_emulated_kernels(case):
 def test_edge_cases_gpu(case):
     capi = pkg("capi")
     run_case(case, lambda sc, p, seed, dep: capi.from_scene(sc, p, seed=seed, depths=dep))
+
+
+# the sized cases again on binary16 tiles (format 2)
+SIZED = ("tiny_16x12_one_source", "narrower_than_a_wave_odd", "odd_height_quirk_H33", "max_images_32")
+
+
+@pytest.mark.parametrize("case", [c for c in cases() if c[0] in SIZED], ids=lambda c: c[0])
+def test_edge_cases_half_planes_emulated_kernels(case, monkeypatch):
+    run_case(case, lambda sc, p, seed, dep: O.from_scene(sc, p, seed=seed, depths=dep, cls=E.Emul), "box", monkeypatch)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", [c for c in cases() if c[0] in SIZED], ids=lambda c: c[0])
+def test_edge_cases_half_planes_gpu(case, monkeypatch):
+    capi = pkg("capi")
+    run_case(case, lambda sc, p, seed, dep: capi.from_scene(sc, p, seed=seed, depths=dep), "box", monkeypatch)
 
 
 def test_rejected_inputs_cpu_side():

@@ -8,6 +8,7 @@ from conftest import (synth, make_params, count_diff, stage_sequence, CHECKED, f
                       second_pass_inputs)
 from oracle import oracle as O
 from tests.emul import emul as E
+from test_edge_cases import image_set
 
 
 def _pair(scene, params, state, seed=1234, sampler=0, depths=None):
@@ -36,7 +37,7 @@ def test_first_pass_strong_path(W, H, S, sampler):
 
 
 @pytest.mark.parametrize("anchors", ["table", "one_wave", "alloc_fail", "per_item"])
-@pytest.mark.parametrize("images", ["8bit", "float"])
+@pytest.mark.parametrize("images", ["8bit", "float", "box"])
 def test_two_pass_weak_path_with_geom(images, anchors, monkeypatch):
     """`anchors`: the reference side of the anchor sub-patches from the pass' table (built once, before the first weak
     update of the pass) or formed per (view, anchor, plane) item as the source text does (DVP_WEAK_ANCHOR_TAB=0).  With the
@@ -44,7 +45,7 @@ def test_two_pass_weak_path_with_geom(images, anchors, monkeypatch):
     (the hand-over buffers do not fit: DVP_TEST_WEAK_PHASE_ALLOC_FAIL) keep a pixel's whole update in one wave; all the same bits.
     pass 1 (FIRST_INIT) on the oracle, then a REFINE_ITER pass with WEAK pixels, labels, adaptive
     radius and geometric consistency on both.  `images`: integer grey levels (the weak update reads the
-    byte planes) or non-integers (float planes)."""
+    byte planes), non-integers (float planes), or workloads.box2x2 of the integers (binary16 planes)."""
     monkeypatch.setenv("DVP_WEAK_ANCHOR_TAB", "0" if anchors == "per_item" else "1")
     if anchors == "one_wave":
         monkeypatch.setenv("DVP_WEAK_PHASED", "0")
@@ -54,6 +55,9 @@ def test_two_pass_weak_path_with_geom(images, anchors, monkeypatch):
     sc = synth.make_scene(W, H, S)
     if images == "float":
         sc["images"] = (sc["images"] * np.float32(0.97) + np.float32(1.3)).astype(np.float32)
+    fmt = None
+    if images == "box":
+        sc, fmt = image_set(sc, "box", monkeypatch)
     p1 = make_params(S + 1, max_iterations=2, state=synth.FIRST_INIT, use_APD=0)
     o = O.from_scene(sc, p1)
     o.upload_state(**first_pass_state(sc))
@@ -69,11 +73,19 @@ def test_two_pass_weak_path_with_geom(images, anchors, monkeypatch):
                      weak_peak_radius=4, rotate_time=2, ransac_threshold=0.01)
     depths = sc["depth_gt"]   # stand-in for the neighbours' depths.dmb
     a, b = _pair(sc, p2, st, depths=depths)
+    if fmt is not None:
+        assert b.image_format() == fmt
     assert a.weak_count() == b.weak_count() > 0
     _run_and_compare(a, b, 2)
     # the weak path really ran
     assert (a.get("weak_reliable") == 1).sum() > 0
     assert np.abs(a.get("fit_planes")).sum() > 0
+
+
+def test_two_pass_weak_path_half_planes_other_groups(monkeypatch):
+    """the phased weak update on binary16 planes with other WEAK pixels per wave in its four evaluation launches"""
+    monkeypatch.setenv("DVP_WEAK_GROUPS", "2,3,1,3")
+    test_two_pass_weak_path_with_geom("box", "table", monkeypatch)
 
 
 @pytest.mark.parametrize("form,wpr", [("passes", None), ("fused", None), ("passes", 9), ("passes", 40)])

@@ -157,6 +157,102 @@ def test_reupload_switches_format_and_keeps_the_bits(monkeypatch):
         b.close()
 
 
+# ---- the upload probe at tile seams and plane corners ----
+# One "spoiler" texel in an integer or box2x2 set.  Widths cover every residue of (W + 4) mod 7, heights every residue of (H + 4)
+# mod 8 and so mod 4: the padded plane (kImgPad = 2) against the byte tiles (7 + 1 elements x 8 rows) and the binary16 tiles
+# (7 + 1 elements x 4 rows), so the spoiler falls at every place of the last tile column and row.
+PROBE_SIZES = [(60 + i, 44 + i) for i in range(8)]
+PROBE_S = 3
+TO_FORMAT_0 = [255.25, 128.0625, 2.0 ** -25, 100.1]     # in either set: not a binary16 value in [0, 255]
+TO_FORMAT_2 = [0.5, 2.0 ** -24, 254.75]                 # in an integer set: binary16-exact, not 8-bit exact
+
+
+def probe_scene(i):
+    W, H = PROBE_SIZES[i]
+    return synth.make_scene(W, H, PROBE_S)
+
+
+def base_images(sc, base):
+    return np.asarray(sc["images"], np.float32) if base == "int" else wl.box2x2(sc["images"])
+
+
+def spoiler_places(sc, i):
+    """(image, y, x): (W-1, H-1) of the reference image, (0, 0) of the last source view, the last column of a source view"""
+    H, W, NI = sc["height"], sc["width"], len(sc["cameras"])
+    return [(0, H - 1, W - 1), (NI - 1, 0, 0), (1 + i % (NI - 1), (5 * i + 3) % H, W - 1)]
+
+
+def spoiled(images, places, value):
+    out = images.copy()
+    for k, y, x in places:
+        out[k, y, x] = np.float32(value)
+    return out
+
+
+def check_probe(i, formats):
+    """formats(images) -> the formats the upload paths report for the set"""
+    sc = probe_scene(i)
+    for base, fmt in (("int", 1), ("box", 2)):
+        assert set(formats(base_images(sc, base))) == {fmt}, (PROBE_SIZES[i], base)
+    cases = [(base, v, 0) for base in ("int", "box") for v in TO_FORMAT_0] + [("int", v, 2) for v in TO_FORMAT_2]
+    for base, v, fmt in cases:
+        for place in spoiler_places(sc, i):
+            got = formats(spoiled(base_images(sc, base), [place], v))
+            assert set(got) == {fmt}, (PROBE_SIZES[i], base, v, place, got)
+
+
+def spoiled_weak_pass(i, fmt, make_engine):
+    """a weak pass on a set whose spoilers sit inside pixels that WEAK pixels' patches read: one value of TO_FORMAT_2 in the
+    integer set (format 2) or of TO_FORMAT_0 in the box set (format 0) at every place of spoiler_places, against the oracle bit for
+    bit.  A probe that missed a spoiler would store it rounded in the tiles."""
+    sc = probe_scene(i)
+    H, W = sc["height"], sc["width"]
+    base, values = ("int", TO_FORMAT_2) if fmt == 2 else ("box", TO_FORMAT_0)
+    sc = dict(sc, images=spoiled(base_images(sc, base), spoiler_places(sc, i), values[i % len(values)]))
+    st, p2 = _weak_pass_inputs(sc, PROBE_S, border_weak=True)
+    wk = st["weak"].reshape(H, W) == synth.WEAK
+    assert wk[H - 11:, W - 11:].any()     # a WEAK pixel within a patch radius (5) of the reference image's (W-1, H-1)
+    a = O.from_scene(sc, p2, seed=1234 + i, sampler=i % 2, depths=sc["depth_gt"])
+    b = make_engine(sc, p2, 1234 + i, i % 2)
+    assert b.image_format() == fmt
+    a.upload_state(**st)
+    b.upload_state(**st)
+    assert a.weak_count() == b.weak_count() > 50
+    _run_and_compare(a, b, 2, what="%dx%d, format %d: " % (W, H, fmt))
+    a.close()
+    b.close()
+
+
+@pytest.mark.parametrize("i", range(len(PROBE_SIZES)), ids=lambda i: "%dx%d" % PROBE_SIZES[i])
+def test_probe_finds_spoilers_at_tile_seams(i, monkeypatch):
+    """both upload paths"""
+    import torch
+    for k in ("DVP_NO_IMAGES8", "DVP_NO_IMAGES16"):
+        monkeypatch.delenv(k, raising=False)
+    W, H = PROBE_SIZES[i]
+    g = capi().Context(W, H, PROBE_S + 1)
+
+    def formats(imgs):
+        g.set_images(imgs)
+        host = g.image_format()
+        t = torch.from_numpy(np.ascontiguousarray(imgs)).to("cuda")
+        g.set_images_device([t[k].data_ptr() for k in range(PROBE_S + 1)], W)
+        torch.cuda.synchronize()
+        return host, g.image_format()
+    try:
+        check_probe(i, formats)
+    finally:
+        g.close()
+
+
+@pytest.mark.parametrize("fmt", [2, 0])
+@pytest.mark.parametrize("i", range(len(PROBE_SIZES)), ids=lambda i: "%dx%d" % PROBE_SIZES[i])
+def test_weak_pass_with_spoilers(i, fmt, monkeypatch):
+    for k in ("DVP_NO_IMAGES8", "DVP_NO_IMAGES16"):
+        monkeypatch.delenv(k, raising=False)
+    spoiled_weak_pass(i, fmt, lambda sc, p, seed, smp: capi().from_scene(sc, p, seed=seed, sampler=smp, depths=sc["depth_gt"]))
+
+
 def _all_buffers_equal(g1, g2, what):
     for n in CHECKED:
         nd = count_diff(g1.get(n), g2.get(n))

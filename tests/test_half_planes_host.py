@@ -27,6 +27,7 @@ def lib():
         L.h16_decode.restype = ctypes.c_float
         L.h16_footprints.argtypes = [fp, ctypes.c_int, ctypes.c_int, ctypes.c_int, fp, fp, ctypes.c_int]
         L.h16_ref_texels.argtypes = [fp, ctypes.c_int, ctypes.c_int, ip, ip, ctypes.c_int]
+        L.h16_offsets.argtypes = [ctypes.c_int, ctypes.c_int]
         _LIB = L
     return _LIB
 
@@ -67,6 +68,15 @@ def test_reference_texels_equal_the_float_planes(W, H):
     yy, xx = np.mgrid[-3:H + 3, -3:W + 3]
     xs, ys = np.ascontiguousarray(xx.ravel(), np.int32), np.ascontiguousarray(yy.ravel(), np.int32)
     assert lib().h16_ref_texels(_p(img, ctypes.c_float), W, H, _p(xs, ctypes.c_int), _p(ys, ctypes.c_int), len(xs)) == 0
+
+
+@pytest.mark.parametrize("W", [37, 38, 39, 40, 41, 42, 43])
+@pytest.mark.parametrize("H", [23, 24, 25, 26, 27, 28, 29, 30])
+def test_tile_addressing_on_distinct_texels(W, H):
+    """img16_offset against the float planes' addressing at every footprint origin of the padded plane, on a plane whose texels all
+    differ (the frame included, where a replicated border would hide a clamp one row or column off); widths cover every residue of
+    (W + 4) mod 7, heights every residue of (H + 4) mod 8"""
+    assert lib().h16_offsets(W, H) == 0
 
 
 def _rule(a, b=0.0):

@@ -425,3 +425,70 @@ def test_prior_ratio_map_on_a_hand_built_point_file(tmp_path):
         worst = max(worst, float(np.abs(R.T @ n - planes[y, x, :3]).max()))
     assert worst < 1e-3, worst
     assert np.all(planes[0, :, :3] == 0) and np.all(planes[:, 0, :3] == 0)     # border pixels keep a zero normal
+
+
+def _np_resize_linear(src, new_cols, new_rows):
+    """host/io.cpp ResizeLinear in float64, rounded to binary32 after every operation the C++ makes in float: the source
+    coordinate (dst + 0.5) * scale - 0.5 in double, then float; the fraction and the horizontal-then-vertical blend in float"""
+    f32 = np.float32
+    rows, cols = src.shape
+
+    def taps(n_src, n_dst):
+        scale = float(n_src) / n_dst
+        i0, frac = np.zeros(n_dst, np.int64), np.zeros(n_dst, np.float32)
+        for d in range(n_dst):
+            f = f32((d + 0.5) * scale - 0.5)
+            i = int(np.floor(f))
+            f = f32(f - f32(i))
+            if i < 0:
+                i, f = 0, f32(0)
+            if i >= n_src - 1:
+                i, f = n_src - 1, f32(0)
+            i0[d], frac[d] = i, f
+        return i0, np.minimum(i0 + 1, n_src - 1), frac
+
+    x0, x1, ax = taps(cols, new_cols)
+    y0, y1, ay = taps(rows, new_rows)
+    s = src.astype(np.float64)
+    one = np.float64(1.0)
+
+    def blend(p, q, a):   # p * (1 - a) + q * a, one binary32 rounding per operation
+        a = a.astype(np.float64)
+        return (f32(p * f32(one - a)).astype(np.float64) + f32(q * a)).astype(np.float32)
+
+    h0 = blend(s[y0][:, x0], s[y0][:, x1], ax[None, :])
+    h1 = blend(s[y1][:, x0], s[y1][:, x1], ax[None, :])
+    return blend(h0.astype(np.float64), h1.astype(np.float64), ay[:, None])
+
+
+def _binary16_exact(a):
+    return bool(((a >= 0) & (a <= 255) & (a.astype(np.float16).astype(np.float32) == a)).all())
+
+
+@pytest.mark.parametrize("W,H,scale,fmt", [(96, 64, 2, 2), (96, 64, 4, 2), (90, 66, 2, 2), (160, 120, 4, 2),
+                                           (200, 1082, 4, 0), (123, 77, 2, 0), (150, 98, 4, 0)])
+def test_resize_linear_levels_and_their_image_format(tmp_path, W, H, scale, fmt):
+    """The driver's pyramid levels (APD.cpp: ResizeLinear of the 8-bit image to round(size / scale)) against a float64 reading of
+    host/io.cpp bit for bit, on a textured 8-bit image.  A level whose size divides the file's takes multiples of 0.25: binary16
+    values in [0, 255], not all integers — the weak update's format 2.  Where round(size / scale) is not exact (1082 rows -> 271
+    at scale 4) the level holds other values: format 0."""
+    rng = np.random.default_rng(W * 131 + H + scale)
+    sc = synth.make_scene(W, H, 1, seed=int(rng.integers(0, 1 << 30)))
+    img = np.clip(sc["images"][0] + rng.integers(-40, 41, (H, W)), 0, 255).astype(np.float32)   # texture down to the pixel
+    assert (img == np.floor(img)).all()
+    factor = np.float32(1.0) / np.float32(scale)
+    nc, nr = (int(np.floor(np.float32(n) * factor + 0.5)) for n in (W, H))   # std::round of int * float
+    src, out = str(tmp_path / "src.dmb"), str(tmp_path / "out.dmb")
+    _write_binmat(src, img, 5)
+    r = _host_tool("--resize", src, nc, nr, out)
+    assert r.returncode == 0, r.stdout + r.stderr
+    got = _read_binmat(out)
+    assert got.shape == (nr, nc)
+    want = _np_resize_linear(img, nc, nr)
+    nd = int((got.view(np.uint32) != want.view(np.uint32)).sum())
+    assert nd == 0, (W, H, scale, nd)
+    integers = bool((got == np.floor(got)).all())
+    assert not integers
+    assert _binary16_exact(got) == (fmt == 2), (W, H, scale, nc, nr)
+    if fmt == 2:
+        assert set(np.unique(got % np.float32(1.0)).tolist()) <= {0.0, 0.25, 0.5, 0.75}

@@ -10,6 +10,7 @@ import pytest
 from conftest import pkg, synth, make_params, count_diff, first_pass_state
 from oracle import oracle as O
 from tests.emul import emul as E
+from test_edge_cases import image_set
 
 
 def draw_config(rng):
@@ -78,3 +79,54 @@ def test_random_configs_gpu(case):
     rng = np.random.default_rng(5000 + case)
     capi = pkg("capi")
     run_pair(lambda sc, p, seed, smp, dep: capi.from_scene(sc, p, seed=seed, sampler=smp, depths=dep), rng)
+
+
+# The image-format axis: draws of draw_config (other seeds) on the image sets of test_edge_cases.IMAGE_SETS, the set cycling with
+# the case number; a second generator adds WEAK blocks along the left, right and bottom borders, just inside the 6-pixel frame
+# (DepthToWeak leaves it UNKNOWN), and widens the depth range so that footprints leave the source images (the clamp cases, as
+# test_half_planes._weak_pass_inputs(border_weak=True)).
+FORMAT_CYCLE = ("box", "scaled", "box_no16", "int")
+
+
+def run_format_pair(make_b, case, seed0, monkeypatch):
+    sc, p, st, depths, sampler, seed = draw_config(np.random.default_rng(seed0 + case))
+    sc, fmt = image_set(sc, FORMAT_CYCLE[case % len(FORMAT_CYCLE)], monkeypatch)
+    W, H = sc["width"], sc["height"]
+    if int(p["state"]) != synth.FIRST_INIT:
+        r2 = np.random.default_rng(seed0 + 100000 + case)
+        weak = st["weak"].reshape(H, W).copy()
+        extra = np.zeros((H, W), bool)
+        y0 = H - 6 - int(r2.integers(2, 7))
+        extra[y0:H - 6, int(r2.integers(6, 12)):W - 6:int(r2.integers(1, 3))] = True
+        y1 = int(r2.integers(6, H // 2))
+        extra[y1:H - 6, 6:6 + int(r2.integers(2, 6))] = True
+        y2 = int(r2.integers(6, H // 2))
+        extra[y2:H - 6, W - 6 - int(r2.integers(2, 6)):W - 6] = True
+        weak[extra & (weak == synth.STRONG)] = synth.WEAK
+        st = dict(st, weak=weak.reshape(-1))
+        p["depth_min"] = np.float32(2.5) * np.float32(0.3)
+        p["depth_max"] = np.float32(6.5) * np.float32(2.0)
+    a = O.from_scene(sc, p, seed=seed, sampler=sampler, depths=depths)
+    b = make_b(sc, p, seed, sampler, depths)
+    assert b.image_format() == fmt
+    a.upload_state(**st)
+    b.upload_state(**st)
+    a.run_patchmatch()
+    b.run_patchmatch()
+    for name in ("planes", "costs", "selected_views", "weak_info", "radius", "view_weight", "neighbours", "weak_reliable"):
+        nd = count_diff(a.get(name), b.get(name))
+        assert nd == 0, (name, nd, fmt, W, H, dict(zip(p.dtype.names, p.tolist())))
+
+
+@pytest.mark.parametrize("case", range(9))
+def test_random_image_formats_emulated_kernels(case, monkeypatch):
+    run_format_pair(lambda sc, p, seed, smp, dep: O.from_scene(sc, p, seed=seed, sampler=smp, depths=dep, cls=E.Emul), case, 3000,
+                    monkeypatch)
+
+
+# DVP_RANDOM_FORMAT_CASES=N widens this sweep for soak runs (default: 30 cases on a GPU box, 9 elsewhere)
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", range(int(os.environ.get("DVP_RANDOM_FORMAT_CASES", "30" if os.path.exists("/dev/kfd") else "9"))))
+def test_random_image_formats_gpu(case, monkeypatch):
+    capi = pkg("capi")
+    run_format_pair(lambda sc, p, seed, smp, dep: capi.from_scene(sc, p, seed=seed, sampler=smp, depths=dep), case, 7000, monkeypatch)

@@ -15,7 +15,7 @@ import pytest
 from conftest import pkg, synth, make_params, count_diff, stage_sequence, CHECKED, first_pass_state, second_pass_inputs
 from oracle import oracle as O
 from tests.emul import emul as E
-from test_edge_cases import scene_with_views
+from test_edge_cases import scene_with_views, image_set, image_env
 
 W, H = 88, 64
 SEED = 4321
@@ -30,6 +30,10 @@ FORMS = {
     "weak_one_wave": dict(DVP_WEAK_PHASED="0"),
 }
 SWEEP_FORMS = {"sweep_split": dict(DVP_SWEEP_SPLIT="2"), "sweep_fused": dict(DVP_SWEEP_SPLIT="0")}
+# the image-format axis (test_edge_cases.IMAGE_SETS): binary16 tiles at the counts around the one-wave update's batches of seven
+# views (kWeakViews), the float planes of the same images at a few
+HALF_SWEEP = [1, 2, 7, 8, 9, 14, 15, 20, 31]
+FLOAT_SWEEP = [1, 8, 15, 31]
 
 
 def cases():
@@ -37,6 +41,12 @@ def cases():
     for S in BOUNDARY:
         out += [(S, f) for f in list(FORMS)[1:] + list(SWEEP_FORMS)]
     return sorted(out, key=lambda c: c[0])   # same S next to each other: the oracle's run is cached per S
+
+
+def format_cases():
+    out = [(S, f, "box") for S in HALF_SWEEP for f in ("default", "weak_one_wave")]
+    out += [(S, "default", "box_no16") for S in FLOAT_SWEEP]
+    return sorted(out, key=lambda c: c[0])   # "box" and "box_no16" share the oracle's run
 
 
 def popcount(a):
@@ -111,9 +121,12 @@ class Trace:
 
 
 @functools.lru_cache(maxsize=1)
-def oracle_run(S):
-    """The oracle's two passes at S, stage by stage; and pass 2 again in one run_patchmatch (the sweep forms)."""
+def oracle_run(S, images="int"):
+    """The oracle's two passes at S on image set `images`, stage by stage; and pass 2 again in one run_patchmatch (the sweep
+    forms)."""
     sc = make_scene(S)
+    if images != "int":
+        sc, _ = image_set(sc, images)
     p1, p2 = pass_params(S)
     o1 = O.from_scene(sc, p1, seed=SEED)
     o1.upload_state(**first_pass_state(sc))
@@ -153,10 +166,15 @@ def check_masks_are_large(S, steps, weak_in):
         assert weak_most >= 8, (S, weak_most)
 
 
-def view_count_case(S, form, make_engine, monkeypatch):
+def view_count_case(S, form, make_engine, monkeypatch, images=None):
     for k, v in dict(FORMS, **SWEEP_FORMS)[form].items():
         monkeypatch.setenv(k, v)
-    sc, st, steps1, steps2, weak_in, final = oracle_run(S)
+    fmt = None
+    if images is None:
+        sc, st, steps1, steps2, weak_in, final = oracle_run(S)
+    else:
+        sc, st, steps1, steps2, weak_in, final = oracle_run(S, "box" if images == "box_no16" else images)
+        fmt = image_env(images, monkeypatch)
     check_masks_are_large(S, steps1 + steps2, weak_in)
     p1, p2 = pass_params(S)
     if form in SWEEP_FORMS:   # DepthToWeak + LocalRefine are one launch site of run_patchmatch only
@@ -167,6 +185,8 @@ def view_count_case(S, form, make_engine, monkeypatch):
         return
     for p, state, steps, dep in ((p1, first_pass_state(sc), steps1, None), (p2, st, steps2, sc["depth_gt"])):
         b = make_engine(sc, p, dep)
+        if fmt is not None:
+            assert b.image_format() == fmt, (S, form, images)
         b.upload_state(**state)
         ref = iter(steps)
 
@@ -198,6 +218,17 @@ def test_view_counts_emulated_kernels(S, form, monkeypatch):
 @pytest.mark.parametrize("S,form", cases(), ids=lambda v: str(v))
 def test_view_counts_gpu(S, form, monkeypatch):
     view_count_case(S, form, gpu_engine, monkeypatch)
+
+
+@pytest.mark.parametrize("S,form,images", format_cases(), ids=lambda v: str(v))
+def test_view_counts_image_formats_emulated_kernels(S, form, images, monkeypatch):
+    view_count_case(S, form, emul_engine, monkeypatch, images)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("S,form,images", format_cases(), ids=lambda v: str(v))
+def test_view_counts_image_formats_gpu(S, form, images, monkeypatch):
+    view_count_case(S, form, gpu_engine, monkeypatch, images)
 
 
 def full_masks_case(S, make_engine):
@@ -252,10 +283,13 @@ GEOMETRIES = {
 }
 
 
-def geometry_case(name, make_engine):
+def geometry_case(name, make_engine, images=None, monkeypatch=None):
     S = 6
     over = GEOMETRIES[name]
     sc = synth.make_scene(W, H, S)
+    fmt = None
+    if images is not None:
+        sc, fmt = image_set(sc, images, monkeypatch)
     p1 = make_params(S + 1, max_iterations=1, state=synth.FIRST_INIT, use_APD=0, **over)
     p2 = make_params(S + 1, max_iterations=1, state=synth.REFINE_ITER, use_APD=1, geom_consistency=1,
                      weak_peak_radius=4, rotate_time=2, ransac_threshold=0.01, **over)
@@ -270,6 +304,8 @@ def geometry_case(name, make_engine):
     for p, st, dep in ((p1, st1, None), (p2, st2, sc["depth_gt"])):
         a = O.from_scene(sc, p, seed=SEED, depths=dep)
         b = make_engine(sc, p, dep)
+        if fmt is not None:
+            assert b.image_format() == fmt, (name, images)
         a.upload_state(**st)
         b.upload_state(**st)
         for stg, it, col in stage_sequence(1):
@@ -306,3 +342,14 @@ def test_patch_geometries_emulated_kernels(name):
 @pytest.mark.parametrize("name", list(GEOMETRIES))
 def test_patch_geometries_gpu(name):
     geometry_case(name, gpu_engine)
+
+
+@pytest.mark.parametrize("name", list(GEOMETRIES))
+def test_patch_geometries_half_planes_emulated_kernels(name, monkeypatch):
+    geometry_case(name, emul_engine, "box", monkeypatch)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", list(GEOMETRIES))
+def test_patch_geometries_half_planes_gpu(name, monkeypatch):
+    geometry_case(name, gpu_engine, "box", monkeypatch)

@@ -33,7 +33,9 @@ EXPORTS = ["dvp_ctx_create", "dvp_ctx_destroy", "dvp_ctx_reserve", "dvp_last_err
            "dvp_run_stage", "dvp_synchronize", "dvp_download_state", "dvp_download_maps", "dvp_download_maps_begin", "dvp_download_maps_finish", "dvp_buffer_bytes", "dvp_download_buffer",
            "dvp_upload_buffer", "dvp_weak_count", "dvp_get_timings", "dvp_reset_timings", "dvp_eval_cost_vectors",
            "dvp_bench_cost_kernel", "dvp_build_id",
-           "dvp_fuse_create", "dvp_fuse_destroy", "dvp_fuse_last_error", "dvp_fuse_set_view", "dvp_fuse_view", "dvp_fuse_view_graded", "dvp_fuse_count", "dvp_fuse_download", "dvp_fuse_last_rounds"]
+           "dvp_fuse_create", "dvp_fuse_destroy", "dvp_fuse_last_error", "dvp_fuse_set_view", "dvp_fuse_view", "dvp_fuse_view_graded", "dvp_fuse_count", "dvp_fuse_download", "dvp_fuse_last_rounds",
+           "dvp_jpeg_bound", "dvp_jpeg_encode", "dvp_jpeg_last_error", "dvp_preview_begin", "dvp_preview_finish", "dvp_preview_pixels"]
+PREVIEW_DEPTH, PREVIEW_NORMAL, PREVIEW_WEAK = 1, 2, 4
 
 
 class DvpTimings(ctypes.Structure):
@@ -93,6 +95,15 @@ def lib():
         L.dvp_build_id.restype = ctypes.c_char_p
         L.dvp_build_id.argtypes = []
         L.dvp_bench_cost_kernel.argtypes = [vp, ci, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_uint64)]
+        ll = ctypes.c_longlong
+        L.dvp_jpeg_bound.restype = ll
+        L.dvp_jpeg_bound.argtypes = [ci, ci, ci]
+        L.dvp_jpeg_encode.argtypes = [ci, vp, ci, ci, ci, ll, ci, ci, vp, ll, ctypes.POINTER(ll)]
+        L.dvp_jpeg_last_error.restype = ctypes.c_char_p
+        L.dvp_jpeg_last_error.argtypes = []
+        L.dvp_preview_begin.argtypes = [vp, ci, ci]
+        L.dvp_preview_finish.argtypes = [vp, ci, vp, ll, ctypes.POINTER(ll)]
+        L.dvp_preview_pixels.argtypes = [vp, ci, vp]
         _LIB = L
     return _LIB
 
@@ -103,6 +114,26 @@ def _p(a):
 
 class DvpError(RuntimeError):
     pass
+
+
+def jpeg_encode(pixels, quality=95, restart=0, device=0):
+    """baseline JPEG of a (H, W) grey or (H, W, 3) BGR uint8 image, encoded on the GPU (include/dvp_mvs.h dvp_jpeg_encode);
+    restart = MCUs per restart interval, 0 = the engine's choice"""
+    L = lib()
+    a = np.asarray(pixels)
+    assert a.dtype == np.uint8 and a.ndim in (2, 3) and (a.ndim == 2 or a.shape[2] == 3), (a.dtype, a.shape)
+    if a.strides[-1] != 1 or (a.ndim == 3 and a.strides[1] != 3):
+        a = np.ascontiguousarray(a)
+    H, W = a.shape[:2]
+    C = 1 if a.ndim == 2 else 3
+    cap = L.dvp_jpeg_bound(W, H, C)
+    if cap < 0:
+        raise DvpError("dvp_jpeg_bound: bad geometry %dx%dx%d" % (W, H, C))
+    dst = np.empty(cap, np.uint8)
+    n = ctypes.c_longlong(0)
+    if L.dvp_jpeg_encode(device, _p(a), W, H, C, a.strides[0], int(quality), int(restart), _p(dst), cap, ctypes.byref(n)) != 0:
+        raise DvpError(L.dvp_jpeg_last_error().decode())
+    return dst[:n.value].tobytes()
 
 
 class Context:
@@ -240,6 +271,26 @@ class Context:
         radius = np.empty(L, np.int32)
         self._ck(self.L.dvp_download_maps_finish(self.h, _p(depth), _p(normal), _p(views), _p(weak), _p(radius)))
         return depth, normal, views, weak, radius
+
+    def preview_begin(self, kinds=PREVIEW_DEPTH | PREVIEW_NORMAL | PREVIEW_WEAK, quality=95):
+        """render + encode the previews of the current planes / weak map on the device (include/dvp_mvs.h dvp_preview_begin)"""
+        self._ck(self.L.dvp_preview_begin(self.h, int(kinds), int(quality)))
+
+    def preview_finish(self, kind):
+        """the JPEG file of one begun preview kind (PREVIEW_DEPTH / _NORMAL / _WEAK)"""
+        n = ctypes.c_longlong(0)
+        self.L.dvp_preview_finish(self.h, int(kind), None, 0, ctypes.byref(n))   # size query (fails on the capacity)
+        if n.value <= 0:
+            raise DvpError(self.L.dvp_last_error(self.h).decode())
+        dst = np.empty(n.value, np.uint8)
+        self._ck(self.L.dvp_preview_finish(self.h, int(kind), _p(dst), n.value, ctypes.byref(n)))
+        return dst.tobytes()
+
+    def preview_pixels(self, kind):
+        """the rendered BGR image of one begun preview kind, (H, W, 3) uint8"""
+        out = np.empty((self.H, self.W, 3), np.uint8)
+        self._ck(self.L.dvp_preview_pixels(self.h, int(kind), _p(out)))
+        return out
 
     def get(self, name):
         bid, dt, k = BUFFERS[name]

@@ -5,6 +5,7 @@
 // stream and every device buffer of one reference view; launches are queued back to back on that
 // stream (the reference calls cudaDeviceSynchronize after each of its 16+5*iters launches).
 #include "dvp_stages.hpp"
+#include "dvp_jpeg_enc.h"
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 #include <string>
@@ -1191,6 +1192,14 @@ struct dvp_ctx {
 	bool dl_busy = false;
 	bool dl_fetching = false;   // a dvp_download_maps_finish call is running right now (it ends in bounded time)
 	size_t coarse_alloc = 0;
+	// dvp_preview_begin / _finish: the rendered previews (BGR) and their encodes, one slot per kind; like maps_out they are
+	// overwritten by the next dvp_preview_begin only
+	uint8_t* pv_bgr[3] = { nullptr, nullptr, nullptr };
+	dvpjpeg::Encoder pv_enc[3];
+	unsigned long long* pv_total = nullptr;   // pinned: the encodes' data sizes
+	hipEvent_t pv_done = nullptr;             // the last dvp_preview_begin's work on `stream`
+	hipStream_t pv_copy = nullptr;            // the fetches of dvp_preview_finish / _pixels (any thread)
+	int pv_kinds = 0;
 	// dvp_save_state / dvp_restore_state: device-side copy of the per-pixel input state
 	f4* saved_planes = nullptr; uint32_t* saved_views = nullptr; uint8_t* saved_weak = nullptr; int* saved_radius = nullptr;
 	bool have_saved = false;
@@ -1387,6 +1396,11 @@ int dvp_ctx_destroy(dvp_ctx* c) {
 		c->dl_cv.wait(lk, [c] { return !c->dl_fetching; });
 	}
 	if (c->copy) { (void)hipStreamSynchronize(c->copy); (void)hipStreamDestroy(c->copy); }
+	if (c->pv_copy) { (void)hipStreamSynchronize(c->pv_copy); (void)hipStreamDestroy(c->pv_copy); }
+	if (c->stream) (void)hipStreamSynchronize(c->stream);
+	for (auto& e : c->pv_enc) dvpjpeg::encoder_free(e);
+	if (c->pv_total) (void)hipHostFree(c->pv_total);
+	if (c->pv_done) (void)hipEventDestroy(c->pv_done);
 	if (c->maps_host) (void)hipHostFree(c->maps_host);
 	if (c->stream) (void)hipStreamSynchronize(c->stream);
 	for (auto& e : c->events) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
@@ -2280,6 +2294,66 @@ int dvp_download_maps_finish(dvp_ctx* c, float* depth, float* normal_xyz, uint32
 	download_done(c);
 	return 0;
 }
+// ---- previews (ShowDepthMap / ShowNormalMap / ShowWeakImage + cv::imwrite, APD.cpp:694-812) ---------------------------------
+int dvp_preview_begin(dvp_ctx* c, int kinds, int quality) {
+	if (set_device(c)) return 1;
+	if (kinds < 1 || kinds > 7) { c->error = "dvp_preview_begin: kinds must be a non-empty set of DVP_PREVIEW_DEPTH | NORMAL | WEAK"; return 1; }
+	if (quality < 1 || quality > 100) { c->error = "dvp_preview_begin: quality must be 1..100"; return 1; }
+	c->pv_kinds = 0;
+	const size_t L = c->L;
+	for (int k = 0; k < 3; ++k)
+		if ((kinds >> k & 1) && !c->pv_bgr[k] && dalloc(c, &c->pv_bgr[k], L * 3, false)) return 1;
+	if (!c->pv_total) HIP_TRY(c, hipHostMalloc(reinterpret_cast<void**>(&c->pv_total), 3 * sizeof(unsigned long long), hipHostMallocDefault));
+	if (!c->pv_done) HIP_TRY(c, hipEventCreateWithFlags(&c->pv_done, hipEventDisableTiming));
+	if (!c->pv_copy) HIP_TRY(c, hipStreamCreateWithFlags(&c->pv_copy, hipStreamNonBlocking));
+	auto bgr = [&](int k) { return (kinds >> k & 1) ? c->pv_bgr[k] : nullptr; };
+	if (dvpjpeg::launch_render(c->stream, reinterpret_cast<const float*>(c->planes), c->weak_info, L, c->d.params.depth_min, c->d.params.depth_max,
+	                           bgr(0), bgr(1), bgr(2))) { c->error = "dvp_preview_begin: render launch failed"; return 1; }
+	for (int k = 0; k < 3; ++k)
+		if ((kinds >> k & 1) && dvpjpeg::encode_begin(c->pv_enc[k], c->stream, c->pv_bgr[k], (long long)c->W * 3, c->W, c->H, 3, quality, 0, &c->pv_total[k])) {
+			c->error = std::string("dvp_preview_begin: ") + c->pv_enc[k].error; return 1;
+		}
+	HIP_TRY(c, hipStreamSynchronize(c->stream));   // the one wait: the encodes' sizes
+	for (int k = 0; k < 3; ++k)
+		if ((kinds >> k & 1) && dvpjpeg::encode_write(c->pv_enc[k], c->stream, c->pv_total[k])) {
+			c->error = std::string("dvp_preview_begin: ") + c->pv_enc[k].error; return 1;
+		}
+	HIP_TRY(c, hipEventRecord(c->pv_done, c->stream));
+	c->pv_kinds = kinds;
+	return 0;
+}
+static int preview_slot(dvp_ctx* c, int kind, const char* who) {
+	t_finish_error.c = c;
+	t_finish_error.msg.clear();
+	const int k = kind == DVP_PREVIEW_DEPTH ? 0 : kind == DVP_PREVIEW_NORMAL ? 1 : kind == DVP_PREVIEW_WEAK ? 2 : -1;
+	if (k < 0 || !(c->pv_kinds >> k & 1)) { t_finish_error.msg = std::string(who) + ": that preview was not begun (dvp_preview_begin)"; return -1; }
+	if (hipSetDevice(c->device) != hipSuccess || hipEventSynchronize(c->pv_done) != hipSuccess) { t_finish_error.msg = std::string(who) + ": device error"; return -1; }
+	return k;
+}
+int dvp_preview_finish(dvp_ctx* c, int kind, uint8_t* dst, long long capacity, long long* bytes) {
+	const int k = preview_slot(c, kind, "dvp_preview_finish");
+	if (k < 0) return 1;
+	const dvpjpeg::Encoder& e = c->pv_enc[k];
+	const long long n = (long long)dvpjpeg::file_bytes(e);
+	if (bytes) *bytes = n;
+	if (!dst || capacity < n) { t_finish_error.msg = "dvp_preview_finish: capacity below the encoded size (*bytes)"; return 1; }
+	memcpy(dst, e.header, e.header_len);
+	if (hipMemcpyAsync(dst + e.header_len, e.out, e.data_bytes, hipMemcpyDeviceToHost, c->pv_copy) != hipSuccess || hipStreamSynchronize(c->pv_copy) != hipSuccess) {
+		t_finish_error.msg = "dvp_preview_finish: copy to the host failed"; return 1;
+	}
+	dst[n - 2] = 0xFF;
+	dst[n - 1] = 0xD9;
+	return 0;
+}
+int dvp_preview_pixels(dvp_ctx* c, int kind, uint8_t* bgr) {
+	const int k = preview_slot(c, kind, "dvp_preview_pixels");
+	if (k < 0) return 1;
+	if (!bgr || hipMemcpyAsync(bgr, c->pv_bgr[k], c->L * 3, hipMemcpyDeviceToHost, c->pv_copy) != hipSuccess || hipStreamSynchronize(c->pv_copy) != hipSuccess) {
+		t_finish_error.msg = "dvp_preview_pixels: copy to the host failed"; return 1;
+	}
+	return 0;
+}
+
 int dvp_download_maps(dvp_ctx* c, float* depth, float* normal_xyz, uint32_t* views, uint8_t* weak, int32_t* radius) {
 	if (!depth || !normal_xyz || !weak) { c->error = "dvp_download_maps: depth, normal and weak_info are required"; return 1; }
 	if (dvp_download_maps_begin(c, nullptr)) return 1;

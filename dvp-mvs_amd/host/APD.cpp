@@ -16,7 +16,8 @@
 
 static int g_device = 0;
 static uint64_t g_seed = 0x5eed5eedULL;
-void APD::SetDevice(int device) { g_device = device; }   // cudaSetDevice(argv[2]), main.cpp:430-434
+void APD::SetDevice(int device) { g_device = device; }
+int APD::GetDevice() { return g_device; }   // cudaSetDevice(argv[2]), main.cpp:430-434
 void APD::SetSeed(uint64_t seed) { g_seed = seed; }      // the reference seeds with clock64() (APD.cu:1270)
 static bool g_use_label_files = false;
 void APD::SetUseLabelFiles(bool on) { g_use_label_files = on; }
@@ -783,6 +784,22 @@ std::function<void()> APD::RunPatchMatchAndStageMaps(Mat& depth, Mat& normal, fl
 	return [c, d, n, v, w, r]() mutable {
 		if (dvp_download_maps_finish(c, d.ptr<float>(0), n.ptr<float>(0), v.ptr<uint32_t>(0), w.ptr<uint8_t>(0), r.empty() ? nullptr : r.ptr<int32_t>(0)) != 0)
 			DvpFatal("dvp_download_maps_finish failed");   // (the context may be gone by now: its error text is not read)
+	};
+}
+
+std::function<std::vector<std::vector<uint8_t>>()> APD::BeginPreviews(int quality) {
+	DVP_SAFE_CALL(ctx, dvp_preview_begin(ctx, DVP_PREVIEW_DEPTH | DVP_PREVIEW_NORMAL | DVP_PREVIEW_WEAK, quality));
+	dvp_ctx* const c = ctx;
+	return [c]() {
+		std::vector<std::vector<uint8_t>> files(3);
+		const int kinds[3] = { DVP_PREVIEW_DEPTH, DVP_PREVIEW_NORMAL, DVP_PREVIEW_WEAK };
+		for (int i = 0; i < 3; ++i) {
+			long long n = 0;
+			(void)dvp_preview_finish(c, kinds[i], nullptr, 0, &n);   // size query
+			files[i].resize(n > 0 ? (size_t)n : 0);
+			if (n <= 0 || dvp_preview_finish(c, kinds[i], files[i].data(), n, &n) != 0) DvpFatal("dvp_preview_finish failed");
+		}
+		return files;
 	};
 }
 

@@ -76,6 +76,11 @@ void ShutdownResultStore();
 // error convention of the reference (CudaSafeCall, APD.cpp:943-951): message on stderr + exit.  Every such exit of the
 // host library goes through DvpFatal; a multi-rank driver installs a hook that turns it into an agreed abort (comm.h).
 [[noreturn]] void DvpFatal(const std::string& message);
+// preview files (preview.cpp): written under a temporary name and renamed
+bool WriteFileAtomic(const path& file, const void* data, size_t bytes);
+bool WritePngRGB(const path& file, const uint8_t* rgb, int width, int height);
+bool WriteWeakPng(const path& file, const Mat& weak);        // weak.png, main.cpp:383-384
+bool WriteGreyJpeg(const path& file, const Mat& grey);       // rawedge_<s>.jpg, main.cpp:219-223
 void DvpSetFatalHook(void (*hook)(const char* message));
 void DvpSafeCall(int rc, dvp_ctx* ctx, const char* what, const char* file, int line);
 #define DVP_SAFE_CALL(ctx, expr) DvpSafeCall((expr), (ctx), #expr, __FILE__, __LINE__)
@@ -109,6 +114,11 @@ public:
 	float GetDepthMax();
 	// extensions (not in the reference): device selection, explicit seed, in-memory inputs
 	static void SetDevice(int device);
+	static int GetDevice();
+	// `apd --previews`: renders and encodes the view's three preview JPEGs (depth, normal, weak; ShowDepthMap / ShowNormalMap /
+	// ShowWeakImage, APD.cpp:694-812) on the device from the maps of the pass just run; the returned function fetches the files
+	// (any thread, before the staged maps are fetched: include/dvp_mvs.h dvp_preview_begin)
+	std::function<std::vector<std::vector<uint8_t>>()> BeginPreviews(int quality = 95);
 	static void SetSeed(uint64_t seed);
 	static void ReleasePooledContext();   // frees the recycled engine context and the image cache
 	// The shipped reference writes labels_<s>.dmb but never loads it (the load is commented out,

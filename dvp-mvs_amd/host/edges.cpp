@@ -165,5 +165,7 @@ void GetProblemEdges(const Problem& problem, const std::vector<path>& outputs) {
 	for (int r = 0; r < new_rows; ++r)
 		for (int c = 0; c < new_cols; ++c) u8.at<uint8_t>(r, c) = (uint8_t)std::min(255L, std::max(0L, std::lrintf(scaled.at<float>(r, c))));
 	Mat edge = EdgeSegment(scale, u8, 0, true);
+	const path rawedge = problem.result_folder / path("rawedge_" + std::to_string(scale) + ".jpg");   // main.cpp:219-223
+	if (problem.show_medium_result && !WriteGreyJpeg(rawedge, edge)) DvpFatal("cannot write " + rawedge.string());
 	PublishResult(edge_path, edge);
 }

@@ -43,6 +43,7 @@ struct Options {
 	int collective_timeout_s = 600;
 	bool sync_io = false;
 	bool host_rescale = false;
+	bool previews = false;                 // --previews: the reference's show_medium_result preview images (depth/normal/weak_<it>.jpg, weak.png, rawedge_<s>.jpg)
 	int views_in_flight = 0;               // --views-in-flight N: that many views of a pass at once (default 2) where the order allows it and the level is small; 1 = never
 	long long in_flight_pixels = 2 << 20;  // ... "small" = at most this many pixels (--in-flight-pixels)
 	std::string job, transport = "rccl";
@@ -188,6 +189,14 @@ ViewResult ProcessProblem(const Problem& problem, const std::function<float*(int
 		depth = Mat(height, width, CV_32FC1);
 		normal = Mat(height, width, CV_32FC3);
 	}
+	// previews (main.cpp:396-403): rendered and encoded from the context's planes right after the maps were staged; fetched by
+	// the background job before it fetches the maps (or here, when there are no staged maps and the context may be gone
+	// before the job runs)
+	const bool previews = problem.show_medium_result;
+	std::function<std::vector<std::vector<uint8_t>>()> fetch_previews;
+	std::vector<std::vector<uint8_t>> preview_files;
+	if (previews) fetch_previews = APD.BeginPreviews();
+	if (fetch_previews && !fetch_maps) { preview_files = fetch_previews(); fetch_previews = nullptr; }
 	lap(g_device_maps ? "RunPatchMatch" : "RunPatchMatch + download");
 	Mat pixel_states = APD.GetPixelStates();
 	Mat views = APD.GetSelectedViews();
@@ -221,6 +230,7 @@ ViewResult ProcessProblem(const Problem& problem, const std::function<float*(int
 	const bool timing = host_timing;
 	RunInBackground([=]() mutable {
 		const auto t0 = std::chrono::steady_clock::now();
+		if (fetch_previews) preview_files = fetch_previews();
 		if (fetch_maps) {
 			fetch_maps();
 			PublishResult(folder / "depths.dmb", depth);
@@ -266,9 +276,15 @@ ViewResult ProcessProblem(const Problem& problem, const std::function<float*(int
 		PublishResult(folder / "weak.bin", pixel_states);
 		PublishResult(folder / "selected_views.bin", views);
 		if (!radius.empty()) PublishResult(folder / "radius.bin", radius);
-		if (iteration == 15 || iteration == g_final_iteration) {   // main.cpp:378-382 (weak.png is a debug image: not written)
+		if (iteration == 15 || iteration == g_final_iteration) {   // main.cpp:378-384
 			writeDepthDmb(folder / "depths_geom.dmb", depth);
 			writeNormalDmb(folder / "normals.dmb", normal);
+			if (previews && !WriteWeakPng(folder / "weak.png", pixel_states)) DvpFatal("cannot write " + (folder / "weak.png").string());
+		}
+		const char* preview_names[3] = { "depth_", "normal_", "weak_" };   // ShowDepthMap / ShowNormalMap / ShowWeakImage, main.cpp:396-403
+		for (size_t i = 0; i < preview_files.size(); ++i) {
+			const path file = folder / (preview_names[i] + std::to_string(iteration) + ".jpg");
+			if (!WriteFileAtomic(file, preview_files[i].data(), preview_files[i].size())) DvpFatal("cannot write " + file.string());
 		}
 		if (timing) {
 			std::ostringstream line;
@@ -475,6 +491,7 @@ Options ParseOptions(int argc, char** argv) {
 		else if (s == "--sync-io") o.sync_io = true;               // no result cache / background worker / device rescale: the reference's synchronous file flow
 		else if (s == "--views-in-flight") { if (a + 1 < argc) o.views_in_flight = std::min(APD::kMaxViewsInFlight, std::max(1, atoi(argv[++a]))); }   // one pooled engine context per view in flight
 		else if (s == "--in-flight-pixels") { if (a + 1 < argc) o.in_flight_pixels = atoll(argv[++a]); }
+		else if (s == "--previews") o.previews = true;
 		else if (s == "--host-rescale") o.host_rescale = true;     // the coarser level's maps are up-sampled on the host (APD::SetDeviceRescale(false))
 		else if (s == "--fusion") { if (a + 1 < argc) o.fusion_kind = argv[++a]; }
 		else if (s == "--fusion-on") { if (a + 1 < argc) o.fusion_on_host = std::string(argv[++a]) == "host"; }   // device (default) | host
@@ -490,7 +507,7 @@ Options ParseOptions(int argc, char** argv) {
 
 int main(int argc, char** argv) {
 	if (argc < 2) {
-		std::cerr << "USAGE: apd dense_folder [gpu_index] [--max-src N] [--iters N] [--min-scale S] [--passes P] [--seed X] [--rank R --world N [--job ID]] [--jacobi] [--no-fusion | --fusion KIND] [--fusion-on device|host] [--views-in-flight N]\n";
+		std::cerr << "USAGE: apd dense_folder [gpu_index] [--previews] [--max-src N] [--iters N] [--min-scale S] [--passes P] [--seed X] [--rank R --world N [--job ID]] [--jacobi] [--no-fusion | --fusion KIND] [--fusion-on device|host] [--views-in-flight N]\n";
 		return EXIT_FAILURE;
 	}
 	const Options opt = ParseOptions(argc, argv);
@@ -526,6 +543,7 @@ int main(int argc, char** argv) {
 	DvpSetFatalHook([](const char* msg) { if (RankComm* c = RankComm::Current()) if (c->world() > 1) c->Abort(msg); });
 
 	std::vector<Problem> problems = ReadViewGraph(opt.dense_folder, opt.max_src);
+	for (Problem& p : problems) p.show_medium_result = opt.previews;
 	std::cout << "There are " << problems.size() << " problems needed to be processed!" << std::endl;
 	const std::vector<int> owner_of = AssignViews(problems, opt.world);
 	if (opt.world > 1) {

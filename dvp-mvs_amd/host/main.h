@@ -81,7 +81,7 @@ struct Problem {
 	std::vector<int> src_image_ids;
 	path dense_folder, result_folder;
 	int scale_size = 1;
-	bool show_medium_result = true;
+	bool show_medium_result = false;   // the reference's default is true (main.h:122); here the preview files are opt-in (apd --previews)
 	PatchMatchParams params;
 };
 

@@ -267,6 +267,31 @@ int dvp_fuse_download(dvp_fuse* job, float* points);
 /* statistics of the last dvp_fuse_view: rounds of the parallel claim resolution, pixels left to the sequential finish */
 int dvp_fuse_last_rounds(const dvp_fuse* job, int* rounds, int* rest);
 
+/* ---- preview images and baseline JPEG (ShowDepthMap / ShowNormalMap / ShowWeakImage + cv::imwrite, APD.cpp:694-812) ----
+ * JPEG files as cv::imwrite has libjpeg write them — JFIF 1.01, quality scaling of the Annex K tables (baseline), YCbCr 4:2:0
+ * (3 channels) or grey (1), the accurate integer DCT, the standard Huffman tables — plus a DRI segment and RST markers every
+ * `restart_mcus` MCUs (an MCU is 16x16 pixels in colour, 8x8 in grey), which is what lets the device code the segments in
+ * parallel.  Decoded, such a file gives the pixels of the same image written without restart markers. */
+enum { DVP_PREVIEW_DEPTH = 1, DVP_PREVIEW_NORMAL = 2, DVP_PREVIEW_WEAK = 4 };
+/* an upper bound of the file size of any image of that geometry (any quality, any restart interval); -1 for bad arguments */
+long long dvp_jpeg_bound(int width, int height, int channels);
+/* Stateless, host in / host out: pixels are `channels` (1, or 3 in BGR order) bytes per pixel, `pitch_bytes` per row;
+ * quality 1..100 (the reference's imwrite: 95); restart_mcus 1..65535, 0 = the engine's choice.  Writes the file
+ * to dst and its size to *bytes; if capacity is too small, *bytes still receives the size and the call fails. */
+int dvp_jpeg_encode(int device, const uint8_t* pixels, int width, int height, int channels, long long pitch_bytes, int quality,
+                    int restart_mcus, uint8_t* dst, long long capacity, long long* bytes);
+const char* dvp_jpeg_last_error(void);   /* the calling thread's last dvp_jpeg_encode error */
+/* Renders the previews named by `kinds` (DVP_PREVIEW_* bits) from the context's current planes and weak map — the maps the
+ * driver stores: depth = plane.w inside [params.depth_min, depth_max], else 0, state UNKNOWN where it is outside — and encodes
+ * them (quality 1..100, the engine's restart interval) on the context's stream; returns after one wait for the encoded sizes.
+ * _finish (the file: header, data, EOI) and _pixels (the BGR image before encoding, width * height * 3 bytes) may be called
+ * from any thread until the next dvp_preview_begin.  A driver begins the previews right after dvp_download_maps_begin and
+ * fetches them in the job that calls dvp_download_maps_finish, before that call: the next view's dvp_download_maps_begin then
+ * cannot come before the fetch.  Allocation failures are returned as errors (dvp_last_error). */
+int dvp_preview_begin(dvp_ctx* ctx, int kinds, int quality);
+int dvp_preview_finish(dvp_ctx* ctx, int kind, uint8_t* dst, long long capacity, long long* bytes);
+int dvp_preview_pixels(dvp_ctx* ctx, int kind, uint8_t* bgr);
+
 #ifdef __cplusplus
 }
 #endif

@@ -34,7 +34,8 @@ EXPORTS = ["dvp_ctx_create", "dvp_ctx_destroy", "dvp_ctx_reserve", "dvp_last_err
            "dvp_upload_buffer", "dvp_weak_count", "dvp_get_timings", "dvp_reset_timings", "dvp_eval_cost_vectors",
            "dvp_bench_cost_kernel", "dvp_build_id",
            "dvp_fuse_create", "dvp_fuse_destroy", "dvp_fuse_last_error", "dvp_fuse_set_view", "dvp_fuse_view", "dvp_fuse_view_graded", "dvp_fuse_count", "dvp_fuse_download", "dvp_fuse_last_rounds",
-           "dvp_jpeg_bound", "dvp_jpeg_encode", "dvp_jpeg_last_error", "dvp_preview_begin", "dvp_preview_finish", "dvp_preview_pixels"]
+           "dvp_jpeg_bound", "dvp_jpeg_encode", "dvp_jpeg_last_error", "dvp_preview_begin", "dvp_preview_finish", "dvp_preview_pixels",
+           "dvp_canny_edge_map", "dvp_edge_hysteresis", "dvp_edge_last_error", "dvp_edge_map_begin", "dvp_edge_map_finish"]
 PREVIEW_DEPTH, PREVIEW_NORMAL, PREVIEW_WEAK = 1, 2, 4
 
 
@@ -104,6 +105,12 @@ def lib():
         L.dvp_preview_begin.argtypes = [vp, ci, ci]
         L.dvp_preview_finish.argtypes = [vp, ci, vp, ll, ctypes.POINTER(ll)]
         L.dvp_preview_pixels.argtypes = [vp, ci, vp]
+        L.dvp_canny_edge_map.argtypes = [ci, vp, ci, ci, ll, vp]
+        L.dvp_edge_hysteresis.argtypes = [ci, vp, ci, ci, vp]
+        L.dvp_edge_last_error.restype = ctypes.c_char_p
+        L.dvp_edge_last_error.argtypes = []
+        L.dvp_edge_map_begin.argtypes = [vp, ci]
+        L.dvp_edge_map_finish.argtypes = [vp, vp]
         _LIB = L
     return _LIB
 
@@ -134,6 +141,34 @@ def jpeg_encode(pixels, quality=95, restart=0, device=0):
     if L.dvp_jpeg_encode(device, _p(a), W, H, C, a.strides[0], int(quality), int(restart), _p(dst), cap, ctypes.byref(n)) != 0:
         raise DvpError(L.dvp_jpeg_last_error().decode())
     return dst[:n.value].tobytes()
+
+
+def canny_edge_map(grey, device=0):
+    """the depth-edge prior (EdgeSegment mode 0) of a (H, W) uint8 image, computed on the GPU (include/dvp_mvs.h
+    dvp_canny_edge_map): (H, W) uint8, 255 = edge"""
+    L = lib()
+    a = np.asarray(grey)
+    assert a.dtype == np.uint8 and a.ndim == 2, (a.dtype, a.shape)
+    if a.strides[1] != 1 or a.strides[0] < a.shape[1]:
+        a = np.ascontiguousarray(a)
+    H, W = a.shape
+    out = np.empty((H, W), np.uint8)
+    if L.dvp_canny_edge_map(device, _p(a), W, H, a.strides[0], _p(out)) != 0:
+        raise DvpError(L.dvp_edge_last_error().decode())
+    return out
+
+
+def edge_hysteresis(map3, device=0):
+    """Canny's hysteresis alone on a (H, W) uint8 map of 0 = candidate, 1 = nothing, 2 = strong (dvp_edge_hysteresis):
+    (H, W) uint8, 255 = edge, no frame fix-ups"""
+    L = lib()
+    a = np.ascontiguousarray(map3, np.uint8)
+    assert a.ndim == 2, a.shape
+    H, W = a.shape
+    out = np.empty((H, W), np.uint8)
+    if L.dvp_edge_hysteresis(device, _p(a), W, H, _p(out)) != 0:
+        raise DvpError(L.dvp_edge_last_error().decode())
+    return out
 
 
 class Context:
@@ -290,6 +325,16 @@ class Context:
         """the rendered BGR image of one begun preview kind, (H, W, 3) uint8"""
         out = np.empty((self.H, self.W, 3), np.uint8)
         self._ck(self.L.dvp_preview_pixels(self.h, int(kind), _p(out)))
+        return out
+
+    def edge_map_begin(self, install=True):
+        """the Canny edge prior of image 0 on the context's stream; install: also into the context's edge buffer"""
+        self._ck(self.L.dvp_edge_map_begin(self.h, int(bool(install))))
+
+    def edge_map_finish(self):
+        """the oldest begun edge map not fetched yet, (H, W) uint8 (any thread)"""
+        out = np.empty((self.H, self.W), np.uint8)
+        self._ck(self.L.dvp_edge_map_finish(self.h, _p(out)))
         return out
 
     def get(self, name):

@@ -6,6 +6,7 @@
 // stream (the reference calls cudaDeviceSynchronize after each of its 16+5*iters launches).
 #include "dvp_stages.hpp"
 #include "dvp_jpeg_enc.h"
+#include "dvp_edges_run.h"
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 #include <string>
@@ -1200,6 +1201,18 @@ struct dvp_ctx {
 	hipEvent_t pv_done = nullptr;             // the last dvp_preview_begin's work on `stream`
 	hipStream_t pv_copy = nullptr;            // the fetches of dvp_preview_finish / _pixels (any thread)
 	int pv_kinds = 0;
+	// dvp_edge_map_begin / _finish: the Canny edge prior from image 0 (dvp_edges.hip).  Scratch and output maps exist from the
+	// first dvp_edge_map_begin (or dvp_ctx_reserve bit 3) on.  Two output slots: a driver fetches a view's map in the view's
+	// background job, when the context may have begun the next view's map already; _finish serves begun maps oldest first, and
+	// a third _begin overwrites the oldest map nobody fetched.
+	dvpedge::Scratch eg;
+	struct EdgeSlot { uint8_t* map = nullptr; hipEvent_t done = nullptr; unsigned long long seq = 0; bool pending = false, fetching = false; };
+	EdgeSlot eg_slot[2];
+	unsigned long long eg_seq = 0;
+	hipStream_t eg_copy = nullptr;            // the fetches of dvp_edge_map_finish (any thread)
+	std::mutex eg_m;
+	std::condition_variable eg_cv;
+	bool have_images = false;                 // dvp_upload_images* has run
 	// dvp_save_state / dvp_restore_state: device-side copy of the per-pixel input state
 	f4* saved_planes = nullptr; uint32_t* saved_views = nullptr; uint8_t* saved_weak = nullptr; int* saved_radius = nullptr;
 	bool have_saved = false;
@@ -1397,8 +1410,15 @@ int dvp_ctx_destroy(dvp_ctx* c) {
 	}
 	if (c->copy) { (void)hipStreamSynchronize(c->copy); (void)hipStreamDestroy(c->copy); }
 	if (c->pv_copy) { (void)hipStreamSynchronize(c->pv_copy); (void)hipStreamDestroy(c->pv_copy); }
+	{   // a dvp_edge_map_finish that is running on another thread
+		std::unique_lock<std::mutex> lk(c->eg_m);
+		c->eg_cv.wait(lk, [c] { return !c->eg_slot[0].fetching && !c->eg_slot[1].fetching; });
+	}
+	if (c->eg_copy) { (void)hipStreamSynchronize(c->eg_copy); (void)hipStreamDestroy(c->eg_copy); }
 	if (c->stream) (void)hipStreamSynchronize(c->stream);
 	for (auto& e : c->pv_enc) dvpjpeg::encoder_free(e);
+	dvpedge::scratch_free(c->eg);
+	for (auto& sl : c->eg_slot) { if (sl.map) (void)hipFree(sl.map); if (sl.done) (void)hipEventDestroy(sl.done); }
 	if (c->pv_total) (void)hipHostFree(c->pv_total);
 	if (c->pv_done) (void)hipEventDestroy(c->pv_done);
 	if (c->maps_host) (void)hipHostFree(c->maps_host);
@@ -1475,11 +1495,15 @@ static int upload_planes(dvp_ctx* c, float* dst, const float* const* src, int pi
 }
 int dvp_upload_images(dvp_ctx* c, const float* const* images, int pitch_floats) {
 	c->anchor_tab_valid = false;
-	return upload_planes(c, c->image_stage, images, pitch_floats, hipMemcpyHostToDevice, c->images);
+	if (upload_planes(c, c->image_stage, images, pitch_floats, hipMemcpyHostToDevice, c->images)) return 1;
+	c->have_images = true;
+	return 0;
 }
 int dvp_upload_images_device(dvp_ctx* c, const float* const* images, int pitch_floats) {
 	c->anchor_tab_valid = false;
-	return upload_planes(c, c->image_stage, images, pitch_floats, hipMemcpyDeviceToDevice, c->images);
+	if (upload_planes(c, c->image_stage, images, pitch_floats, hipMemcpyDeviceToDevice, c->images)) return 1;
+	c->have_images = true;
+	return 0;
 }
 static int ensure_depths(dvp_ctx* c) {
 	if (!c->depths) {
@@ -2081,11 +2105,23 @@ int dvp_run_stage(dvp_ctx* c, int stage, int iter, int colour) {
 // pyramid level): flags bit 0 = the split strong update's cost block, bit 1 = the view-compacted sweep passes' buffers;
 // weak_pixels > 0: anchor table and hand-over buffers of the weak update for that many WEAK pixels.  Nothing here is required —
 // every launch site allocates what it lacks — and a buffer that does not fit selects the fall-back form exactly as there.
+// scratch + the first `slots` output maps of dvp_edge_map_begin
+static int ensure_edge_buffers(dvp_ctx* c, int slots) {
+	if (dvpedge::scratch_reserve(c->eg, c->L)) { c->error = "dvp_edge_map: out of device memory"; return 1; }
+	for (int k = 0; k < slots; ++k) {
+		dvp_ctx::EdgeSlot& sl = c->eg_slot[k];
+		if (!sl.map && hipMalloc(reinterpret_cast<void**>(&sl.map), c->L) != hipSuccess) { (void)hipGetLastError(); sl.map = nullptr; c->error = "dvp_edge_map: out of device memory"; return 1; }
+		if (!sl.done && hipEventCreateWithFlags(&sl.done, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); sl.done = nullptr; c->error = "dvp_edge_map: hipEventCreate failed"; return 1; }
+	}
+	return 0;
+}
+
 int dvp_ctx_reserve(dvp_ctx* c, int weak_pixels, int flags) {
 	if (set_device(c)) return 1;
 	if (flags & 1) ensure_strong_split_buffers(c);
 	if (flags & 2) ensure_sweep_buffers(c);
 	if ((flags & 4) && !c->no_images8 && !c->no_images16 && ensure_images16(c)) return 1;
+	if ((flags & 8) && ensure_edge_buffers(c, 2)) return 1;
 	if (weak_pixels > 0) {
 		const size_t wc = std::min<size_t>((size_t)weak_pixels, c->L);
 		if (grow_anchor_table(c, wc)) return 1;
@@ -2294,6 +2330,62 @@ int dvp_download_maps_finish(dvp_ctx* c, float* depth, float* normal_xyz, uint32
 	download_done(c);
 	return 0;
 }
+// ---- the Canny edge prior from the resident image 0 (EdgeSegment mode 0, APD.cpp:404-466; dvp_edges.hip) ----------------------
+int dvp_edge_map_begin(dvp_ctx* c, int install) {
+	if (set_device(c)) return 1;
+	if (!c->have_images) { c->error = "dvp_edge_map_begin: no images in the context yet (dvp_upload_images)"; return 1; }
+	if (c->W < 3 || c->H < 3) { c->error = "dvp_edge_map_begin: width and height must be at least 3"; return 1; }
+	int k;
+	{   // the slot of this map: a free one, else the older of the two (its map was never fetched)
+		std::unique_lock<std::mutex> lk(c->eg_m);
+		k = !c->eg_slot[0].pending ? 0 : (!c->eg_slot[1].pending ? 1 : (c->eg_slot[0].seq < c->eg_slot[1].seq ? 0 : 1));
+		c->eg_cv.wait(lk, [c, k] { return !c->eg_slot[k].fetching; });   // (a running copy ends in bounded time)
+		c->eg_slot[k].pending = false;
+	}
+	if (ensure_edge_buffers(c, k + 1)) return 1;
+	dvp_ctx::EdgeSlot& sl = c->eg_slot[k];
+	// image 0 of the row-pair planes: texel (x, y) is the first float of pair (x, y) (dvp_dev.hpp img_texel)
+	const float* img0 = c->images + (size_t)c->d.org * 2;
+	if (dvpedge::launch_grey_from_float(c->stream, c->eg, img0, (long long)c->pitch, 2, c->W, c->H) || dvpedge::launch_suppress(c->stream, c->eg, c->W, c->H, true) ||
+	    dvpedge::launch_hysteresis(c->stream, c->eg, c->W, c->H) || dvpedge::launch_fixups(c->stream, c->eg, c->W, c->H, sl.map, install ? c->edge : nullptr)) {
+		c->error = "dvp_edge_map_begin: launch failed"; return 1;
+	}
+	HIP_TRY(c, hipEventRecord(sl.done, c->stream));
+	std::lock_guard<std::mutex> lk(c->eg_m);
+	sl.seq = ++c->eg_seq;
+	sl.pending = true;
+	return 0;
+}
+
+int dvp_edge_map_finish(dvp_ctx* c, uint8_t* edge) {
+	t_finish_error.c = c;
+	t_finish_error.msg.clear();
+	auto fail = [](const char* what) { t_finish_error.msg = what; return 1; };
+	if (!edge) return fail("dvp_edge_map_finish: edge is required");
+	if (hipSetDevice(c->device) != hipSuccess) { (void)hipGetLastError(); return fail("dvp_edge_map_finish: hipSetDevice failed"); }
+	int k = -1;
+	{
+		std::lock_guard<std::mutex> lk(c->eg_m);
+		for (int i = 0; i < 2; ++i)
+			if (c->eg_slot[i].pending && !c->eg_slot[i].fetching && (k < 0 || c->eg_slot[i].seq < c->eg_slot[k].seq)) k = i;
+		if (k < 0) return fail("dvp_edge_map_finish: no edge map was begun (dvp_edge_map_begin)");
+		c->eg_slot[k].fetching = true;
+		if (!c->eg_copy && hipStreamCreateWithFlags(&c->eg_copy, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); c->eg_copy = nullptr; c->eg_slot[k].fetching = false; return fail("dvp_edge_map_finish: hipStreamCreate failed"); }
+	}
+	dvp_ctx::EdgeSlot& sl = c->eg_slot[k];
+	// (two fetches at once share eg_copy: they queue behind each other, each waits for its own copy)
+	const bool ok = hipEventSynchronize(sl.done) == hipSuccess && hipMemcpyAsync(edge, sl.map, c->L, hipMemcpyDeviceToHost, c->eg_copy) == hipSuccess &&
+	                hipStreamSynchronize(c->eg_copy) == hipSuccess;
+	{
+		std::lock_guard<std::mutex> lk(c->eg_m);
+		sl.fetching = false;
+		sl.pending = false;
+	}
+	c->eg_cv.notify_all();
+	if (!ok) { (void)hipGetLastError(); return fail("dvp_edge_map_finish: copy to the host failed"); }
+	return 0;
+}
+
 // ---- previews (ShowDepthMap / ShowNormalMap / ShowWeakImage + cv::imwrite, APD.cpp:694-812) ---------------------------------
 int dvp_preview_begin(dvp_ctx* c, int kinds, int quality) {
 	if (set_device(c)) return 1;

@@ -21,6 +21,9 @@ int APD::GetDevice() { return g_device; }   // cudaSetDevice(argv[2]), main.cpp:
 void APD::SetSeed(uint64_t seed) { g_seed = seed; }      // the reference seeds with clock64() (APD.cu:1270)
 static bool g_use_label_files = false;
 void APD::SetUseLabelFiles(bool on) { g_use_label_files = on; }
+static bool g_edges_on_device = false;
+void APD::SetEdgesOnDevice(bool on) { g_edges_on_device = on; }
+bool APD::EdgesOnDevice() { return g_edges_on_device; }
 // DVP_HOST_TIMING=1: wall time of the parts of the host steps (tools/e2e_timing.sh folds them per pass)
 namespace {
 struct HostLap {
@@ -177,7 +180,7 @@ void APD::PrewarmContext(int w, int h, int ni, int scale_size) {
 			const long long per_px = 1408ll * (ni - 1) + 544 + 32ll * (ni - 1);
 			const long long budget = (long long)w * h <= 8000000ll ? 48000000000ll : 24000000000ll;
 			const long long room = std::min<long long>((long long)w * h * 9 / 10, budget / per_px);
-			(void)dvp_ctx_reserve(c, (int)std::min<long long>(room, 2000000000ll), scale_size > 1 ? 7 : 3);
+			(void)dvp_ctx_reserve(c, (int)std::min<long long>(room, 2000000000ll), (scale_size > 1 ? 7 : 3) | (g_edges_on_device ? 8 : 0));   // (+ the edge prior's scratch)
 		}
 		g_prewarm.ctx = c;
 	});
@@ -386,6 +389,10 @@ void APD::SetResidentDownloader(void (*copy)(float*, const float*, size_t)) { g_
 
 APD::~APD() {                        // APD.cpp:989-1043
 	delete[] plane_hypotheses_host;
+	if (edge_on_device) {   // announced in SupportInitialization: readers of the file wait for it
+		if (ctx) TakeEdgeFetch()();
+		else PublishResult(edge_file, Mat());
+	}
 	if (!ctx) return;
 	give_pooled(ctx, ctx_device, width, height, num_images);
 }
@@ -624,9 +631,18 @@ void APD::CoarseStateToHost() {
 void APD::SupportInitialization() {
 	int scale = 0;
 	while ((1 << scale) < problem.scale_size) scale++;
+	edge_on_device = false;
 	if (problem.params.use_edge || problem.params.use_limit) {
 		path edge_path = problem.result_folder / path("edges_" + std::to_string(scale) + ".dmb");
-		if (!LoadResult(edge_path, edge_host) || edge_host.cols != width || edge_host.rows != height) {
+		// (the passes GetProblemEdges runs before: the photometric pass of a level, main.cpp:480)
+		if (g_edges_on_device && problem.params.use_edge && !problem.params.geom_consistency && !ResultExists(edge_path)) {
+			ExpectResult(edge_path);
+			edge_on_device = true;
+			edge_file = edge_path;
+			rawedge_file = problem.result_folder / path("rawedge_" + std::to_string(scale) + ".jpg");
+			edge_host = Mat();   // nothing to upload: the engine writes the map into the context (CudaSpaceInitialization)
+			ViewLog() << "Edge map: made on the device" << std::endl;
+		} else if (!LoadResult(edge_path, edge_host) || edge_host.cols != width || edge_host.rows != height) {
 			// edges_<s>.dmb is written by GetProblemEdges (edges.cpp) before the first pass; a caller
 			// that skipped it gets an empty edge map (no edge pixels)
 			edge_host = Mat::zeros(height, width, CV_8UC1);
@@ -714,6 +730,8 @@ void APD::CudaSpaceInitialization() {
 	}
 	image_format = dvp_image_format(ctx);
 	lap("images upload");
+	// the edge prior from image 0, into the context's edge buffer (no upload below); queued behind nothing the host waits for
+	if (edge_on_device) DVP_SAFE_CALL(ctx, dvp_edge_map_begin(ctx, 1));
 	if (params_host.geom_consistency) {
 		if (!depths_device.empty()) {
 			DVP_SAFE_CALL(ctx, dvp_upload_depths_device(ctx, depths_device.data(), width));
@@ -728,7 +746,7 @@ void APD::CudaSpaceInitialization() {
 		DVP_SAFE_CALL(ctx, dvp_upload_state_rescaled(ctx, coarse_depth.cols, coarse_depth.rows, coarse_depth.ptr<float>(0), coarse_normal.ptr<float>(0),
 			coarse_views.ptr<uint32_t>(0), coarse_weak.empty() ? nullptr : coarse_weak.ptr<uint8_t>(0),
 			coarse_radius.empty() ? nullptr : coarse_radius.ptr<int32_t>(0), problem.params.strong_radius,
-			(problem.params.use_edge || problem.params.use_limit) ? edge_host.ptr<uint8_t>(0) : nullptr,
+			((problem.params.use_edge || problem.params.use_limit) && !edge_on_device) ? edge_host.ptr<uint8_t>(0) : nullptr,
 			(problem.params.use_label && !label_host.empty()) ? label_host.ptr<int32_t>(0) : nullptr));
 		weak_count = dvp_weak_count(ctx);
 		ViewLog() << "Weak count: " << weak_count << " / " << width * height << " = " << (float)weak_count / (float)(width * height) * 100 << "%" << std::endl;
@@ -738,7 +756,7 @@ void APD::CudaSpaceInitialization() {
 	}
 	DVP_SAFE_CALL(ctx, dvp_upload_state(ctx, reinterpret_cast<const float*>(plane_hypotheses_host),
 		selected_views_host.ptr<uint32_t>(0), weak_info_host.ptr<uint8_t>(0),
-		(problem.params.use_edge || problem.params.use_limit) ? edge_host.ptr<uint8_t>(0) : nullptr,
+		((problem.params.use_edge || problem.params.use_limit) && !edge_on_device) ? edge_host.ptr<uint8_t>(0) : nullptr,
 		(problem.params.use_label && !label_host.empty()) ? label_host.ptr<int32_t>(0) : nullptr,
 		problem.params.use_radius ? radius_host.ptr<int32_t>(0) : nullptr));
 	lap("state upload");
@@ -803,10 +821,31 @@ std::function<std::vector<std::vector<uint8_t>>()> APD::BeginPreviews(int qualit
 	};
 }
 
+std::function<void()> APD::TakeEdgeFetch() {
+	if (!edge_on_device) return nullptr;
+	edge_on_device = false;
+	dvp_ctx* const c = ctx;
+	const int w = width, h = height;
+	const path file = edge_file, rawedge = rawedge_file;
+	const bool previews = problem.show_medium_result;
+	return [c, w, h, file, rawedge, previews]() {
+		Mat edge(h, w, CV_8UC1);
+		if (dvp_edge_map_finish(c, edge.ptr<uint8_t>(0)) != 0) DvpFatal("dvp_edge_map_finish failed");   // (the context may be gone by now: its error text is not read)
+		if (previews && !WriteGreyJpeg(rawedge, edge)) DvpFatal("cannot write " + rawedge.string());   // main.cpp:219-223
+		PublishResult(file, edge);
+	};
+}
+
 float4 APD::GetPlaneHypothesis(int r, int c) { return plane_hypotheses_host[c + r * width]; }   // APD.cpp:1706-1708
 int APD::GetPixelSelectedViews(int r, int c) { return selected_views_host.at<int>(r, c); }
 void APD::SetPixelSelectedViews(int r, int c, int v) { selected_views_host.at<int>(r, c) = v; }
-Mat APD::GetEdge() { return edge_host; }
+Mat APD::GetEdge() {
+	if (edge_on_device) {   // made on the device: publish it now and read it back
+		TakeEdgeFetch()();
+		if (!LoadResult(edge_file, edge_host)) edge_host = Mat::zeros(height, width, CV_8UC1);
+	}
+	return edge_host;
+}
 Mat APD::GetPixelStates() { return weak_info_host; }
 Mat APD::GetSelectedViews() { return selected_views_host; }
 Mat APD::GetRadiusMap() { return radius_host; }

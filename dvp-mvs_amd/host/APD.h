@@ -125,6 +125,15 @@ public:
 	// APD.cpp:1630-1633): its label map stays zero unless MVS4/<id>.dmb needs rescaling.  true: load
 	// labels_<s>.dmb in SupportInitialization (what the commented-out lines do).  Default false.
 	static void SetUseLabelFiles(bool on);
+	// `apd --edges-on gpu`.  true: a view whose edges_<s>.dmb neither exists nor is cached nor announced does not wait for a
+	// helper thread's EdgeSegment: SupportInitialization announces the file, CudaSpaceInitialization has the engine compute the
+	// map from the context's image 0 straight into the context's edge buffer (dvp_edge_map_begin), and the function
+	// TakeEdgeFetch returns copies it to the host, writes rawedge_<s>.jpg if previews are on and publishes the file (any
+	// thread, after this object is gone too; the destructor runs it if nobody took it).  Same bytes as the host's map.
+	// Default false: GetProblemEdges makes the file (edges.cpp).
+	static void SetEdgesOnDevice(bool on);
+	static bool EdgesOnDevice();
+	std::function<void()> TakeEdgeFetch();   // empty when this view's edge map came from its file
 	// true (default): a pass that starts from maps of another size (REFINE_INIT on a finer pyramid level) hands them to the
 	// engine at their own size and RescaleMatToTargetSize runs there (dvp_upload_state_rescaled); false: the five host-side
 	// rescales + the plane assembly of the reference's flow (APD.cpp:1176-1180, 1440-1456, 1656-1659).  Same maps either way.
@@ -178,5 +187,7 @@ private:
 	int ctx_device = 0;
 	DvpTimings timings{};
 	int image_format = 0;
+	bool edge_on_device = false;   // the edge map is made by the engine (SetEdgesOnDevice) and its file still has to be published
+	path edge_file, rawedge_file;
 };
 #endif

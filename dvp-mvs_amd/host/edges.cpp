@@ -125,7 +125,8 @@ std::vector<path> ProblemEdgeOutputs(const Problem& problem) {
 	std::vector<path> out;
 	const path edge_path = problem.result_folder / path("edges_" + std::to_string(scale) + ".dmb");
 	const path label_path = problem.result_folder / path("labels_" + std::to_string(scale) + ".dmb");
-	if (problem.params.use_edge && !ResultExists(edge_path)) out.push_back(edge_path);
+	// (APD::SetEdgesOnDevice: the view itself has the engine make the map, APD::SupportInitialization)
+	if (problem.params.use_edge && !APD::EdgesOnDevice() && !ResultExists(edge_path)) out.push_back(edge_path);
 	if (problem.params.use_label && !ResultExists(label_path)) out.push_back(label_path);
 	return out;
 }

@@ -43,6 +43,7 @@ struct Options {
 	int collective_timeout_s = 600;
 	bool sync_io = false;
 	bool host_rescale = false;
+	bool edges_on_gpu = false;             // --edges-on gpu: the Canny edge prior is made by the engine from the resident image (APD::SetEdgesOnDevice)
 	bool previews = false;                 // --previews: the reference's show_medium_result preview images (depth/normal/weak_<it>.jpg, weak.png, rawedge_<s>.jpg)
 	int views_in_flight = 0;               // --views-in-flight N: that many views of a pass at once (default 2) where the order allows it and the level is small; 1 = never
 	long long in_flight_pixels = 2 << 20;  // ... "small" = at most this many pixels (--in-flight-pixels)
@@ -197,6 +198,10 @@ ViewResult ProcessProblem(const Problem& problem, const std::function<float*(int
 	std::vector<std::vector<uint8_t>> preview_files;
 	if (previews) fetch_previews = APD.BeginPreviews();
 	if (fetch_previews && !fetch_maps) { preview_files = fetch_previews(); fetch_previews = nullptr; }
+	// --edges-on gpu: the edge map the engine made for this view (APD::SetEdgesOnDevice) is fetched and published as
+	// edges_<s>.dmb by the background job, or here when that job may run after the context is gone
+	std::function<void()> fetch_edge = APD.TakeEdgeFetch();
+	if (fetch_edge && !fetch_maps) { fetch_edge(); fetch_edge = nullptr; }
 	lap(g_device_maps ? "RunPatchMatch" : "RunPatchMatch + download");
 	Mat pixel_states = APD.GetPixelStates();
 	Mat views = APD.GetSelectedViews();
@@ -230,6 +235,7 @@ ViewResult ProcessProblem(const Problem& problem, const std::function<float*(int
 	const bool timing = host_timing;
 	RunInBackground([=]() mutable {
 		const auto t0 = std::chrono::steady_clock::now();
+		if (fetch_edge) fetch_edge();
 		if (fetch_previews) preview_files = fetch_previews();
 		if (fetch_maps) {
 			fetch_maps();
@@ -492,6 +498,11 @@ Options ParseOptions(int argc, char** argv) {
 		else if (s == "--views-in-flight") { if (a + 1 < argc) o.views_in_flight = std::min(APD::kMaxViewsInFlight, std::max(1, atoi(argv[++a]))); }   // one pooled engine context per view in flight
 		else if (s == "--in-flight-pixels") { if (a + 1 < argc) o.in_flight_pixels = atoll(argv[++a]); }
 		else if (s == "--previews") o.previews = true;
+		else if (s == "--edges-on" && a + 1 < argc) {
+			const std::string where = argv[++a];
+			if (where != "host" && where != "gpu") { std::cerr << "--edges-on takes host or gpu\n"; std::exit(1); }
+			o.edges_on_gpu = where == "gpu";
+		}
 		else if (s == "--host-rescale") o.host_rescale = true;     // the coarser level's maps are up-sampled on the host (APD::SetDeviceRescale(false))
 		else if (s == "--fusion") { if (a + 1 < argc) o.fusion_kind = argv[++a]; }
 		else if (s == "--fusion-on") { if (a + 1 < argc) o.fusion_on_host = std::string(argv[++a]) == "host"; }   // device (default) | host
@@ -507,7 +518,7 @@ Options ParseOptions(int argc, char** argv) {
 
 int main(int argc, char** argv) {
 	if (argc < 2) {
-		std::cerr << "USAGE: apd dense_folder [gpu_index] [--previews] [--max-src N] [--iters N] [--min-scale S] [--passes P] [--seed X] [--rank R --world N [--job ID]] [--jacobi] [--no-fusion | --fusion KIND] [--fusion-on device|host] [--views-in-flight N]\n";
+		std::cerr << "USAGE: apd dense_folder [gpu_index] [--previews] [--max-src N] [--iters N] [--min-scale S] [--passes P] [--seed X] [--rank R --world N [--job ID]] [--jacobi] [--no-fusion | --fusion KIND] [--fusion-on device|host] [--edges-on host|gpu] [--views-in-flight N]\n";
 		return EXIT_FAILURE;
 	}
 	const Options opt = ParseOptions(argc, argv);
@@ -534,6 +545,7 @@ int main(int argc, char** argv) {
 	}
 	APD::SetSeed(opt.seed);
 	APD::SetUseLabelFiles(opt.label_files);
+	APD::SetEdgesOnDevice(opt.edges_on_gpu);
 	SetResultCache(!opt.sync_io);
 	APD::SetDeviceRescale(!opt.sync_io && !opt.host_rescale);
 	g_device_maps = !opt.sync_io && !opt.host_rescale;

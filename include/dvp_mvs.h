@@ -175,7 +175,7 @@ int dvp_restore_state(dvp_ctx* ctx);
  * for the next pyramid level, so that no multi-GB allocation lands inside a view's launches (the reference allocates everything in
  * CudaSpaceInitialization, APD.cpp:1497-1613).  flags: bit 0 = the split strong update's cost block, bit 1 = the view-compacted
  * DepthToWeak / LocalRefine passes' buffers, bit 2 = the binary16 image planes of format 2 (dvp_image_format: a context for a
- * down-sampled pyramid level); weak_pixels > 0: the weak update's anchor table and hand-over buffers for that many
+ * down-sampled pyramid level), bit 3 = the scratch and output maps of dvp_edge_map_begin (8 + 1 bytes per pixel); weak_pixels > 0: the weak update's anchor table and hand-over buffers for that many
  * WEAK pixels.  Never required: every launch site (and dvp_upload_images*) allocates what it lacks. */
 int dvp_ctx_reserve(dvp_ctx* ctx, int weak_pixels, int flags);
 int dvp_set_params(dvp_ctx* ctx, const DvpParams* params);                     /* APD.cpp:1607-1608 */
@@ -291,6 +291,28 @@ const char* dvp_jpeg_last_error(void);   /* the calling thread's last dvp_jpeg_e
 int dvp_preview_begin(dvp_ctx* ctx, int kinds, int quality);
 int dvp_preview_finish(dvp_ctx* ctx, int kind, uint8_t* dst, long long capacity, long long* bytes);
 int dvp_preview_pixels(dvp_ctx* ctx, int kind, uint8_t* bgr);
+
+/* ---- the depth-edge prior (EdgeSegment(scale, image, mode 0, use_canny), APD.cpp:404-466) on the device -------------------------
+ * The median-adaptive Canny whose result fills DVP_BUF_EDGE: median of the grey histogram over bins 0..254 (-1 if more than half
+ * of the pixels are 255), thresholds (int)((1 - 0.67f) * median) and median, cv::Canny's rules for 8-bit input with aperture 3 and
+ * L2gradient (Sobel with replicated border, squared thresholds, sector suppression with the fixed-point tan 22.5 test, hysteresis
+ * over 8-connected candidates), 255 / 0, then the frame fix-ups of APD.cpp:452-463.  Integer arithmetic: the map is the same on
+ * every device and equal to the host mirror's EdgeSegment byte for byte.  Widths and heights below 3 are rejected (the fix-ups
+ * read columns 1, W - 2 and rows 1, H - 2).  The number of launches does not depend on the image. */
+/* Stateless, host in / host out: grey is width x height bytes, `pitch_bytes` per row; edge_out receives width * height bytes. */
+int dvp_canny_edge_map(int device, const uint8_t* grey, int width, int height, long long pitch_bytes, uint8_t* edge_out);
+/* The hysteresis step alone: map3 holds 0 = candidate, 1 = nothing, 2 = strong per pixel (width * height bytes); edge_out
+ * receives 255 where a pixel is strong or a candidate 8-connected through candidates to a strong pixel, else 0; no fix-ups. */
+int dvp_edge_hysteresis(int device, const uint8_t* map3, int width, int height, uint8_t* edge_out);
+const char* dvp_edge_last_error(void);   /* the calling thread's last dvp_canny_edge_map / dvp_edge_hysteresis error */
+/* The edge map of the context's image 0 — grey byte = the texel rounded to nearest (ties to even) and saturated, what the
+ * reference's convertTo(CV_8UC1) gives (main.cpp:205-214) — on the context's stream, without a host wait; install != 0 also
+ * writes it to DVP_BUF_EDGE, as dvp_upload_state(..., edge, ...) of the same map would.  An error before the first
+ * dvp_upload_images*.  _finish copies the map (width * height bytes) to the host and may be called from another thread once
+ * _begin has returned.  The context keeps the maps of the last two _begin calls: _finish returns the oldest one not fetched
+ * yet, so a driver may begin the next view's map on a context before the last view's background job has fetched its own. */
+int dvp_edge_map_begin(dvp_ctx* ctx, int install);
+int dvp_edge_map_finish(dvp_ctx* ctx, uint8_t* edge);
 
 #ifdef __cplusplus
 }

@@ -35,7 +35,8 @@ EXPORTS = ["dvp_ctx_create", "dvp_ctx_destroy", "dvp_ctx_reserve", "dvp_last_err
            "dvp_bench_cost_kernel", "dvp_build_id",
            "dvp_fuse_create", "dvp_fuse_destroy", "dvp_fuse_last_error", "dvp_fuse_set_view", "dvp_fuse_view", "dvp_fuse_view_graded", "dvp_fuse_count", "dvp_fuse_download", "dvp_fuse_last_rounds",
            "dvp_jpeg_bound", "dvp_jpeg_encode", "dvp_jpeg_last_error", "dvp_preview_begin", "dvp_preview_finish", "dvp_preview_pixels",
-           "dvp_canny_edge_map", "dvp_edge_hysteresis", "dvp_edge_last_error", "dvp_edge_map_begin", "dvp_edge_map_finish"]
+           "dvp_canny_edge_map", "dvp_edge_hysteresis", "dvp_edge_last_error", "dvp_edge_map_begin", "dvp_edge_map_finish",
+           "dvp_clean_selected_views", "dvp_viewclean_last_error", "dvp_set_view_cleanup"]
 PREVIEW_DEPTH, PREVIEW_NORMAL, PREVIEW_WEAK = 1, 2, 4
 
 
@@ -111,6 +112,10 @@ def lib():
         L.dvp_edge_last_error.argtypes = []
         L.dvp_edge_map_begin.argtypes = [vp, ci]
         L.dvp_edge_map_finish.argtypes = [vp, vp]
+        L.dvp_clean_selected_views.argtypes = [ci, vp, ci, ci, ci, ci, vp]
+        L.dvp_viewclean_last_error.restype = ctypes.c_char_p
+        L.dvp_viewclean_last_error.argtypes = []
+        L.dvp_set_view_cleanup.argtypes = [vp, ci, ci, ci]
         _LIB = L
     return _LIB
 
@@ -168,6 +173,19 @@ def edge_hysteresis(map3, device=0):
     out = np.empty((H, W), np.uint8)
     if L.dvp_edge_hysteresis(device, _p(a), W, H, _p(out)) != 0:
         raise DvpError(L.dvp_edge_last_error().decode())
+    return out
+
+
+def clean_selected_views(views, num_src, min_region, device=0):
+    """ProcessProblem's visibility-mask clean-up of a (H, W) uint32 map of selected-view words, computed on the GPU
+    (include/dvp_mvs.h dvp_clean_selected_views): (H, W) uint32"""
+    L = lib()
+    a = np.ascontiguousarray(views, np.uint32)
+    assert a.ndim == 2, a.shape
+    H, W = a.shape
+    out = np.empty((H, W), np.uint32)
+    if L.dvp_clean_selected_views(device, _p(a), W, H, int(num_src), int(min_region), _p(out)) != 0:
+        raise DvpError(L.dvp_viewclean_last_error().decode())
     return out
 
 
@@ -326,6 +344,10 @@ class Context:
         out = np.empty((self.H, self.W, 3), np.uint8)
         self._ck(self.L.dvp_preview_pixels(self.h, int(kind), _p(out)))
         return out
+
+    def set_view_cleanup(self, enable, num_src=0, min_region=0):
+        """while on, download_maps (begin) hands out the selected-view words after the visibility-mask clean-up"""
+        self._ck(self.L.dvp_set_view_cleanup(self.h, int(bool(enable)), int(num_src), int(min_region)))
 
     def edge_map_begin(self, install=True):
         """the Canny edge prior of image 0 on the context's stream; install: also into the context's edge buffer"""

@@ -9,6 +9,26 @@
 
 namespace dvpedge {
 
+// parent words are read and written by other CUs inside the same launch: device-scope atomics (L2), never L1
+struct DevMem {
+	__host__ __device__ unsigned load(const unsigned* p) const {
+#if defined(__HIP_DEVICE_COMPILE__)
+		return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#else
+		return *p;
+#endif
+	}
+	__host__ __device__ unsigned min(unsigned* p, unsigned v) const {
+#if defined(__HIP_DEVICE_COMPILE__)
+		return __hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#else
+		const unsigned o = *p;
+		if (v < o) *p = v;
+		return o;
+#endif
+	}
+};
+
 // Device scratch of one map, 7 bytes per pixel (+ 1 per output map the caller keeps); grows, and is kept for the next map of
 // the same or a smaller size.
 struct Scratch {

@@ -7,6 +7,7 @@
 #include "dvp_stages.hpp"
 #include "dvp_jpeg_enc.h"
 #include "dvp_edges_run.h"
+#include "dvp_viewclean_run.h"
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 #include <string>
@@ -1183,7 +1184,7 @@ struct dvp_ctx {
 	int* weak_counts = nullptr;  // scratch of the device-side compaction: per-slot black / red counts, per-chunk counts, then 3 totals
 	int* weak_totals_host = nullptr;   // pinned: (black, red, all)
 	uint8_t* coarse = nullptr;   // staging of the coarser level's maps (dvp_upload_state_rescaled)
-	uint8_t* maps_out = nullptr; // staging of dvp_download_maps: depth [L] f32, normal [L][3] f32, states [L] u8, selected views [L] u32, radius [L] i32
+	uint8_t* maps_out = nullptr; // staging of dvp_download_maps: depth [L] f32, normal [L][3] f32, selected views [L] u32, radius [L] i32, states [L] u8 (words first: all aligned)
 	// dvp_download_maps_begin / _finish: the copies to the host run on their own stream, from any thread, while this context is
 	// already on its next view; `dl_busy` = maps_out holds maps that have not been fetched yet
 	hipStream_t copy = nullptr;
@@ -1213,6 +1214,11 @@ struct dvp_ctx {
 	std::mutex eg_m;
 	std::condition_variable eg_cv;
 	bool have_images = false;                 // dvp_upload_images* has run
+	// dvp_set_view_cleanup: the visibility-mask clean-up of the staged selected-view words (dvp_viewclean.hip).  The scratch exists
+	// from the first dvp_download_maps_begin with the clean-up on (or dvp_ctx_reserve bit 4) on.
+	dvpvc::Scratch vc;
+	bool vc_on = false;
+	int vc_num_src = 0, vc_min_region = 0;
 	// dvp_save_state / dvp_restore_state: device-side copy of the per-pixel input state
 	f4* saved_planes = nullptr; uint32_t* saved_views = nullptr; uint8_t* saved_weak = nullptr; int* saved_radius = nullptr;
 	bool have_saved = false;
@@ -1418,6 +1424,7 @@ int dvp_ctx_destroy(dvp_ctx* c) {
 	if (c->stream) (void)hipStreamSynchronize(c->stream);
 	for (auto& e : c->pv_enc) dvpjpeg::encoder_free(e);
 	dvpedge::scratch_free(c->eg);
+	dvpvc::scratch_free(c->vc);
 	for (auto& sl : c->eg_slot) { if (sl.map) (void)hipFree(sl.map); if (sl.done) (void)hipEventDestroy(sl.done); }
 	if (c->pv_total) (void)hipHostFree(c->pv_total);
 	if (c->pv_done) (void)hipEventDestroy(c->pv_done);
@@ -2122,6 +2129,7 @@ int dvp_ctx_reserve(dvp_ctx* c, int weak_pixels, int flags) {
 	if (flags & 2) ensure_sweep_buffers(c);
 	if ((flags & 4) && !c->no_images8 && !c->no_images16 && ensure_images16(c)) return 1;
 	if ((flags & 8) && ensure_edge_buffers(c, 2)) return 1;
+	if ((flags & 16) && dvpvc::scratch_reserve(c->vc, c->L, c->NI - 1)) { c->error = "dvp_ctx_reserve: out of device memory (view clean-up)"; return 1; }
 	if (weak_pixels > 0) {
 		const size_t wc = std::min<size_t>((size_t)weak_pixels, c->L);
 		if (grow_anchor_table(c, wc)) return 1;
@@ -2271,13 +2279,18 @@ int dvp_download_maps_begin(dvp_ctx* c, float* depth_device_copy) {
 	if (!c->maps_out && dalloc(c, &c->maps_out, L * 25, false)) return fail();
 	float* d_depth = reinterpret_cast<float*>(c->maps_out);
 	float* d_normal = d_depth + L;
-	uint8_t* d_state = c->maps_out + L * 16;
+	uint8_t* d_state = c->maps_out + L * 24;
+	uint32_t* d_views = reinterpret_cast<uint32_t*>(c->maps_out + L * 16);
 	hipLaunchKernelGGL(dvp_unpack_maps, dim3((unsigned)((L + 255) / 256)), dim3(256), 0, c->stream, c->planes, c->weak_info, L, c->d.params.depth_min, c->d.params.depth_max,
 	                   d_depth, d_normal, d_state);
 	if (hipGetLastError() != hipSuccess) { c->error = "dvp_download_maps_begin: launch failed"; return fail(); }
 	// the view maps and the radius map are live state: the next view's uploads overwrite them
-	if (hipMemcpyAsync(c->maps_out + L * 17, c->selected_views, L * 4, hipMemcpyDeviceToDevice, c->stream) != hipSuccess ||
-	    hipMemcpyAsync(c->maps_out + L * 21, c->radius, L * 4, hipMemcpyDeviceToDevice, c->stream) != hipSuccess ||
+	if (c->vc_on) {   // dvp_set_view_cleanup: the staged words are the cleaned ones; the device state keeps the raw ones
+		if (dvpvc::scratch_reserve(c->vc, L, c->vc_num_src)) { c->error = "dvp_download_maps_begin: out of device memory (view clean-up)"; return fail(); }
+		if (dvpvc::launch_clean(c->stream, c->vc, c->selected_views, c->W, c->H, c->vc_num_src, c->vc_min_region, d_views)) { c->error = "dvp_download_maps_begin: launch failed (view clean-up)"; return fail(); }
+	}
+	if ((!c->vc_on && hipMemcpyAsync(d_views, c->selected_views, L * 4, hipMemcpyDeviceToDevice, c->stream) != hipSuccess) ||
+	    hipMemcpyAsync(c->maps_out + L * 20, c->radius, L * 4, hipMemcpyDeviceToDevice, c->stream) != hipSuccess ||
 	    (depth_device_copy && hipMemcpyAsync(depth_device_copy, d_depth, L * 4, hipMemcpyDeviceToDevice, c->stream) != hipSuccess) ||
 	    hipStreamSynchronize(c->stream) != hipSuccess) { c->error = "dvp_download_maps_begin: device copies failed"; return fail(); }
 	return 0;
@@ -2303,7 +2316,7 @@ int dvp_download_maps_finish(dvp_ctx* c, float* depth, float* normal_xyz, uint32
 		if (hipMemcpyAsync(c->maps_host, c->maps_out, L * 25, hipMemcpyDeviceToHost, c->copy) != hipSuccess || hipStreamSynchronize(c->copy) != hipSuccess)
 			return fail("dvp_download_maps_finish: copy to the host failed");
 		struct Part { void* dst; size_t off, bytes; };
-		const Part parts[5] = { { depth, 0, L * 4 }, { normal_xyz, L * 4, L * 12 }, { weak, L * 16, L }, { views, L * 17, L * 4 }, { radius, L * 21, L * 4 } };
+		const Part parts[5] = { { depth, 0, L * 4 }, { normal_xyz, L * 4, L * 12 }, { weak, L * 24, L }, { views, L * 16, L * 4 }, { radius, L * 20, L * 4 } };
 		std::vector<std::thread> team;
 		const uint8_t* src = c->maps_host;
 		for (const Part& pt : parts) {
@@ -2323,13 +2336,22 @@ int dvp_download_maps_finish(dvp_ctx* c, float* depth, float* normal_xyz, uint32
 	const uint8_t* m = c->maps_out;
 	if (hipMemcpyAsync(depth, m, L * 4, hipMemcpyDeviceToHost, c->copy) != hipSuccess ||
 	    hipMemcpyAsync(normal_xyz, m + L * 4, L * 12, hipMemcpyDeviceToHost, c->copy) != hipSuccess ||
-	    hipMemcpyAsync(weak, m + L * 16, L, hipMemcpyDeviceToHost, c->copy) != hipSuccess ||
-	    (views && hipMemcpyAsync(views, m + L * 17, L * 4, hipMemcpyDeviceToHost, c->copy) != hipSuccess) ||
-	    (radius && hipMemcpyAsync(radius, m + L * 21, L * 4, hipMemcpyDeviceToHost, c->copy) != hipSuccess) ||
+	    hipMemcpyAsync(weak, m + L * 24, L, hipMemcpyDeviceToHost, c->copy) != hipSuccess ||
+	    (views && hipMemcpyAsync(views, m + L * 16, L * 4, hipMemcpyDeviceToHost, c->copy) != hipSuccess) ||
+	    (radius && hipMemcpyAsync(radius, m + L * 20, L * 4, hipMemcpyDeviceToHost, c->copy) != hipSuccess) ||
 	    hipStreamSynchronize(c->copy) != hipSuccess) return fail("dvp_download_maps_finish: copies to the host failed");
 	download_done(c);
 	return 0;
 }
+// ---- the visibility-mask clean-up of the staged words (main.cpp:311-363; dvp_viewclean.hip) ------------------------------------
+int dvp_set_view_cleanup(dvp_ctx* c, int enable, int num_src, int min_region) {
+	if (enable && (num_src < 0 || num_src > 32)) { c->error = "dvp_set_view_cleanup: num_src must be 0 ... 32 (one bit of a word per source view)"; return 1; }
+	c->vc_on = enable != 0;
+	c->vc_num_src = enable ? num_src : 0;
+	c->vc_min_region = enable ? min_region : 0;
+	return 0;
+}
+
 // ---- the Canny edge prior from the resident image 0 (EdgeSegment mode 0, APD.cpp:404-466; dvp_edges.hip) ----------------------
 int dvp_edge_map_begin(dvp_ctx* c, int install) {
 	if (set_device(c)) return 1;

@@ -24,6 +24,9 @@ void APD::SetUseLabelFiles(bool on) { g_use_label_files = on; }
 static bool g_edges_on_device = false;
 void APD::SetEdgesOnDevice(bool on) { g_edges_on_device = on; }
 bool APD::EdgesOnDevice() { return g_edges_on_device; }
+static bool g_cleanup_on_device = false;
+void APD::SetCleanupOnDevice(bool on) { g_cleanup_on_device = on; }
+bool APD::CleanupOnDevice() { return g_cleanup_on_device; }
 // DVP_HOST_TIMING=1: wall time of the parts of the host steps (tools/e2e_timing.sh folds them per pass)
 namespace {
 struct HostLap {
@@ -180,7 +183,7 @@ void APD::PrewarmContext(int w, int h, int ni, int scale_size) {
 			const long long per_px = 1408ll * (ni - 1) + 544 + 32ll * (ni - 1);
 			const long long budget = (long long)w * h <= 8000000ll ? 48000000000ll : 24000000000ll;
 			const long long room = std::min<long long>((long long)w * h * 9 / 10, budget / per_px);
-			(void)dvp_ctx_reserve(c, (int)std::min<long long>(room, 2000000000ll), (scale_size > 1 ? 7 : 3) | (g_edges_on_device ? 8 : 0));   // (+ the edge prior's scratch)
+			(void)dvp_ctx_reserve(c, (int)std::min<long long>(room, 2000000000ll), (scale_size > 1 ? 7 : 3) | (g_edges_on_device ? 8 : 0) | (g_cleanup_on_device ? 16 : 0));   // (+ the edge prior's and the view clean-up's scratch)
 		}
 		g_prewarm.ctx = c;
 	});
@@ -784,6 +787,7 @@ void APD::RunPatchMatchToMaps(Mat& depth, Mat& normal) {
 	if (!problem.params.use_radius) radius_host = Mat::zeros(height, width, CV_32S);
 	depth = Mat(height, width, CV_32FC1);
 	normal = Mat(height, width, CV_32FC3);
+	DVP_SAFE_CALL(ctx, dvp_set_view_cleanup(ctx, 0, 0, 0));   // (a pooled context keeps the last view's setting; this caller gets the raw words)
 	DVP_SAFE_CALL(ctx, dvp_download_maps(ctx, depth.ptr<float>(0), normal.ptr<float>(0), selected_views_host.ptr<uint32_t>(0),
 		weak_info_host.ptr<uint8_t>(0), problem.params.use_radius ? radius_host.ptr<int32_t>(0) : nullptr));
 	DVP_SAFE_CALL(ctx, dvp_get_timings(ctx, &timings));
@@ -794,6 +798,9 @@ std::function<void()> APD::RunPatchMatchAndStageMaps(Mat& depth, Mat& normal, fl
 	if (!problem.params.use_radius) radius_host = Mat::zeros(height, width, CV_32S);
 	depth = Mat(height, width, CV_32FC1);
 	normal = Mat(height, width, CV_32FC3);
+	// (a pooled context keeps the last view's setting: set it for every view)
+	const int region_side = 8 / problem.scale_size;
+	DVP_SAFE_CALL(ctx, dvp_set_view_cleanup(ctx, g_cleanup_on_device ? 1 : 0, (int)problem.src_image_ids.size(), 20 * region_side * region_side));
 	DVP_SAFE_CALL(ctx, dvp_download_maps_begin(ctx, depth_device_copy));
 	DVP_SAFE_CALL(ctx, dvp_get_timings(ctx, &timings));
 	// (the Mats share their buffers with the copies held here: they stay alive with the function)

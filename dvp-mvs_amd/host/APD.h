@@ -134,6 +134,12 @@ public:
 	static void SetEdgesOnDevice(bool on);
 	static bool EdgesOnDevice();
 	std::function<void()> TakeEdgeFetch();   // empty when this view's edge map came from its file
+	// `apd --cleanup-on gpu`.  true: RunPatchMatchAndStageMaps has the engine run ProcessProblem's visibility-mask clean-up
+	// (main.cpp:311-363) on the staged selected-view words (dvp_set_view_cleanup with the view's source count and
+	// min_region = 20 * (8 / scale_size)^2): the words its fetch returns are final, and the driver's background job skips its
+	// Connect loop.  Flows that do not stage maps on the device keep the host loop.  Same words either way.  Default false.
+	static void SetCleanupOnDevice(bool on);
+	static bool CleanupOnDevice();
 	// true (default): a pass that starts from maps of another size (REFINE_INIT on a finer pyramid level) hands them to the
 	// engine at their own size and RescaleMatToTargetSize runs there (dvp_upload_state_rescaled); false: the five host-side
 	// rescales + the plane assembly of the reference's flow (APD.cpp:1176-1180, 1440-1456, 1656-1659).  Same maps either way.

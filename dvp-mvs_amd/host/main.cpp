@@ -44,6 +44,7 @@ struct Options {
 	bool sync_io = false;
 	bool host_rescale = false;
 	bool edges_on_gpu = false;             // --edges-on gpu: the Canny edge prior is made by the engine from the resident image (APD::SetEdgesOnDevice)
+	bool cleanup_on_gpu = false;           // --cleanup-on gpu: the visibility-mask clean-up runs in the engine on the staged selected-view words (APD::SetCleanupOnDevice)
 	bool previews = false;                 // --previews: the reference's show_medium_result preview images (depth/normal/weak_<it>.jpg, weak.png, rawedge_<s>.jpg)
 	int views_in_flight = 0;               // --views-in-flight N: that many views of a pass at once (default 2) where the order allows it and the level is small; 1 = never
 	long long in_flight_pixels = 2 << 20;  // ... "small" = at most this many pixels (--in-flight-pixels)
@@ -233,6 +234,8 @@ ViewResult ProcessProblem(const Problem& problem, const std::function<float*(int
 	const int scale_size = problem.scale_size;
 	const int iteration = problem.iteration;
 	const bool timing = host_timing;
+	// --cleanup-on gpu: the engine cleaned the staged words (APD::SetCleanupOnDevice); flows without staged maps keep the host loop
+	const bool cleaned_on_device = fetch_maps && APD::CleanupOnDevice();
 	RunInBackground([=]() mutable {
 		const auto t0 = std::chrono::steady_clock::now();
 		if (fetch_edge) fetch_edge();
@@ -249,9 +252,17 @@ ViewResult ProcessProblem(const Problem& problem, const std::function<float*(int
 		// Visibility clean-up (main.cpp:311-363): per source view, every 4-connected region of pixels that do
 		// NOT select the view and is smaller than 20 * (8 / scale)^2 pixels is switched to "selected".
 		const int min_region = 20 * (8 / scale_size) * (8 / scale_size);
+		// DVP_RAW_VIEWS_DIR=<dir> (host clean-up only): the words as the pass left them, <dir>/<view folder>_<iteration>.bin, so that
+		// a test can tell whether the clean-up had anything to do
+		if (const char* raw_dir = cleaned_on_device ? nullptr : std::getenv("DVP_RAW_VIEWS_DIR")) {
+			const path file = path(raw_dir) / (folder.filename().string() + "_" + std::to_string(iteration) + ".bin");
+			if (!views.empty() && !WriteFileAtomic(file, views.ptr<uint8_t>(0), (size_t)width * height * 4)) DvpFatal("cannot write " + file.string());
+		}
+		if (cleaned_on_device) std::cout << "Visibility clean-up: on the device\n" << std::flush;   // (the words fetched above are final)
+		const int nhost = cleaned_on_device ? 0 : nsrc;
 		std::vector<Mat> fill(nsrc);   // per source: 1 where the bit has to be set
 #pragma omp parallel for schedule(dynamic, 1) num_threads(nsrc < 8 ? (nsrc > 0 ? nsrc : 1) : 8)
-		for (int i = 0; i < nsrc; ++i) {
+		for (int i = 0; i < nhost; ++i) {
 			Mat visible(height, width, CV_8UC1);
 			for (int r = 0; r < height; ++r) {
 				const uint32_t* w = views.ptr<uint32_t>(r);
@@ -270,7 +281,7 @@ ViewResult ProcessProblem(const Problem& problem, const std::function<float*(int
 			}
 		}
 #pragma omp parallel for schedule(static) num_threads(HostThreads())
-		for (int r = 0; r < height; ++r) {
+		for (int r = 0; r < (cleaned_on_device ? 0 : height); ++r) {
 			uint32_t* w = views.ptr<uint32_t>(r);
 			for (int c = 0; c < width; ++c) {
 				unsigned int mask = 0;
@@ -503,6 +514,11 @@ Options ParseOptions(int argc, char** argv) {
 			if (where != "host" && where != "gpu") { std::cerr << "--edges-on takes host or gpu\n"; std::exit(1); }
 			o.edges_on_gpu = where == "gpu";
 		}
+		else if (s == "--cleanup-on" && a + 1 < argc) {
+			const std::string where = argv[++a];
+			if (where != "host" && where != "gpu") { std::cerr << "--cleanup-on takes host or gpu\n"; std::exit(1); }
+			o.cleanup_on_gpu = where == "gpu";
+		}
 		else if (s == "--host-rescale") o.host_rescale = true;     // the coarser level's maps are up-sampled on the host (APD::SetDeviceRescale(false))
 		else if (s == "--fusion") { if (a + 1 < argc) o.fusion_kind = argv[++a]; }
 		else if (s == "--fusion-on") { if (a + 1 < argc) o.fusion_on_host = std::string(argv[++a]) == "host"; }   // device (default) | host
@@ -518,7 +534,7 @@ Options ParseOptions(int argc, char** argv) {
 
 int main(int argc, char** argv) {
 	if (argc < 2) {
-		std::cerr << "USAGE: apd dense_folder [gpu_index] [--previews] [--max-src N] [--iters N] [--min-scale S] [--passes P] [--seed X] [--rank R --world N [--job ID]] [--jacobi] [--no-fusion | --fusion KIND] [--fusion-on device|host] [--edges-on host|gpu] [--views-in-flight N]\n";
+		std::cerr << "USAGE: apd dense_folder [gpu_index] [--previews] [--max-src N] [--iters N] [--min-scale S] [--passes P] [--seed X] [--rank R --world N [--job ID]] [--jacobi] [--no-fusion | --fusion KIND] [--fusion-on device|host] [--edges-on host|gpu] [--cleanup-on host|gpu] [--views-in-flight N]\n";
 		return EXIT_FAILURE;
 	}
 	const Options opt = ParseOptions(argc, argv);
@@ -546,6 +562,7 @@ int main(int argc, char** argv) {
 	APD::SetSeed(opt.seed);
 	APD::SetUseLabelFiles(opt.label_files);
 	APD::SetEdgesOnDevice(opt.edges_on_gpu);
+	APD::SetCleanupOnDevice(opt.cleanup_on_gpu);
 	SetResultCache(!opt.sync_io);
 	APD::SetDeviceRescale(!opt.sync_io && !opt.host_rescale);
 	g_device_maps = !opt.sync_io && !opt.host_rescale;

@@ -175,7 +175,8 @@ int dvp_restore_state(dvp_ctx* ctx);
  * for the next pyramid level, so that no multi-GB allocation lands inside a view's launches (the reference allocates everything in
  * CudaSpaceInitialization, APD.cpp:1497-1613).  flags: bit 0 = the split strong update's cost block, bit 1 = the view-compacted
  * DepthToWeak / LocalRefine passes' buffers, bit 2 = the binary16 image planes of format 2 (dvp_image_format: a context for a
- * down-sampled pyramid level), bit 3 = the scratch and output maps of dvp_edge_map_begin (8 + 1 bytes per pixel); weak_pixels > 0: the weak update's anchor table and hand-over buffers for that many
+ * down-sampled pyramid level), bit 3 = the scratch and output maps of dvp_edge_map_begin (8 + 1 bytes per pixel), bit 4 = the scratch of dvp_set_view_cleanup
+ * (8 bytes per pixel and source view); weak_pixels > 0: the weak update's anchor table and hand-over buffers for that many
  * WEAK pixels.  Never required: every launch site (and dvp_upload_images*) allocates what it lacks. */
 int dvp_ctx_reserve(dvp_ctx* ctx, int weak_pixels, int flags);
 int dvp_set_params(dvp_ctx* ctx, const DvpParams* params);                     /* APD.cpp:1607-1608 */
@@ -313,6 +314,23 @@ const char* dvp_edge_last_error(void);   /* the calling thread's last dvp_canny_
  * yet, so a driver may begin the next view's map on a context before the last view's background job has fetched its own. */
 int dvp_edge_map_begin(dvp_ctx* ctx, int install);
 int dvp_edge_map_finish(dvp_ctx* ctx, uint8_t* edge);
+
+/* ---- the visibility-mask clean-up of ProcessProblem (main.cpp:311-363) on the device ----------------------------------------------
+ * For every bit i < num_src of the selected-view words: the 4-connected components (no diagonal contact) of the pixels whose bit i
+ * is clear are formed, and  out bit i = in bit i | (the pixel's component has fewer than min_region pixels); a component of exactly
+ * min_region pixels stays clear, min_region <= 0 changes no bit below num_src.  Bits >= num_src are 0 in out; num_src = 0 gives
+ * zeros.  The reference's driver passes min_region = 20 * (8 / scale_size)^2 in integer arithmetic.  Integer and exact: equal to
+ * the host mirror's Connect + fill loop word for word.  Four launches whatever the words hold. */
+/* Stateless, host in / host out: views and out are width * height words (out may be views); width, height >= 1; num_src outside
+ * 0 ... 32 is an error.  Scratch: 8 * num_src bytes per pixel, for the duration of the call. */
+int dvp_clean_selected_views(int device, const uint32_t* views, int width, int height, int num_src, int min_region, uint32_t* out);
+const char* dvp_viewclean_last_error(void);   /* the calling thread's last dvp_clean_selected_views error */
+/* enable != 0: from now on dvp_download_maps_begin (and with it dvp_download_maps) cleans the STAGED copy of the selected-view words
+ * with these arguments, on the context's stream before its wait: _finish hands out the cleaned words, DVP_BUF_SELECTED_VIEWS keeps
+ * the raw ones (as weak_info keeps the states the UNKNOWN rule changes in the staged copy).  Off by default; enable = 0 restores
+ * exactly what dvp_download_maps_begin did before.  The scratch (8 * num_src bytes per pixel) is allocated at the first use or by
+ * dvp_ctx_reserve bit 4 and freed with the context. */
+int dvp_set_view_cleanup(dvp_ctx* ctx, int enable, int num_src, int min_region);
 
 #ifdef __cplusplus
 }

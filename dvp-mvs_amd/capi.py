@@ -36,7 +36,8 @@ EXPORTS = ["dvp_ctx_create", "dvp_ctx_destroy", "dvp_ctx_reserve", "dvp_last_err
            "dvp_fuse_create", "dvp_fuse_destroy", "dvp_fuse_last_error", "dvp_fuse_set_view", "dvp_fuse_view", "dvp_fuse_view_graded", "dvp_fuse_count", "dvp_fuse_download", "dvp_fuse_last_rounds",
            "dvp_jpeg_bound", "dvp_jpeg_encode", "dvp_jpeg_last_error", "dvp_preview_begin", "dvp_preview_finish", "dvp_preview_pixels",
            "dvp_canny_edge_map", "dvp_edge_hysteresis", "dvp_edge_last_error", "dvp_edge_map_begin", "dvp_edge_map_finish",
-           "dvp_clean_selected_views", "dvp_viewclean_last_error", "dvp_set_view_cleanup"]
+           "dvp_clean_selected_views", "dvp_viewclean_last_error", "dvp_set_view_cleanup",
+           "dvp_labels_sizes", "dvp_labels_create", "dvp_labels_destroy", "dvp_labels_run", "dvp_labels_stage", "dvp_labels_timings", "dvp_label_map", "dvp_labels_last_error"]
 PREVIEW_DEPTH, PREVIEW_NORMAL, PREVIEW_WEAK = 1, 2, 4
 
 
@@ -116,6 +117,16 @@ def lib():
         L.dvp_viewclean_last_error.restype = ctypes.c_char_p
         L.dvp_viewclean_last_error.argtypes = []
         L.dvp_set_view_cleanup.argtypes = [vp, ci, ci, ci]
+        pi = ctypes.POINTER(ci)
+        L.dvp_labels_sizes.argtypes = [ci, ci, ci, pi, pi, pi, pi, pi]
+        L.dvp_labels_create.argtypes = [ci, ctypes.POINTER(vp)]
+        L.dvp_labels_destroy.argtypes = [vp]
+        L.dvp_labels_run.argtypes = [vp, vp, ci, ci, ll, ci, vp]
+        L.dvp_labels_stage.argtypes = [vp, ci, vp]
+        L.dvp_labels_timings.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ll)]
+        L.dvp_label_map.argtypes = [ci, vp, ci, ci, ll, ci, vp]
+        L.dvp_labels_last_error.restype = ctypes.c_char_p
+        L.dvp_labels_last_error.argtypes = []
         _LIB = L
     return _LIB
 
@@ -187,6 +198,80 @@ def clean_selected_views(views, num_src, min_region, device=0):
     if L.dvp_clean_selected_views(device, _p(a), W, H, int(num_src), int(min_region), _p(out)) != 0:
         raise DvpError(L.dvp_viewclean_last_error().decode())
     return out
+
+
+def labels_sizes(width, height, scale):
+    """dict(quarter=(rows, cols), level=(rows, cols), weak_tex_num=n) of the label prior (dvp_labels_sizes)"""
+    L = lib()
+    v = [ctypes.c_int(0) for _ in range(5)]
+    if L.dvp_labels_sizes(int(width), int(height), int(scale), *[ctypes.byref(x) for x in v]) != 0:
+        raise DvpError(L.dvp_labels_last_error().decode())
+    return dict(quarter=(v[1].value, v[0].value), level=(v[3].value, v[2].value), weak_tex_num=v[4].value)
+
+
+def _grey_rows(grey):
+    a = np.asarray(grey)
+    assert a.dtype == np.uint8 and a.ndim == 2, (a.dtype, a.shape)
+    if a.strides[1] != 1 or a.strides[0] < a.shape[1]:
+        a = np.ascontiguousarray(a)
+    return a
+
+
+def label_map(grey, scale, device=0):
+    """the label prior (EdgeSegment mode 1) of a full-size (H, W) uint8 image at pyramid level `scale`, computed on the GPU
+    (include/dvp_mvs.h dvp_label_map): level-size int32, 0 = textured, -1 = a small flat region, k >= 1 = a flat region"""
+    L = lib()
+    a = _grey_rows(grey)
+    H, W = a.shape
+    out = np.empty(labels_sizes(W, H, scale)["level"], np.int32)
+    if L.dvp_label_map(device, _p(a), W, H, a.strides[0], int(scale), _p(out)) != 0:
+        raise DvpError(L.dvp_labels_last_error().decode())
+    return out
+
+
+class LabelJob:
+    """a dvp_labels job: its own stream and device scratch, kept from one image to the next"""
+    STAGES = dict(quarter=(0, np.uint8), texture=(1, np.uint8), region=(2, np.int32), lines=(3, np.uint8), resized=(4, np.uint8), cleaned=(5, np.uint8))
+
+    def __init__(self, device=0):
+        self.L = lib()
+        h = ctypes.c_void_p()
+        if self.L.dvp_labels_create(device, ctypes.byref(h)) != 0:
+            raise DvpError(self.L.dvp_labels_last_error().decode())
+        self.h, self.sizes = h, None
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.dvp_labels_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def run(self, grey, scale):
+        a = _grey_rows(grey)
+        H, W = a.shape
+        sizes = labels_sizes(W, H, scale)
+        out = np.empty(sizes["level"], np.int32)
+        if self.L.dvp_labels_run(self.h, _p(a), W, H, a.strides[0], int(scale), _p(out)) != 0:
+            raise DvpError(self.L.dvp_labels_last_error().decode())
+        self.sizes = sizes
+        return out
+
+    def stage(self, name):
+        """an intermediate map of the last run: quarter, texture, region, lines (quarter size), resized, cleaned (level size)"""
+        which, dt = self.STAGES[name]
+        shape = self.sizes["level" if which >= 4 else "quarter"] if self.sizes else (1, 1)
+        out = np.empty(shape, dt)
+        if self.L.dvp_labels_stage(self.h, which, _p(out)) != 0:
+            raise DvpError(self.L.dvp_labels_last_error().decode())
+        return out
+
+    def timings(self):
+        """dict(part_a_ms, host_ms, part_b_ms, regions, outline_points) of the last run"""
+        ms, n = (ctypes.c_double * 3)(), (ctypes.c_longlong * 2)()
+        if self.L.dvp_labels_timings(self.h, ms, n) != 0:
+            raise DvpError(self.L.dvp_labels_last_error().decode())
+        return dict(part_a_ms=ms[0], host_ms=ms[1], part_b_ms=ms[2], regions=int(n[0]), outline_points=int(n[1]))
 
 
 class Context:

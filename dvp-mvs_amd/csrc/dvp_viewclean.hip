@@ -97,7 +97,8 @@ void scratch_free(Scratch& s) {
 	s = Scratch();
 }
 
-int launch_clean(hipStream_t stream, Scratch& s, const uint32_t* views, int W, int H, int num_src, int min_region, uint32_t* out) {
+// steps 1-3: after them parent leads every clear pixel to its component's root, whose size word holds the component's pixels
+int launch_components(hipStream_t stream, Scratch& s, const uint32_t* views, int W, int H, int num_src) {
 	const size_t L = (size_t)W * H;
 	unsigned* parent = s.words;
 	unsigned* size = s.words + (size_t)num_src * L;
@@ -109,7 +110,13 @@ int launch_clean(hipStream_t stream, Scratch& s, const uint32_t* views, int W, i
 		hipLaunchKernelGGL(dvp_vc_seams, dim3((unsigned)((items + 255) / 256 > 0 ? (items + 255) / 256 : 1), (unsigned)num_src), dim3(256), 0, stream, views, W, H, parent, L, items);
 		hipLaunchKernelGGL(dvp_vc_rollup, dim3(per_pixel, (unsigned)num_src), dim3(256), 0, stream, parent, size, L);
 	}
-	hipLaunchKernelGGL(dvp_vc_resolve, dim3(per_pixel), dim3(256), 0, stream, views, num_src, min_region, parent, size, L, out);
+	return hipGetLastError() != hipSuccess;
+}
+
+int launch_clean(hipStream_t stream, Scratch& s, const uint32_t* views, int W, int H, int num_src, int min_region, uint32_t* out) {
+	const size_t L = (size_t)W * H;
+	if (launch_components(stream, s, views, W, H, num_src)) return 1;
+	hipLaunchKernelGGL(dvp_vc_resolve, dim3((unsigned)((L + 255) / 256)), dim3(256), 0, stream, views, num_src, min_region, s.words, s.words + (size_t)num_src * L, L, out);
 	return hipGetLastError() != hipSuccess;
 }
 

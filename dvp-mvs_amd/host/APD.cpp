@@ -27,6 +27,9 @@ bool APD::EdgesOnDevice() { return g_edges_on_device; }
 static bool g_cleanup_on_device = false;
 void APD::SetCleanupOnDevice(bool on) { g_cleanup_on_device = on; }
 bool APD::CleanupOnDevice() { return g_cleanup_on_device; }
+static bool g_labels_on_device = false;
+void APD::SetLabelsOnDevice(bool on) { g_labels_on_device = on; }
+bool APD::LabelsOnDevice() { return g_labels_on_device; }
 // DVP_HOST_TIMING=1: wall time of the parts of the host steps (tools/e2e_timing.sh folds them per pass)
 namespace {
 struct HostLap {

@@ -140,6 +140,12 @@ public:
 	// Connect loop.  Flows that do not stage maps on the device keep the host loop.  Same words either way.  Default false.
 	static void SetCleanupOnDevice(bool on);
 	static bool CleanupOnDevice();
+	// `apd --labels-on gpu`.  true: GetProblemEdges makes labels_<s>.dmb with a dvp_labels job on the driver's device
+	// (include/dvp_mvs.h: resizes, Roberts cross, both component passes and the numbering on the device, the Hough lines on the
+	// host in between) instead of the helper thread's LabelSegment — one job per calling thread, kept for the thread's life.
+	// Announcing, publishing, file names and SetUseLabelFiles are untouched.  Same values.  Default false.
+	static void SetLabelsOnDevice(bool on);
+	static bool LabelsOnDevice();
 	// true (default): a pass that starts from maps of another size (REFINE_INIT on a finer pyramid level) hands them to the
 	// engine at their own size and RescaleMatToTargetSize runs there (dvp_upload_state_rescaled); false: the five host-side
 	// rescales + the plane assembly of the reference's flow (APD.cpp:1176-1180, 1440-1456, 1656-1659).  Same maps either way.

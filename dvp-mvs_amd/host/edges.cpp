@@ -120,6 +120,24 @@ static int scale_level(const Problem& problem) {
 	while ((1 << scale) < problem.scale_size) scale++;
 	return scale;
 }
+// APD::SetLabelsOnDevice: LabelSegment's map from a dvp_labels job of the calling thread (a helper thread, or the driver's with
+// --sync-io), made at the first map and destroyed when the thread ends.  A failure is fatal: there is no quiet way back to the host
+static Mat DeviceLabelMap(const int scale, const Mat& image_uint) {
+	struct Holder {
+		dvp_labels* job = nullptr;
+		~Holder() { if (job) (void)dvp_labels_destroy(job); }
+	};
+	static thread_local Holder mine;
+	if (!mine.job && dvp_labels_create(APD::GetDevice(), &mine.job) != 0) DvpFatal(std::string("label map on the device: ") + dvp_labels_last_error());
+	int cols = 0, rows = 0;
+	if (dvp_labels_sizes(image_uint.cols, image_uint.rows, scale, nullptr, nullptr, &cols, &rows, nullptr) != 0) DvpFatal(std::string("label map on the device: ") + dvp_labels_last_error());
+	Mat label(rows, cols, CV_32S);
+	if (dvp_labels_run(mine.job, image_uint.data, image_uint.cols, image_uint.rows, (long long)image_uint.step, scale, label.ptr<int32_t>(0)) != 0)
+		DvpFatal(std::string("label map on the device: ") + dvp_labels_last_error());
+	std::cout << std::string("Label map: on the device\n") << std::flush;   // (one write: several helper threads log at once)
+	return label;
+}
+
 std::vector<path> ProblemEdgeOutputs(const Problem& problem) {
 	const int scale = scale_level(problem);
 	std::vector<path> out;
@@ -151,7 +169,7 @@ void GetProblemEdges(const Problem& problem, const std::vector<path>& outputs) {
 	if (need_label) {   // from the full-size image (main.cpp:236)
 		const Mat image_uint = APD::DecodedGray(problem.dense_folder / path("images") / path(ToFormatIndex(problem.ref_image_id) + ".jpg"));
 		if (image_uint.empty()) { publish_empty(); return; }
-		PublishResult(label_path, EdgeSegment(scale, image_uint, 1));
+		PublishResult(label_path, APD::LabelsOnDevice() ? DeviceLabelMap(scale, image_uint) : EdgeSegment(scale, image_uint, 1));
 		need_label = false;
 	}
 	if (!need_edge) return;

@@ -20,6 +20,8 @@
 #include "APD.h"
 #include <vector>
 
+#include "../csrc/dvp_labels_mid.hpp"   // the outlines, the Hough transform and the lines: one text with the engine library
+
 namespace {
 
 Mat to_float(const Mat& u8) {
@@ -63,110 +65,6 @@ Mat RobertsCross(const Mat& src) {
 	return dst;
 }
 
-// 8-connected line, both end points included, clipped to the image (cv::line, thickness 1)
-void draw_line(Mat& img, int x0, int y0, int x1, int y1, uint8_t value) {
-	const int dx = std::abs(x1 - x0), dy = std::abs(y1 - y0);
-	const int sx = x0 < x1 ? 1 : -1, sy = y0 < y1 ? 1 : -1;
-	int err = dx - dy;
-	for (;;) {
-		if (x0 >= 0 && x0 < img.cols && y0 >= 0 && y0 < img.rows) img.at<uint8_t>(y0, x0) = value;
-		if (x0 == x1 && y0 == y1) break;
-		const int e2 = 2 * err;
-		if (e2 > -dy) { err -= dy; x0 += sx; }
-		if (e2 < dx) { err += dx; y0 += sy; }
-	}
-}
-
-struct Segment { int x0, y0, x1, y1; };
-
-// Progressive probabilistic Hough transform (Matas, Galambos, Kittler) in the shape of cv::HoughLinesP:
-// rho = 1 px, theta = 1 degree.  Points are visited in random order; each votes for its 180 lines; when a
-// bin reaches `threshold` the line is walked from the point in both directions through the mask, gaps of
-// up to `max_gap` pixels are bridged, the walked points are removed (their votes withdrawn if the segment
-// is long enough) and a segment of at least `min_length` is reported.
-std::vector<Segment> HoughSegments(const Mat& image, int threshold, int min_length, int max_gap) {
-	const int width = image.cols, height = image.rows;
-	const int numangle = 180;
-	const int numrho = (int)std::lround(((width + height) * 2 + 1) / 1.0);
-	std::vector<int> accum((size_t)numangle * numrho, 0);
-	std::vector<uint8_t> mask((size_t)width * height, 0);
-	std::vector<float> trig((size_t)numangle * 2);
-	for (int n = 0; n < numangle; ++n) {
-		const double ang = n * (M_PI / 180.0);
-		trig[2 * n] = (float)std::cos(ang);
-		trig[2 * n + 1] = (float)std::sin(ang);
-	}
-	struct Pt { int x, y; };
-	std::vector<Pt> pts;
-	for (int y = 0; y < height; ++y)
-		for (int x = 0; x < width; ++x)
-			if (image.at<uint8_t>(y, x)) { mask[(size_t)y * width + x] = 1; pts.push_back(Pt{ x, y }); }
-	uint64_t state = (uint64_t)-1;   // cv::RNG((uint64)-1), multiply-with-carry
-	auto next_u32 = [&]() { state = (uint64_t)(uint32_t)state * 4164903690U + (uint32_t)(state >> 32); return (uint32_t)state; };
-	std::vector<Segment> out;
-	for (int count = (int)pts.size(); count > 0; --count) {
-		const int idx = (int)(next_u32() % (uint32_t)count);
-		const Pt point = pts[idx];
-		pts[idx] = pts[count - 1];
-		if (!mask[(size_t)point.y * width + point.x]) continue;   // already swallowed by an earlier segment
-		int max_val = threshold - 1, max_n = 0;
-		for (int n = 0; n < numangle; ++n) {
-			const int r = (int)std::lround(point.x * trig[2 * n] + point.y * trig[2 * n + 1]) + (numrho - 1) / 2;
-			const int val = ++accum[(size_t)n * numrho + r];
-			if (max_val < val) { max_val = val; max_n = n; }
-		}
-		if (max_val < threshold) continue;
-		// walk along the line: the major axis advances one pixel per step, the minor one in 16.16 fixed point
-		const int shift = 16;
-		const float a = -trig[2 * max_n + 1], b = trig[2 * max_n];
-		int x0 = point.x, y0 = point.y, dx0, dy0;
-		bool xflag;
-		if (std::fabs(a) > std::fabs(b)) {
-			xflag = true;
-			dx0 = a > 0 ? 1 : -1;
-			dy0 = (int)std::lround(b * (1 << shift) / std::fabs(a));
-			y0 = (y0 << shift) + (1 << (shift - 1));
-		} else {
-			xflag = false;
-			dy0 = b > 0 ? 1 : -1;
-			dx0 = (int)std::lround(a * (1 << shift) / std::fabs(b));
-			x0 = (x0 << shift) + (1 << (shift - 1));
-		}
-		Pt line_end[2] = { point, point };
-		for (int k = 0; k < 2; ++k) {
-			int gap = 0, x = x0, y = y0, dx = dx0, dy = dy0;
-			if (k > 0) { dx = -dx; dy = -dy; }
-			for (;; x += dx, y += dy) {
-				const int i1 = xflag ? x : x >> shift, j1 = xflag ? y >> shift : y;
-				if (i1 < 0 || i1 >= width || j1 < 0 || j1 >= height) break;
-				if (mask[(size_t)j1 * width + i1]) { gap = 0; line_end[k] = Pt{ i1, j1 }; }
-				else if (++gap > max_gap) break;
-			}
-		}
-		const bool good = std::abs(line_end[1].x - line_end[0].x) >= min_length || std::abs(line_end[1].y - line_end[0].y) >= min_length;
-		for (int k = 0; k < 2; ++k) {
-			int x = x0, y = y0, dx = dx0, dy = dy0;
-			if (k > 0) { dx = -dx; dy = -dy; }
-			for (;; x += dx, y += dy) {
-				const int i1 = xflag ? x : x >> shift, j1 = xflag ? y >> shift : y;
-				if (i1 < 0 || i1 >= width || j1 < 0 || j1 >= height) break;
-				uint8_t& m = mask[(size_t)j1 * width + i1];
-				if (m) {
-					if (good)
-						for (int n = 0; n < numangle; ++n) {
-							const int r = (int)std::lround(i1 * trig[2 * n] + j1 * trig[2 * n + 1]) + (numrho - 1) / 2;
-							--accum[(size_t)n * numrho + r];
-						}
-					m = 0;
-				}
-				if (i1 == line_end[k].x && j1 == line_end[k].y) break;
-			}
-		}
-		if (good) out.push_back(Segment{ line_end[0].x, line_end[0].y, line_end[1].x, line_end[1].y });
-	}
-	return out;
-}
-
 }  // namespace
 
 // EdgeSegment(scale, src_image, mode = 1, use_canny = false): CV_32SC1 label map at src size / 2^scale
@@ -184,22 +82,13 @@ Mat LabelSegment(const int scale, const Mat& src_image, LabelStages* stages) {
 		std::vector<int> region_size;
 		Connect(texture, region, region_size);
 		Label_Update(region, region_size);
-		Mat outline(texture.rows, texture.cols, CV_8UC1);
-		for (size_t k = 1; k < region_size.size(); ++k) {
-			if (region_size[k] < weak_tex_num) continue;
-			const int id = (int)k;
-			std::memset(outline.data, 0, outline.step * outline.rows);
-			for (int y = 0; y < outline.rows; ++y) {
-				const int* row = region.ptr<int>(y);
-				for (int x = 0; x < outline.cols; ++x) {
-					if (row[x] == id) continue;
-					const bool touches = (x > 0 && row[x - 1] == id) || (x + 1 < outline.cols && row[x + 1] == id) ||
-					                     (y > 0 && region.at<int>(y - 1, x) == id) || (y + 1 < outline.rows && region.at<int>(y + 1, x) == id);
-					if (touches) outline.at<uint8_t>(y, x) = 255;
-				}
-			}
-			for (const Segment& s : HoughSegments(outline, unit, unit, unit)) draw_line(texture, s.x0, s.y0, s.x1, s.y1, 255);
+		// the large regions by number, everything else -1: the outlines, the transform and the lines are dvp_labels_mid.hpp's
+		std::vector<int32_t> key((size_t)region.rows * region.cols);
+		for (int y = 0; y < region.rows; ++y) {
+			const int* row = region.ptr<int>(y);
+			for (int x = 0; x < region.cols; ++x) key[(size_t)y * region.cols + x] = (row[x] != 0 && region_size[row[x]] >= weak_tex_num) ? row[x] : -1;
 		}
+		dvplabmid::DrawRegionLines(key.data(), region.cols, region.rows, unit, [&](int x, int y) { texture.at<uint8_t>(y, x) = 255; });
 	}
 	if (stages) stages->texture_lines = texture.clone();
 	const float factor = 1.0f / (float)(1 << scale);

@@ -44,6 +44,7 @@ struct Options {
 	bool sync_io = false;
 	bool host_rescale = false;
 	bool edges_on_gpu = false;             // --edges-on gpu: the Canny edge prior is made by the engine from the resident image (APD::SetEdgesOnDevice)
+	bool labels_on_gpu = false;            // --labels-on gpu: GetProblemEdges makes the label maps with a dvp_labels job on the rank's device (APD::SetLabelsOnDevice)
 	bool cleanup_on_gpu = false;           // --cleanup-on gpu: the visibility-mask clean-up runs in the engine on the staged selected-view words (APD::SetCleanupOnDevice)
 	bool previews = false;                 // --previews: the reference's show_medium_result preview images (depth/normal/weak_<it>.jpg, weak.png, rawedge_<s>.jpg)
 	int views_in_flight = 0;               // --views-in-flight N: that many views of a pass at once (default 2) where the order allows it and the level is small; 1 = never
@@ -514,6 +515,11 @@ Options ParseOptions(int argc, char** argv) {
 			if (where != "host" && where != "gpu") { std::cerr << "--edges-on takes host or gpu\n"; std::exit(1); }
 			o.edges_on_gpu = where == "gpu";
 		}
+		else if (s == "--labels-on" && a + 1 < argc) {
+			const std::string where = argv[++a];
+			if (where != "host" && where != "gpu") { std::cerr << "--labels-on takes host or gpu\n"; std::exit(1); }
+			o.labels_on_gpu = where == "gpu";
+		}
 		else if (s == "--cleanup-on" && a + 1 < argc) {
 			const std::string where = argv[++a];
 			if (where != "host" && where != "gpu") { std::cerr << "--cleanup-on takes host or gpu\n"; std::exit(1); }
@@ -534,7 +540,7 @@ Options ParseOptions(int argc, char** argv) {
 
 int main(int argc, char** argv) {
 	if (argc < 2) {
-		std::cerr << "USAGE: apd dense_folder [gpu_index] [--previews] [--max-src N] [--iters N] [--min-scale S] [--passes P] [--seed X] [--rank R --world N [--job ID]] [--jacobi] [--no-fusion | --fusion KIND] [--fusion-on device|host] [--edges-on host|gpu] [--cleanup-on host|gpu] [--views-in-flight N]\n";
+		std::cerr << "USAGE: apd dense_folder [gpu_index] [--previews] [--max-src N] [--iters N] [--min-scale S] [--passes P] [--seed X] [--rank R --world N [--job ID]] [--jacobi] [--no-fusion | --fusion KIND] [--fusion-on device|host] [--edges-on host|gpu] [--labels-on host|gpu] [--cleanup-on host|gpu] [--views-in-flight N]\n";
 		return EXIT_FAILURE;
 	}
 	const Options opt = ParseOptions(argc, argv);
@@ -563,6 +569,7 @@ int main(int argc, char** argv) {
 	APD::SetUseLabelFiles(opt.label_files);
 	APD::SetEdgesOnDevice(opt.edges_on_gpu);
 	APD::SetCleanupOnDevice(opt.cleanup_on_gpu);
+	APD::SetLabelsOnDevice(opt.labels_on_gpu);
 	SetResultCache(!opt.sync_io);
 	APD::SetDeviceRescale(!opt.sync_io && !opt.host_rescale);
 	g_device_maps = !opt.sync_io && !opt.host_rescale;

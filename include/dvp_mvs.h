@@ -332,6 +332,40 @@ const char* dvp_viewclean_last_error(void);   /* the calling thread's last dvp_c
  * dvp_ctx_reserve bit 4 and freed with the context. */
 int dvp_set_view_cleanup(dvp_ctx* ctx, int enable, int num_src, int min_region);
 
+/* ---- the label prior (EdgeSegment(scale, image, mode 1), APD.cpp:348-401, 437-499) on the device ----------------------------------
+ * The low-texture segmentation whose result fills DVP_BUF_LABEL, from the FULL-size grey image whatever the level: two bilinear
+ * halvings (cv::resize through float, rounded to nearest even), Roberts cross with the reference's byte cast and threshold 4,
+ * 4-connected components of the flat pixels at quarter size; on the host, between the two device halves, the progressive
+ * probabilistic Hough transform over the outline of every region of at least weak_tex_num pixels and the lines it finds; then the
+ * resize to the level, the threshold again, the frame clean-up, components at level size numbered 1, 2, ... in raster order of
+ * their first pixels, 0 = textured, -1 = a region of at most weak_tex_num pixels.  Equal to the host mirror's LabelSegment value
+ * for value.  The number of launches does not depend on the image.
+ *   quarter size = (width / 2 / 2) x (height / 2 / 2)                        (integer divisions)
+ *   level size   = round(width * f) x round(height * f), float f = 1 / 2^scale  (halves away from zero)
+ *   weak_tex_num = (int)(1.0 * width * height / (1024 << scale << scale))
+ * dvp_labels_sizes returns them (NULL pointers are skipped).  scale outside 0 ... 10, a quarter or level map below 3 x 3,
+ * pitch_bytes < width, null pointers are errors with a message (dvp_labels_last_error). */
+typedef struct dvp_labels dvp_labels;
+int dvp_labels_sizes(int width, int height, int scale, int* quarter_cols, int* quarter_rows, int* level_cols, int* level_rows, int* weak_tex_num);
+/* A job: its own stream; device scratch that grows on demand and is kept for the next image (about 1.9 bytes per full-size pixel
+ * plus 22 per level pixel).  Two jobs may run at the same time from two threads; one job serves one thread at a time. */
+int dvp_labels_create(int device, dvp_labels** out);
+int dvp_labels_destroy(dvp_labels* job);
+/* grey: width x height bytes, `pitch_bytes` per row; label_out receives level cols x level rows int32.  Returns after the map
+ * has arrived: the call waits twice, for the region map the host middle reads and for the result. */
+int dvp_labels_run(dvp_labels* job, const uint8_t* grey, int width, int height, long long pitch_bytes, int scale, int32_t* label_out);
+/* After a run: an intermediate map of it.  QUARTER, TEXTURE, LINES: quarter-size bytes (the grey image; 255 = textured; the same
+ * with the lines drawn); REGION: quarter-size int32, the smallest pixel index of the pixel's flat region where that has at least
+ * weak_tex_num pixels, else -1; RESIZED, CLEANED: level-size bytes before and after the frame clean-up. */
+enum { DVP_LABEL_STAGE_QUARTER = 0, DVP_LABEL_STAGE_TEXTURE = 1, DVP_LABEL_STAGE_REGION = 2, DVP_LABEL_STAGE_LINES = 3, DVP_LABEL_STAGE_RESIZED = 4, DVP_LABEL_STAGE_CLEANED = 5 };
+int dvp_labels_stage(dvp_labels* job, int which, void* dst);
+/* After a run: ms[3] = wall time of the first device half (upload to region map), the host middle, the second device half;
+ * counts[2] = regions with an outline, outline points over all of them.  NULL pointers are skipped. */
+int dvp_labels_timings(const dvp_labels* job, double* ms, long long* counts);
+/* One-shot: create, run, destroy. */
+int dvp_label_map(int device, const uint8_t* grey, int width, int height, long long pitch_bytes, int scale, int32_t* label_out);
+const char* dvp_labels_last_error(void);   /* the calling thread's last dvp_labels_* / dvp_label_map error */
+
 #ifdef __cplusplus
 }
 #endif

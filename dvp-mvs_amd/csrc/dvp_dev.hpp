@@ -68,6 +68,14 @@ struct ViewConst {
 // The buffer bundle every kernel receives (the engine's DataPassHelper, APD.h:60-92).
 struct AnchorRec;   // dvp_weak_wave.hpp
 struct WeakRec;     // dvp_weak_phased.hpp
+// per-pixel plane cache of the split strong update (dvp_strong.hpp: strong_reuse_plan)
+struct alignas(16) PlaneKey { uint32_t w[4]; };   // a plane's four raw words
+struct alignas(16) ReuseHdr {
+	uint32_t valid;    // places whose key and vector are current
+	uint32_t radius;   // patch radius the vectors were computed with
+	uint32_t epoch;    // Dev::reuse_epoch at the time
+	uint32_t eval;     // slots the evaluation launch of this visit takes (hand-over from the plan launch)
+};
 struct Dev {
 	int width, height, num_images;
 	int pitch;                 // floats per padded image row (multiple of 64 -> 256 B aligned rows)
@@ -132,6 +140,12 @@ struct Dev {
 	// [slot][view][row * half_w + x / 2] (a red/black launch touches every second pixel of a row), or null
 	float* slot_costs;         // [half_w * H][17][S] (dvp_strong.hpp: slot_cost_index)
 	float* strong_rec;         // [SR_FIELDS][half_w * H]: hand-over from dvp_strong_decide to dvp_strong_refine
+	// the same cost vectors kept from one visit of a pixel to its next (dvp_strong.hpp: strong_reuse_plan), per pixel of the FULL
+	// image (black and red pixels keep their own records), or all null: the launches then use slot_costs exactly as before
+	float* reuse_costs;        // [L][17 places][S]: replaces slot_costs when set
+	PlaneKey* reuse_keys;      // [L][17 places]: the plane whose vector a place holds
+	ReuseHdr* reuse_hdr;       // [L]
+	uint32_t reuse_epoch;      // a record written under another epoch is empty (the engine bumps it whenever a vector's inputs can change)
 	// DepthToWeak + LocalRefine as view-compacted passes (dvp_strong.hpp: sweep_*), or null (the fused per-pixel kernel)
 	f4* sweep_rec;             // [2][L]: (camera-frame normal, depth) and (mean baseline, disparity, weight sum, flags) per pixel
 	float* sweep_cost;         // [L/64][S][kSweepFields][64] (sweep_cost_index): per (view, sweep slot, pixel) costs written by dvp_sweep_eval

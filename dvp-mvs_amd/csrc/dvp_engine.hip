@@ -184,11 +184,15 @@ __device__ __forceinline__ void strong_eval_items_body(const Dev& d, const Launc
 		int radius, inc;
 		patch_geometry(d, center, &radius, &inc);
 		build_patch_ctx(d, px, py, radius, inc, 0, c.tab, &c);
-		uint32_t w[3];
-		uniq = strong_slot_sources(d, center, w);
-		const size_t Lh = (size_t)d.half_w * (size_t)d.height;
-		uint32_t* dup = reinterpret_cast<uint32_t*>(d.strong_rec) + half_index(d, px, py);
-		dup[SR_DUP * Lh] = w[0]; dup[(SR_DUP + 1) * Lh] = w[1]; dup[(SR_DUP + 2) * Lh] = w[2];
+		if (d.reuse_hdr) uniq = d.reuse_hdr[center].eval;   // dvp_strong_plan has listed the slots and written their places
+		else {
+			uint32_t src[3], w[3];
+			uniq = strong_slot_sources(d, center, src);
+			strong_source_places(src, w);
+			const size_t Lh = (size_t)d.half_w * (size_t)d.height;
+			uint32_t* dup = reinterpret_cast<uint32_t*>(d.strong_rec) + half_index(d, px, py);
+			dup[SR_DUP * Lh] = w[0]; dup[(SR_DUP + 1) * Lh] = w[1]; dup[(SR_DUP + 2) * Lh] = w[2];
+		}
 	}
 	// Item order: pixel-major — all distinct slots of pixel 0, then pixel 1, ...; exclusive prefix sum of the lanes' item
 	// counts.  (Rank-major — the first distinct slot of every pixel, then the second, ... — keeps neighbouring pixels with the
@@ -727,6 +731,15 @@ extern "C" __global__ void __launch_bounds__(256) dvp_strong_search(const Dev d,
 		strong_search_px(d, px, py);
 }
 
+// plane-cache plan of the split strong update (strong_reuse_plan): which of the pixel's planes still have their vector from its
+// previous visit, and where every slot's vector lies.  Light like the search, so that the 256-VGPR evaluation kernel only reads the result.
+extern "C" __global__ void __launch_bounds__(256) dvp_strong_plan(const Dev d, const LaunchArgs a) {
+	int px, py;
+	if (block_to_pixel(blockIdx.x, threadIdx.x & 63, threadIdx.x >> 6, a.tiles_x, a.tiles, a.rows, a.half, a.colour, d.width, d.height, &px, &py) &&
+	    d.weak_info[px + py * d.width] != DVP_WEAK)
+		strong_plan_px(d, px, py);
+}
+
 // line-scan pre-pass of GenEdgeInform: nearest edge pixel in 8 directions (blockIdx.y = direction)
 extern "C" __global__ void __launch_bounds__(256) dvp_edge_rays(const Dev d, int what) {
 	edge_ray_line(d, blockIdx.y, blockIdx.x * blockDim.x + threadIdx.x, what);
@@ -1150,6 +1163,10 @@ struct dvp_ctx {
 	int* search_pos = nullptr;   // [16][L]
 	float* slot_costs = nullptr; // [17][S][half_w * H]: split strong update (allocated at its first launch)
 	float* strong_rec = nullptr; // [SR_FIELDS][half_w * H]
+	// plane cache of the split strong update (Dev::reuse_*), allocated with slot_costs' stand-in at the first launch
+	float* reuse_costs = nullptr; PlaneKey* reuse_keys = nullptr; ReuseHdr* reuse_hdr = nullptr;
+	bool strong_reuse = true;    // DVP_STRONG_REUSE=0, or the records did not fit: the per-launch half-size cost buffer
+	uint32_t reuse_epoch = 0;    // bump_reuse_epoch
 	bool strong_split = true;    // DVP_STRONG_SPLIT=0 in the environment: the monolithic kernel (A/B measurements)
 	bool eval_items = true;      // DVP_EVAL_ITEMS=0: dvp_strong_eval with a pixel per lane instead of (pixel, slot) items over the lanes
 	bool refine_lanes = true;    // DVP_REFINE_LANES=0: dvp_strong_refine with the wave in lock step over hypotheses and views
@@ -1264,6 +1281,17 @@ static void dfree(dvp_ctx* c, T** p) {
 	*p = nullptr;
 }
 
+// The plane cache's records (Dev::reuse_*) hold cost vectors from one strong update of a pass to the next.  A vector depends on
+// the images, the cameras, the parameters, the sampler and the radius map (the header checks the pixel's own radius): every call
+// that can change one of them, and the start of every dvp_run_patchmatch, makes all records empty by moving on to a new epoch.
+static void bump_reuse_epoch(dvp_ctx* c) {
+	if (++c->reuse_epoch == 0) {   // wrapped: headers of 2^32 epochs ago must not match
+		if (c->reuse_hdr) (void)hipMemsetAsync(c->reuse_hdr, 0, c->L * sizeof(ReuseHdr), c->stream);
+		c->reuse_epoch = 1;
+	}
+	c->d.reuse_epoch = c->reuse_epoch;
+}
+
 static size_t img16_plane_bytes(int W, int H) { return (size_t)img16_tiles_x(W) * img16_tiles_y(H) * 128; }
 
 static void sync_dev_struct(dvp_ctx* c) {
@@ -1277,6 +1305,7 @@ static void sync_dev_struct(dvp_ctx* c) {
 	d.search_pos = c->search_pos;
 	d.sweep_px0 = 0; d.sweep_row0 = 0; d.sweep_row1 = 0;   // (set per band by the sweep passes' launches)
 	d.sweep_rec = c->sweep_rec; d.sweep_cost = c->sweep_cost; d.sweep_pc = c->sweep_pc; d.slot_costs = c->slot_costs; d.strong_rec = c->strong_rec; d.half_w = (c->W + 1) / 2;
+	d.reuse_costs = c->reuse_costs; d.reuse_keys = c->reuse_keys; d.reuse_hdr = c->reuse_hdr; d.reuse_epoch = c->reuse_epoch;
 	d.planes = c->planes; d.planes_snap = c->planes_snap; d.costs = c->costs; d.costs_snap = c->costs_snap;
 	d.selected_views = c->selected_views; d.view_weight = c->view_weight; d.weak_info = c->weak_info;
 	d.weak_reliable = c->weak_reliable; d.weak_nearest_strong = c->weak_nearest_strong;
@@ -1320,6 +1349,8 @@ int dvp_ctx_create(int device, int width, int height, int num_images, dvp_ctx** 
 	c->no_images8 = getenv("DVP_NO_IMAGES8") != nullptr;
 	c->no_images16 = getenv("DVP_NO_IMAGES16") != nullptr;
 	if (const char* e = getenv("DVP_STRONG_SPLIT")) c->strong_split = atoi(e) != 0;
+	if (const char* e = getenv("DVP_STRONG_REUSE")) c->strong_reuse = atoi(e) != 0;
+	bump_reuse_epoch(c);
 	if (const char* e = getenv("DVP_REFINE_LANES")) c->refine_lanes = atoi(e) != 0;
 	if (const char* e = getenv("DVP_EVAL_ITEMS")) c->eval_items = atoi(e) != 0;
 	if (const char* e = getenv("DVP_SWEEP_SPLIT")) { c->sweep_split = atoi(e) != 0; c->sweep_force = atoi(e) == 2; }
@@ -1502,12 +1533,14 @@ static int upload_planes(dvp_ctx* c, float* dst, const float* const* src, int pi
 }
 int dvp_upload_images(dvp_ctx* c, const float* const* images, int pitch_floats) {
 	c->anchor_tab_valid = false;
+	bump_reuse_epoch(c);
 	if (upload_planes(c, c->image_stage, images, pitch_floats, hipMemcpyHostToDevice, c->images)) return 1;
 	c->have_images = true;
 	return 0;
 }
 int dvp_upload_images_device(dvp_ctx* c, const float* const* images, int pitch_floats) {
 	c->anchor_tab_valid = false;
+	bump_reuse_epoch(c);
 	if (upload_planes(c, c->image_stage, images, pitch_floats, hipMemcpyDeviceToDevice, c->images)) return 1;
 	c->have_images = true;
 	return 0;
@@ -1530,6 +1563,7 @@ int dvp_upload_depths_device(dvp_ctx* c, const float* const* depths, int pitch_f
 }
 
 int dvp_upload_cameras(dvp_ctx* c, const DvpCamera* cams, int n) {
+	bump_reuse_epoch(c);
 	if (set_device(c)) return 1;
 	if (n != c->NI) { c->error = "dvp_upload_cameras: n != num_images"; return 1; }
 	HIP_TRY(c, hipMemcpyAsync(c->cameras, cams, sizeof(DvpCamera) * n, hipMemcpyHostToDevice, c->stream));
@@ -1609,6 +1643,7 @@ static int rebuild_weak_lists(dvp_ctx* c) {
 int dvp_upload_state(dvp_ctx* c, const float* planes, const uint32_t* views, const uint8_t* weak,
                      const uint8_t* edge, const int32_t* label, const int32_t* radius) {
 	c->anchor_tab_valid = false;
+	bump_reuse_epoch(c);
 	if (set_device(c)) return 1;
 	const size_t L = c->L;
 	if (planes) HIP_TRY(c, hipMemcpyAsync(c->planes, planes, L * 16, hipMemcpyHostToDevice, c->stream));
@@ -1626,6 +1661,7 @@ int dvp_upload_state(dvp_ctx* c, const float* planes, const uint32_t* views, con
 int dvp_upload_state_rescaled(dvp_ctx* c, int src_w, int src_h, const float* depth, const float* normal_xyz, const uint32_t* views,
                               const uint8_t* weak, const int32_t* radius, int radius_fallback, const uint8_t* edge, const int32_t* label) {
 	c->anchor_tab_valid = false;
+	bump_reuse_epoch(c);
 	if (set_device(c)) return 1;
 	if (src_w <= 0 || src_h <= 0 || !depth || !normal_xyz || !views) { c->error = "dvp_upload_state_rescaled: depth, normal and selected_views are required"; return 1; }
 	const size_t L = c->L, n = (size_t)src_w * src_h;
@@ -1660,6 +1696,7 @@ int dvp_upload_state_rescaled(dvp_ctx* c, int src_w, int src_h, const float* dep
 
 int dvp_reset_state(dvp_ctx* c) {
 	c->anchor_tab_valid = false;
+	bump_reuse_epoch(c);
 	if (set_device(c)) return 1;
 	const size_t L = c->L;
 	HIP_TRY(c, hipMemsetAsync(c->planes, 0, L * 16, c->stream));
@@ -1701,6 +1738,7 @@ int dvp_save_state(dvp_ctx* c) {
 }
 int dvp_restore_state(dvp_ctx* c) {
 	c->anchor_tab_valid = false;
+	bump_reuse_epoch(c);
 	if (set_device(c)) return 1;
 	if (!c->have_saved) { c->error = "dvp_restore_state: no saved state"; return 1; }
 	const size_t L = c->L;
@@ -1718,6 +1756,7 @@ int dvp_restore_state(dvp_ctx* c) {
 
 int dvp_set_params(dvp_ctx* c, const DvpParams* p) {
 	c->anchor_tab_valid = false;
+	bump_reuse_epoch(c);
 	if (set_device(c)) return 1;
 	if (p->num_images != c->NI) { c->error = "dvp_set_params: params.num_images != context num_images"; return 1; }
 	if (p->use_edge == 0) { c->error = "dvp_set_params: use_edge=false is rejected: the reference's legacy ACMH branch (APD.cu:2142-2460) adopts planes through positions[], which only the use_edge branch assigns (APD.cu:2036, 2084, 2133 vs 2559-2563) - it has no defined result to reproduce"; return 1; }
@@ -1737,7 +1776,7 @@ int dvp_set_params(dvp_ctx* c, const DvpParams* p) {
 	return 0;
 }
 int dvp_set_seed(dvp_ctx* c, uint64_t seed) { c->d.seed = seed; return 0; }
-int dvp_set_sampler(dvp_ctx* c, int s) { c->d.sampler = s ? 1 : 0; return 0; }
+int dvp_set_sampler(dvp_ctx* c, int s) { c->d.sampler = s ? 1 : 0; bump_reuse_epoch(c); return 0; }
 int dvp_set_profiling(dvp_ctx* c, int on) { c->profiling = on != 0; sync_dev_struct(c); return 0; }
 
 // ---- launches ---------------------------------------------------------------------------------
@@ -1830,8 +1869,13 @@ static int grow_weak_phase_buffers(dvp_ctx* c, size_t wc) {
 // The optional buffers of the split strong update and of the view-compacted sweep passes: allocated at the first launch that
 // wants them — or ahead of it by dvp_ctx_reserve, off the critical path (a multi-GB hipMalloc inside a launch site took 0.5-1 s
 // of a view on some boxes: profiles/r06_ab_notes.txt).  A context that cannot have them keeps the monolithic / fused kernels.
+static void ensure_strong_reuse_buffers(dvp_ctx* c);
 static void ensure_strong_split_buffers(dvp_ctx* c) {
 	if (c->slot_costs || !c->strong_split || c->NI - 1 > 16) return;
+	if (!getenv("DVP_TEST_SPLIT_ALLOC_FAIL")) {
+		ensure_strong_reuse_buffers(c);
+		if (c->reuse_costs) return;   // the full-size records stand in for slot_costs
+	}
 	// 17 x S floats per pixel of one colour (7.8 GB at 6208x4128, S = 9): a part that cannot spare them runs the
 	// monolithic kernel instead, which gives the same bits (test_strong_update_forms_equal_the_oracle)
 	const size_t Lh = (size_t)((c->W + 1) / 2) * c->H;
@@ -1844,6 +1888,29 @@ static void ensure_strong_split_buffers(dvp_ctx* c) {
 	} else {
 		c->allocs.push_back(sc); c->allocs.push_back(sr);
 		c->slot_costs = (decltype(c->slot_costs))sc; c->strong_rec = (decltype(c->strong_rec))sr;
+		sync_dev_struct(c);
+	}
+}
+// The plane cache's records: 17 x S floats + 17 keys + a header per pixel of the whole image (15.7 + 7.0 + 0.4 GB at 6208x4128,
+// S = 9), in place of the half-size slot_costs (7.8 GB), which such a context never allocates.  A context that cannot have them
+// keeps slot_costs and evaluates every distinct plane at every visit.
+static void ensure_strong_reuse_buffers(dvp_ctx* c) {
+	if (c->reuse_costs || !c->strong_reuse || !c->strong_split || c->NI - 1 > 16) return;
+	const size_t L = c->L, vec = (size_t)kSlotCount * (c->NI - 1) * L * sizeof(float) + 64 /* load_slot_costs reads whole 16-byte pieces */;
+	void *rc = nullptr, *rk = nullptr, *rh = nullptr, *sr = nullptr;
+	const size_t Lh = (size_t)((c->W + 1) / 2) * c->H;
+	const bool need_rec = !c->strong_rec;
+	if (getenv("DVP_TEST_REUSE_ALLOC_FAIL") /* test hook: take the fallback */ || hipMalloc(&rc, vec) != hipSuccess || hipMalloc(&rk, L * kSlotCount * sizeof(PlaneKey)) != hipSuccess ||
+	    hipMalloc(&rh, L * sizeof(ReuseHdr)) != hipSuccess || (need_rec && hipMalloc(&sr, (size_t)SR_FIELDS * Lh * sizeof(*c->strong_rec)) != hipSuccess) ||
+	    hipMemsetAsync(rh, 0, L * sizeof(ReuseHdr), c->stream) != hipSuccess) {
+		(void)hipGetLastError();
+		for (void* q : { rc, rk, rh, sr }) if (q) (void)hipFree(q);
+		c->strong_reuse = false;
+		fprintf(stderr, "dvp: no room for the strong update's plane cache (%.1f GB); every visit evaluates all its planes\n", (double)(vec + L * (kSlotCount * sizeof(PlaneKey) + sizeof(ReuseHdr))) / 1e9);
+	} else {
+		for (void* q : { rc, rk, rh }) c->allocs.push_back(q);
+		c->reuse_costs = (float*)rc; c->reuse_keys = (PlaneKey*)rk; c->reuse_hdr = (ReuseHdr*)rh;
+		if (need_rec) { c->allocs.push_back(sr); c->strong_rec = (decltype(c->strong_rec))sr; }
 		sync_dev_struct(c);
 	}
 }
@@ -1901,7 +1968,9 @@ static int launch_stage(dvp_ctx* c, int stage, int iter, int colour, bool fused 
 		HIP_TRY(c, hipEventRecord(prep.a, c->stream));
 		HIP_TRY(c, hipMemcpyAsync(c->planes_snap, c->planes, c->L * 16, hipMemcpyDeviceToDevice, c->stream));
 		HIP_TRY(c, hipMemcpyAsync(c->costs_snap, c->costs, c->L * 4, hipMemcpyDeviceToDevice, c->stream));
+		if (c->strong_split && c->NI - 1 <= 16) ensure_strong_split_buffers(c);   // (before the first launch that takes c->d)
 		hipLaunchKernelGGL(dvp_strong_search, dim3(g.grid()), dim3(256), 0, c->stream, c->d, a);
+		if (c->strong_split && c->NI - 1 <= 16 && c->d.reuse_hdr) hipLaunchKernelGGL(dvp_strong_plan, dim3(g.grid()), dim3(256), 0, c->stream, c->d, a);
 		HIP_TRY(c, hipGetLastError());
 		HIP_TRY(c, hipEventRecord(prep.b, c->stream));
 		c->events.push_back(prep);
@@ -2148,6 +2217,7 @@ int dvp_synchronize(dvp_ctx* c) {
 // APD::RunPatchMatch (APD.cu:4406-4532): same launch order; no host sync between launches.
 int dvp_run_patchmatch(dvp_ctx* c) {
 	c->anchor_tab_valid = false;
+	bump_reuse_epoch(c);
 	if (set_device(c)) return 1;
 	EventPair tot, itl;
 	tot.stage = EV_TOTAL; itl.stage = EV_ITER_LOOP;
@@ -2527,6 +2597,7 @@ int dvp_download_buffer(dvp_ctx* c, int id, void* dst) {
 }
 int dvp_upload_buffer(dvp_ctx* c, int id, const void* src) {
 	c->anchor_tab_valid = false;
+	bump_reuse_epoch(c);
 	if (set_device(c)) return 1;
 	size_t b; void* p = buffer_ptr(c, id, &b);
 	if (!p) { c->error = "bad or unallocated buffer id"; return 1; }

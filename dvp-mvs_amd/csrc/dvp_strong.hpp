@@ -566,7 +566,7 @@ DVP_HD void strong_update_px(const Dev& d, int px, int py, PatchTab tab, int ite
 // strong_update_px stays the definition (host emulation, S > 16, dvp_run_stage A/B with DVP_STRONG_SPLIT=0).
 constexpr int kSlotCur = 16;                 // slot_costs slot of the pixel's current plane
 constexpr int kSlotCount = 17;
-enum { SR_PLANE = 0, SR_DEPTH = 4, SR_COST = 5, SR_CENTER = 6, SR_DRAND = 7, SR_DPERT = 8, SR_NRAND = 9, SR_DUP = 12 /* 3 words: strong_slot_sources */, SR_FIELDS = 15 };
+enum { SR_PLANE = 0, SR_DEPTH = 4, SR_COST = 5, SR_CENTER = 6, SR_DRAND = 7, SR_DPERT = 8, SR_NRAND = 9, SR_DUP = 12 /* 3 words: the place of every slot's vector, 5 bits each (strong_slot_place_of) */, SR_FIELDS = 15 };
 DVP_HD size_t half_index(const Dev& d, int px, int py) { return (size_t)py * d.half_w + (size_t)(px >> 1); }
 // Layout of Dev::slot_costs.  Round 6: [pixel of the colour][slot][view] — a pixel's 17 x S costs are one contiguous record.
 // The evaluation launch's lanes are (pixel, slot) items, pixel-major: neighbouring lanes now write neighbouring 4 S-byte
@@ -619,16 +619,20 @@ DVP_HD SlotCostView slot_cost_view(const Dev& d, int px, int py) {
 DVP_HD bool same_plane_bits(const f4 a, const f4 b) {
 	return f32_bits(a.x) == f32_bits(b.x) && f32_bits(a.y) == f32_bits(b.y) && f32_bits(a.z) == f32_bits(b.z) && f32_bits(a.w) == f32_bits(b.w);
 }
-DVP_HD uint32_t strong_slot_sources(const Dev& d, int center, uint32_t w[3]) {
+// the 17 planes of a pixel's slots (a missing slot: zeros, bit clear in the returned mask)
+DVP_HD uint32_t strong_slot_planes(const Dev& d, int center, f4 pl[kSlotCount]) {
 	const size_t L = (size_t)d.width * d.height;
-	f4 pl[kSlotCount];
-	uint32_t have = 0, uniq = 0;
+	uint32_t have = 0;
 #pragma unroll
 	for (int slot = 0; slot < kSlotCount; ++slot) {
 		const int pos = slot < 16 ? d.search_pos[(size_t)slot * L + center] : center;
 		pl[slot] = mk4(0.0f, 0.0f, 0.0f, 0.0f);
 		if (pos >= 0) { pl[slot] = d.planes_snap[pos]; have |= 1u << slot; }
 	}
+	return have;
+}
+DVP_HD uint32_t strong_slot_sources_of(const f4 pl[kSlotCount], uint32_t have, uint32_t w[3]) {
+	uint32_t uniq = 0;
 	w[0] = w[1] = w[2] = 0;
 #pragma unroll
 	for (int slot = 0; slot < kSlotCount; ++slot) {
@@ -644,8 +648,97 @@ DVP_HD uint32_t strong_slot_sources(const Dev& d, int center, uint32_t w[3]) {
 	}
 	return uniq;
 }
+DVP_HD uint32_t strong_slot_sources(const Dev& d, int center, uint32_t w[3]) {
+	f4 pl[kSlotCount];
+	const uint32_t have = strong_slot_planes(d, center, pl);
+	return strong_slot_sources_of(pl, have, w);
+}
 DVP_HD int strong_slot_source(uint32_t w0, uint32_t w1, uint32_t w2, int slot) {
 	return slot < 8 ? (int)((w0 >> (4 * slot)) & 15u) : slot < 16 ? (int)((w1 >> (4 * (slot - 8))) & 15u) : (int)w2;
+}
+// Round 8: the vector of a (pixel, plane) pair does not change inside the iteration loop either — it depends on the images,
+// the cameras, the parameters, the sampler and the pixel's patch radius — and after the first iteration most neighbours still
+// carry the plane they had at the pixel's previous visit.  With Dev::reuse_* set, every pixel of the FULL image keeps a record:
+// 17 PLACES of S costs (reuse_costs), the plane of each place as raw bits (reuse_keys) and a header (valid places, radius,
+// epoch).  The plan launch (dvp_strong_plan, next to the sample search) looks every distinct plane of the visit up among the
+// valid keys, bitwise like same_plane_bits (-0 != +0, NaNs by payload).  A hit keeps its place and is not evaluated; a miss
+// takes the lowest place no hit holds (17 places, at most 17 distinct planes: there always is one) and is evaluated into it.
+// A record of another epoch or radius is empty.  Places no plane of this visit uses are dropped.
+// The three SR_DUP words then carry the PLACE of every slot, 5 bits each, six slots per word.
+constexpr uint32_t kPlaceMask = (1u << kSlotCount) - 1u;
+DVP_HD int strong_slot_place_of(uint32_t w0, uint32_t w1, uint32_t w2, int slot) {
+	return slot < 6 ? (int)((w0 >> (5 * slot)) & 31u) : slot < 12 ? (int)((w1 >> (5 * (slot - 6))) & 31u) : (int)((w2 >> (5 * (slot - 12))) & 31u);
+}
+// without the cache a slot's vector lies at the fixed place of its source slot (slot_place): the same words
+DVP_HD void strong_source_places(const uint32_t src[3], uint32_t place_w[3]) {
+	place_w[0] = place_w[1] = place_w[2] = 0;
+#pragma unroll
+	for (int s = 0; s < kSlotCount; ++s)
+		place_w[s / 6] |= (uint32_t)slot_place(strong_slot_source(src[0], src[1], src[2], s)) << (5 * (s % 6));
+}
+DVP_HD PlaneKey plane_key(const f4 p) {
+	PlaneKey k;
+	k.w[0] = f32_bits(p.x); k.w[1] = f32_bits(p.y); k.w[2] = f32_bits(p.z); k.w[3] = f32_bits(p.w);
+	return k;
+}
+// pl / have: strong_slot_planes; uniq / src: strong_slot_sources_of; keys: the pixel's 17 keys (read where the header says
+// valid, written where a miss lands); hdr: read and rewritten.  Returns the slots to evaluate (also left in hdr->eval).
+DVP_HD uint32_t strong_reuse_plan(const f4 pl[kSlotCount], uint32_t uniq, const uint32_t src[3], PlaneKey* keys, ReuseHdr* hdr,
+                                  uint32_t epoch, int radius, uint32_t place_w[3]) {
+	const ReuseHdr h = *hdr;
+	const uint32_t valid = (h.epoch == epoch && h.radius == (uint32_t)radius) ? (h.valid & kPlaceMask) : 0u;
+	int place[kSlotCount];
+#pragma unroll
+	for (int s = 0; s < kSlotCount; ++s) place[s] = -1;
+	uint32_t held = 0;
+	if (valid) {
+#pragma unroll
+		for (int p = 0; p < kSlotCount; ++p) {
+			if (!((valid >> p) & 1u)) continue;
+			const PlaneKey k = keys[p];
+#pragma unroll
+			for (int s = 0; s < kSlotCount; ++s) {
+				if (!((uniq >> s) & 1u) || place[s] >= 0) continue;
+				if (k.w[0] == f32_bits(pl[s].x) && k.w[1] == f32_bits(pl[s].y) && k.w[2] == f32_bits(pl[s].z) && k.w[3] == f32_bits(pl[s].w)) { place[s] = p; held |= 1u << p; }
+			}
+		}
+	}
+	uint32_t free_places = kPlaceMask & ~held, eval = 0;
+#pragma unroll
+	for (int s = 0; s < kSlotCount; ++s) {
+		if (!((uniq >> s) & 1u) || place[s] >= 0) continue;
+		const int p = dvp_ctz(free_places);
+		free_places &= free_places - 1;
+		place[s] = p;
+		eval |= 1u << s;
+		keys[p] = plane_key(pl[s]);
+	}
+	place_w[0] = place_w[1] = place_w[2] = 0;
+#pragma unroll
+	for (int s = 0; s < kSlotCount; ++s) {
+		const int from = strong_slot_source(src[0], src[1], src[2], s);   // (a missing slot: 0; nobody reads its place)
+		int p = 0;
+#pragma unroll
+		for (int u = 0; u <= s; ++u)
+			if (u == from && place[u] >= 0) p = place[u];
+		place_w[s / 6] |= (uint32_t)p << (5 * (s % 6));
+	}
+	ReuseHdr o;
+	o.valid = kPlaceMask & ~free_places; o.radius = (uint32_t)radius; o.epoch = epoch; o.eval = eval;
+	*hdr = o;
+	return eval;
+}
+// the plan launch's lane: one non-WEAK pixel of the launch's colour
+DVP_HD void strong_plan_px(const Dev& d, int px, int py) {
+	const int center = py * d.width + px;
+	f4 pl[kSlotCount];
+	const uint32_t have = strong_slot_planes(d, center, pl);
+	uint32_t src[3], pw[3];
+	const uint32_t uniq = strong_slot_sources_of(pl, have, src);
+	strong_reuse_plan(pl, uniq, src, d.reuse_keys + (size_t)center * kSlotCount, d.reuse_hdr + center, d.reuse_epoch, d.radius[center], pw);
+	const size_t Lh = (size_t)d.half_w * (size_t)d.height;
+	uint32_t* dup = reinterpret_cast<uint32_t*>(d.strong_rec) + half_index(d, px, py);
+	dup[SR_DUP * Lh] = pw[0]; dup[(SR_DUP + 1) * Lh] = pw[1]; dup[(SR_DUP + 2) * Lh] = pw[2];
 }
 // one (pixel, slot) item: the slot's plane against all S views -> slot_costs
 template <int SMP>
@@ -656,9 +749,25 @@ DVP_HD void strong_eval_item(const Dev& d, const PatchCtx& c, int px, int py, in
 	const size_t L = (size_t)W * d.height;
 	const int pos = slot < 16 ? d.search_pos[(size_t)slot * L + center] : center;
 	const f4 plane = d.planes_snap[pos];
+	// one loop for both record forms (a second inlined copy of the evaluator would cost the kernel its registers): `rec` = the
+	// pixel's record, `at` = the vector's position in it — with the plane cache the slot's place in the pixel's own full-size record
+	const bool reuse = d.reuse_costs != nullptr;
+	float* const buf = reuse ? d.reuse_costs : d.slot_costs;
+	int at = slot_place(slot);
+	if (reuse) {
+		const size_t Lh = (size_t)d.half_w * (size_t)d.height;
+		const int word = (slot >= 6) + (slot >= 12);
+		const uint32_t pw = reinterpret_cast<const uint32_t*>(d.strong_rec)[(size_t)(SR_DUP + word) * Lh + half_index(d, px, py)];
+		at = (int)((pw >> (5 * (slot - 6 * word))) & 31u);
+	}
 	for (int v = 0; v < S; ++v) {
 		const float cost = ncc_old<SMP>(d, c, px, py, v + 1, plane);
-		if (store) DVP_NT_STORE(4, &d.slot_costs[slot_cost_index(d, slot, v, px, py)], cost);
+#if DVP_SLOT_LAYOUT
+		const size_t rec = reuse ? (size_t)center : half_index(d, px, py);
+		if (store) DVP_NT_STORE(4, &buf[(rec * kSlotCount + (size_t)at) * (size_t)S + (size_t)v], cost);
+#else
+		if (store) DVP_NT_STORE(4, &buf[reuse ? ((size_t)center * kSlotCount + (size_t)at) * (size_t)S + (size_t)v : slot_cost_index(d, slot, v, px, py)], cost);
+#endif
 	}
 	if (nevals && store) *nevals += (unsigned long long)S;
 }
@@ -674,11 +783,16 @@ DVP_HD void strong_eval_px(const Dev& d, int px, int py, PatchTab tab, unsigned 
 		patch_geometry(d, center, &radius, &inc);
 		build_patch_ctx(d, px, py, radius, inc, 0, tab, &c);
 	}
-	uint32_t w[3];
-	const uint32_t uniq = strong_slot_sources(d, center, w);
-	const size_t Lh = (size_t)d.half_w * (size_t)d.height, hi = half_index(d, px, py);
-	uint32_t* dup = reinterpret_cast<uint32_t*>(d.strong_rec) + hi;
-	dup[SR_DUP * Lh] = w[0]; dup[(SR_DUP + 1) * Lh] = w[1]; dup[(SR_DUP + 2) * Lh] = w[2];
+	uint32_t uniq;
+	if (d.reuse_hdr) uniq = d.reuse_hdr[center].eval;   // the plan launch has listed the slots and written their places
+	else {
+		uint32_t src[3], w[3];
+		uniq = strong_slot_sources(d, center, src);
+		strong_source_places(src, w);
+		const size_t Lh = (size_t)d.half_w * (size_t)d.height, hi = half_index(d, px, py);
+		uint32_t* dup = reinterpret_cast<uint32_t*>(d.strong_rec) + hi;
+		dup[SR_DUP * Lh] = w[0]; dup[(SR_DUP + 1) * Lh] = w[1]; dup[(SR_DUP + 2) * Lh] = w[2];
+	}
 	for (uint32_t m = uniq; m; m &= m - 1) strong_eval_item<SMP>(d, c, px, py, dvp_ctz(m), true, nevals);
 }
 
@@ -704,12 +818,17 @@ DVP_HD void load_slot_costs(const float* sc, size_t view_stride, int S, float* o
 // statement, with the cost vectors in registers (all loops over directions / views are unrolled; MV >= S).
 template <int MV>
 DVP_HD void strong_decide_px(const Dev& d, int px, int py, int iter) {
-	const SlotCostView cv = slot_cost_view(d, px, py);
 	const int W = d.width;
 	const int center = py * W + px;
 	const DvpParams& P = d.params;
 	const DvpCamera rc = load_camera(d, 0);
 	const int S = P.num_images - 1;
+	// with the plane cache the vectors lie in the pixel's full-size record (strong_reuse_plan), else in the launch's half-size one;
+	// either way the SR_DUP words give every slot's place in the record
+	const bool reuse = d.reuse_costs != nullptr;
+	SlotCostView cv;
+	if (reuse) { cv.base = d.reuse_costs + (size_t)center * kSlotCount * (size_t)S; cv.slot_stride = (size_t)S; cv.view_stride = 1; }
+	else cv = slot_cost_view(d, px, py);
 	const size_t L = (size_t)W * d.height;
 	const size_t Lh = (size_t)d.half_w * (size_t)d.height, hi = half_index(d, px, py);
 	const float good_thr = 0.8f * dvp_expf((iter) * (iter) / (-90.0f));
@@ -717,7 +836,7 @@ DVP_HD void strong_decide_px(const Dev& d, int px, int py, int iter) {
 	float ca[8][MV];
 	uint32_t flag = 0;
 	int positions[8];
-	// which slot's vector serves a slot (strong_slot_sources, written by the evaluation launch)
+	// the place of every slot's vector (strong_source_places, written by the evaluation launch, or strong_reuse_plan's)
 	const uint32_t* dup = reinterpret_cast<const uint32_t*>(d.strong_rec) + hi;
 	const uint32_t dw0 = dup[SR_DUP * Lh], dw1 = dup[(SR_DUP + 1) * Lh], dw2 = dup[(SR_DUP + 2) * Lh];
 #pragma unroll
@@ -736,7 +855,7 @@ DVP_HD void strong_decide_px(const Dev& d, int px, int py, int iter) {
 			if (pos >= 0) {
 				flag |= 1u << k;
 				positions[k] = pos;
-				load_slot_costs<MV>(cv.base + (size_t)slot_place(strong_slot_source(dw0, dw1, dw2, k)) * cv.slot_stride, cv.view_stride, S, ca[k]);
+				load_slot_costs<MV>(cv.base + (size_t)strong_slot_place_of(dw0, dw1, dw2, k) * cv.slot_stride, cv.view_stride, S, ca[k]);
 			}
 		}
 		// slot 8 + k: the fixed-stride sample replaces the adaptive one if it is better
@@ -746,7 +865,7 @@ DVP_HD void strong_decide_px(const Dev& d, int px, int py, int iter) {
 			flag |= 1u << k;
 			float cb[MV];
 			int good0 = 0, good1 = 0, bad0 = 0, bad1 = 0;
-			load_slot_costs<MV>(cv.base + (size_t)slot_place(strong_slot_source(dw0, dw1, dw2, 8 + k)) * cv.slot_stride, cv.view_stride, S, cb);
+			load_slot_costs<MV>(cv.base + (size_t)strong_slot_place_of(dw0, dw1, dw2, 8 + k) * cv.slot_stride, cv.view_stride, S, cb);
 #pragma unroll
 			for (int j = 0; j < MV; ++j) {
 				if (j < S) {
@@ -862,7 +981,7 @@ DVP_HD void strong_decide_px(const Dev& d, int px, int py, int iter) {
 	float cn = 0.0f;
 #pragma unroll
 	for (int v = 0; v < MV; ++v)
-		if (v < S && vw[v] > 0) cn += vw[v] * cv.base[(size_t)slot_place((int)dw2) * cv.slot_stride + (size_t)v * cv.view_stride];
+		if (v < S && vw[v] > 0) cn += vw[v] * cv.base[(size_t)strong_slot_place_of(dw0, dw1, dw2, kSlotCur) * cv.slot_stride + (size_t)v * cv.view_stride];
 	float cost_now = cn / weight_norm;
 	const float costs_center = cost_now;
 	f4 plane_now = d.planes_snap[center];

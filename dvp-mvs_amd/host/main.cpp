@@ -558,6 +558,10 @@ int main(int argc, char** argv) {
 	// per view in drained launches, 5 bands 20): a full-size context is 64 GB instead of 107.  Measured neutral on the ten-view
 	// schedule (32.8 s either way).  DVP_SWEEP_BAND_GB in the environment wins; 0 = whole image.
 	setenv("DVP_SWEEP_BAND_GB", "24", 0);
+	// The strong update's plane cache (DVP_STRONG_REUSE) costs a full-size context 15.3 GB more (23.1 GB of records in place of the
+	// 7.8 GB cost buffer): 4 contexts in flight are then 317 GB, more than the part has, and the contexts made last would lose
+	// buffers they need more.  Off here unless the environment says otherwise (a driver with fewer views in flight may turn it on).
+	setenv("DVP_STRONG_REUSE", "0", 0);
 	SetHostThreadShare(opt.world);
 	if (opt.world > 1) std::cout << "rank " << opt.rank << " of " << opt.world << ": " << HostThreads() << " host threads (of " << std::thread::hardware_concurrency() << " cores)" << std::endl;
 	APD::SetDevice(opt.gpu);

@@ -37,7 +37,11 @@ EXPORTS = ["dvp_ctx_create", "dvp_ctx_destroy", "dvp_ctx_reserve", "dvp_last_err
            "dvp_jpeg_bound", "dvp_jpeg_encode", "dvp_jpeg_last_error", "dvp_preview_begin", "dvp_preview_finish", "dvp_preview_pixels",
            "dvp_canny_edge_map", "dvp_edge_hysteresis", "dvp_edge_last_error", "dvp_edge_map_begin", "dvp_edge_map_finish",
            "dvp_clean_selected_views", "dvp_viewclean_last_error", "dvp_set_view_cleanup",
-           "dvp_labels_sizes", "dvp_labels_create", "dvp_labels_destroy", "dvp_labels_run", "dvp_labels_stage", "dvp_labels_timings", "dvp_label_map", "dvp_labels_last_error"]
+           "dvp_labels_sizes", "dvp_labels_create", "dvp_labels_destroy", "dvp_labels_run", "dvp_labels_stage", "dvp_labels_timings", "dvp_label_map", "dvp_labels_last_error",
+           "dvp_images_create", "dvp_images_destroy", "dvp_images_put", "dvp_images_drop", "dvp_images_size", "dvp_images_bytes", "dvp_images_level", "dvp_images_last_error",
+           "dvp_download_image"]
+# ... and the one whose name holds a digit (a scan of the header for [a-z_] names does not see it)
+EXPORTS_WITH_DIGITS = ["dvp_upload_images_u8"]
 PREVIEW_DEPTH, PREVIEW_NORMAL, PREVIEW_WEAK = 1, 2, 4
 
 
@@ -127,6 +131,18 @@ def lib():
         L.dvp_label_map.argtypes = [ci, vp, ci, ci, ll, ci, vp]
         L.dvp_labels_last_error.restype = ctypes.c_char_p
         L.dvp_labels_last_error.argtypes = []
+        L.dvp_images_create.argtypes = [ci, ctypes.POINTER(vp)]
+        L.dvp_images_destroy.argtypes = [vp]
+        L.dvp_images_put.argtypes = [vp, ci, vp, ci, ci, ll]
+        L.dvp_images_drop.argtypes = [vp, ci]
+        L.dvp_images_size.argtypes = [vp, ci, pi, pi]
+        L.dvp_images_bytes.restype = ll
+        L.dvp_images_bytes.argtypes = [vp]
+        L.dvp_images_level.argtypes = [vp, ci, ci, ci, ci, ci, vp]
+        L.dvp_images_last_error.restype = ctypes.c_char_p
+        L.dvp_images_last_error.argtypes = []
+        L.dvp_upload_images_u8.argtypes = [vp, vp, vp, ci, ci]
+        L.dvp_download_image.argtypes = [vp, ci, vp, ci]
         _LIB = L
     return _LIB
 
@@ -274,6 +290,51 @@ class LabelJob:
         return dict(part_a_ms=ms[0], host_ms=ms[1], part_b_ms=ms[2], regions=int(n[0]), outline_points=int(n[1]))
 
 
+class ImageStore:
+    """a dvp_images store: decoded (H, W) uint8 images resident on one device, under integer ids; every pyramid level of
+    every image is made from them on the device (include/dvp_mvs.h)"""
+
+    def __init__(self, device=0):
+        self.L = lib()
+        h = ctypes.c_void_p()
+        if self.L.dvp_images_create(device, ctypes.byref(h)) != 0:
+            raise DvpError(self.L.dvp_images_last_error().decode())
+        self.h = h
+
+    def _ck(self, rc):
+        if rc != 0:
+            raise DvpError(self.L.dvp_images_last_error().decode())
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.dvp_images_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def put(self, image_id, grey):
+        a = _grey_rows(grey)
+        self._ck(self.L.dvp_images_put(self.h, int(image_id), _p(a), a.shape[1], a.shape[0], a.strides[0]))
+
+    def drop(self, image_id):
+        self._ck(self.L.dvp_images_drop(self.h, int(image_id)))
+
+    def size(self, image_id):
+        """(width, height) of a stored image"""
+        w, h = ctypes.c_int(0), ctypes.c_int(0)
+        self._ck(self.L.dvp_images_size(self.h, int(image_id), ctypes.byref(w), ctypes.byref(h)))
+        return w.value, h.value
+
+    def bytes(self):
+        return int(self.L.dvp_images_bytes(self.h))
+
+    def level(self, image_id, level_w, level_h, pad_w=0, pad_h=0):
+        """the (level_h, level_w) float32 level of a stored image on a pad_w x pad_h canvas (0: the image's own size)"""
+        out = np.empty((max(int(level_h), 0), max(int(level_w), 0)), np.float32)
+        self._ck(self.L.dvp_images_level(self.h, int(image_id), int(pad_w), int(pad_h), int(level_w), int(level_h), _p(out)))
+        return out
+
+
 class Context:
     """One reference view on one GPU (dvp_ctx).  Method names follow oracle.oracle.Oracle so the
     parity tests drive both through the same code."""
@@ -311,6 +372,18 @@ class Context:
     def set_images(self, images):
         arrs, ptrs = self._planes_ptrs(images)
         self._ck(self.L.dvp_upload_images(self.h, ptrs, self.W))
+
+    def set_images_u8(self, store, ids, pad_w, pad_h):
+        """the levels of the stored images `ids` at the context's size, made on the device (dvp_upload_images_u8)"""
+        a = np.ascontiguousarray(ids, np.int32)
+        assert a.shape == (self.NI,), a.shape
+        self._ck(self.L.dvp_upload_images_u8(self.h, store.h, _p(a), int(pad_w), int(pad_h)))
+
+    def image(self, i):
+        """the (H, W) float32 image i the context holds"""
+        out = np.empty((self.H, self.W), np.float32)
+        self._ck(self.L.dvp_download_image(self.h, int(i), _p(out), self.W))
+        return out
 
     def set_depths(self, depths):
         arrs, ptrs = self._planes_ptrs(depths)

@@ -8,6 +8,7 @@
 #include "dvp_jpeg_enc.h"
 #include "dvp_edges_run.h"
 #include "dvp_viewclean_run.h"
+#include "dvp_pyramid_run.h"
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 #include <string>
@@ -1486,6 +1487,7 @@ const char* dvp_last_error(const dvp_ctx* c) {
 	return c ? c->error.c_str() : g_create_error.c_str();
 }
 
+static int finish_planes(dvp_ctx* c, float* dst, float* pairs);
 // `pairs` != nullptr: `dst` is the staging set and the row-pair planes are produced from it
 static int upload_planes(dvp_ctx* c, float* dst, const float* const* src, int pitch_floats, hipMemcpyKind kind, float* pairs = nullptr) {
 	if (set_device(c)) return 1;
@@ -1496,6 +1498,11 @@ static int upload_planes(dvp_ctx* c, float* dst, const float* const* src, int pi
 		HIP_TRY(c, hipMemcpy2DAsync(dst + (size_t)i * stride + (size_t)kImgPad * c->pitch + kImgPad, (size_t)c->pitch * 4, src[i],
 		                            (size_t)pitch_floats * 4, (size_t)c->W * 4, (size_t)c->H, kind, c->stream));
 	}
+	return finish_planes(c, dst, pairs);
+}
+// the interiors of the planes at `dst` are queued on the stream: the border, and with `pairs` every other form of the images
+static int finish_planes(dvp_ctx* c, float* dst, float* pairs) {
+	const size_t stride = (size_t)c->pitch * (c->H + 2 * kImgPad);
 	{   // border replication == clamp-to-edge addressing (APD.cpp:1511-1515)
 		const long long cells = (long long)(2 * kImgPad * (c->W + 2 * kImgPad) + 2 * kImgPad * c->H) * c->NI;
 		hipLaunchKernelGGL(dvp_pad_replicate, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, c->stream, dst, c->W, c->H, c->pitch, stride, c->NI);
@@ -1543,6 +1550,39 @@ int dvp_upload_images_device(dvp_ctx* c, const float* const* images, int pitch_f
 	bump_reuse_epoch(c);
 	if (upload_planes(c, c->image_stage, images, pitch_floats, hipMemcpyDeviceToDevice, c->images)) return 1;
 	c->have_images = true;
+	return 0;
+}
+// the same images made on the device from the store's bytes (dvp_pyramid.hip): only the interiors' origin differs
+int dvp_upload_images_u8(dvp_ctx* c, const dvp_images* store, const int* ids, int pad_w, int pad_h) {
+	if (!c) return 1;
+	if (!store || !ids) { c->error = "dvp_upload_images_u8: the store and the ids are required"; return 1; }
+	if (pad_w < 1 || pad_h < 1 || pad_w > 32767 || pad_h > 32767) { c->error = "dvp_upload_images_u8: bad canvas size (1 ... 32767)"; return 1; }
+	if (dvppyr::store_device(store) != c->device) { c->error = "dvp_upload_images_u8: the store is on another device than the context"; return 1; }
+	dvppyr::Sources src;
+	std::string message;
+	if (dvppyr::store_sources(store, ids, c->NI, &src, &message)) { c->error = "dvp_upload_images_u8: " + message; return 1; }
+	if (src.v[0].sw != pad_w || src.v[0].sh != pad_h) { c->error = "dvp_upload_images_u8: the reference image (ids[0]) must have the canvas size"; return 1; }
+	c->anchor_tab_valid = false;
+	bump_reuse_epoch(c);
+	if (set_device(c)) return 1;
+	const size_t stride = (size_t)c->pitch * (c->H + 2 * kImgPad);
+	if (dvppyr::launch_levels(c->stream, src, c->NI, pad_w, pad_h, c->W, c->H, c->image_stage + (size_t)kImgPad * c->pitch + kImgPad, c->pitch, stride)) {
+		c->error = "dvp_upload_images_u8: launch failed";
+		return 1;
+	}
+	if (finish_planes(c, c->image_stage, c->images)) return 1;
+	c->have_images = true;
+	return 0;
+}
+int dvp_download_image(dvp_ctx* c, int index, float* out, int pitch_floats) {
+	if (!c) return 1;
+	if (!out || index < 0 || index >= c->NI || pitch_floats < c->W) { c->error = "dvp_download_image: bad arguments (0 <= index < num_images, pitch_floats >= width)"; return 1; }
+	if (!c->have_images) { c->error = "dvp_download_image: no images in the context yet (dvp_upload_images)"; return 1; }
+	if (set_device(c)) return 1;
+	const size_t stride = (size_t)c->pitch * (c->H + 2 * kImgPad);
+	HIP_TRY(c, hipMemcpy2DAsync(out, (size_t)pitch_floats * 4, c->image_stage + (size_t)index * stride + (size_t)kImgPad * c->pitch + kImgPad, (size_t)c->pitch * 4,
+	                            (size_t)c->W * 4, (size_t)c->H, hipMemcpyDeviceToHost, c->stream));
+	HIP_TRY(c, hipStreamSynchronize(c->stream));
 	return 0;
 }
 static int ensure_depths(dvp_ctx* c) {

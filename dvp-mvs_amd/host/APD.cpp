@@ -30,6 +30,9 @@ bool APD::CleanupOnDevice() { return g_cleanup_on_device; }
 static bool g_labels_on_device = false;
 void APD::SetLabelsOnDevice(bool on) { g_labels_on_device = on; }
 bool APD::LabelsOnDevice() { return g_labels_on_device; }
+static bool g_images_on_device = false;
+void APD::SetImagesOnDevice(bool on) { g_images_on_device = on; }
+bool APD::ImagesOnDevice() { return g_images_on_device; }
 // DVP_HOST_TIMING=1: wall time of the parts of the host steps (tools/e2e_timing.sh folds them per pass)
 namespace {
 struct HostLap {
@@ -233,6 +236,7 @@ void APD::PrefetchLevelImages(std::vector<Problem> views, int scale) {
 		--g_prefetch_threads;
 	}).detach();
 }
+static void release_image_store();
 void APD::ReserveImageCache(size_t views) { std::lock_guard<std::recursive_mutex> lock(g_img_cache_mutex); g_img_cache_capacity = std::max<size_t>(96, 2 * views + 8); }   // reference + padded source role
 void APD::ReleasePooledContext() {
 	while (g_prefetch_threads.load() > 0) std::this_thread::sleep_for(std::chrono::milliseconds(2));   // (they use the caches cleared below)
@@ -242,6 +246,7 @@ void APD::ReleasePooledContext() {
 		g_pool.clear();
 	}
 	if (dvp_ctx* c = take_prewarmed(-1, 0, 0, 0)) dvp_ctx_destroy(c);   // (never fits: joined and freed)
+	release_image_store();
 	std::lock_guard<std::recursive_mutex> lock(g_img_cache_mutex);
 	g_img_cache.clear();
 	g_decoded.clear();
@@ -283,6 +288,58 @@ Mat APD::DecodedGray(const path& file) {
 	g_decoded_cv.notify_all();
 	return image_uint;
 }
+void APD::InsertDecoded(const path& file, const Mat& gray) {
+	std::lock_guard<std::recursive_mutex> lock(g_img_cache_mutex);
+	if (gray.empty() || g_decoded.count(file.string()) || g_decoded_bytes + gray.step * gray.rows > kDecodedLimit) return;
+	g_decoded[file.string()] = gray;
+	g_decoded_bytes += gray.step * gray.rows;
+}
+// `apd --images-on gpu`: the job's decoded images resident on the driver's device (include/dvp_mvs.h dvp_images), 1 byte per pixel,
+// put once by the decode prefetch threads or at a view's first use; every level of every view is made from them on the device
+// (dvp_upload_images_u8).  Bounded by DVP_RESIDENT_IMAGES_GB (default 24), the budget of the float blocks it replaces: what does
+// not fit is not stored, and a view that uses it keeps the host path.
+namespace {
+dvp_images* g_image_store = nullptr;
+std::mutex g_image_store_mutex;   // the store's creation, and the check-then-put of an id
+int image_id_of(const path& file) {   // images/<8 digits>.jpg
+	const std::string stem = file.stem().string();
+	if (stem.empty() || stem.size() > 9 || stem.find_first_not_of("0123456789") != std::string::npos) return -1;
+	return std::atoi(stem.c_str());
+}
+bool stored_size_locked(int image_id, int* w, int* h) {
+	if (!g_image_store && dvp_images_create(g_device, &g_image_store) != 0) DvpFatal(std::string("dvp_images_create failed: ") + dvp_images_last_error());
+	return dvp_images_size(g_image_store, image_id, w, h) == 0;
+}
+}
+static void release_image_store() {
+	std::lock_guard<std::mutex> lock(g_image_store_mutex);
+	if (g_image_store) (void)dvp_images_destroy(g_image_store);
+	g_image_store = nullptr;
+}
+bool APD::StoreDecoded(int image_id, const path& file, int* width, int* height) {
+	{
+		std::lock_guard<std::mutex> lock(g_image_store_mutex);
+		if (stored_size_locked(image_id, width, height)) return true;
+	}
+	const Mat gray = DecodedGray(file);   // (a decode takes the time of hundreds of puts: outside the lock)
+	if (gray.empty()) return false;
+	static const size_t budget = [] {
+		const char* e = std::getenv("DVP_RESIDENT_IMAGES_GB");
+		return (size_t)(e ? std::max(0, std::atoi(e)) : 24) << 30;
+	}();
+	std::lock_guard<std::mutex> lock(g_image_store_mutex);
+	if (stored_size_locked(image_id, width, height)) return true;   // another thread put it meanwhile
+	if ((size_t)dvp_images_bytes(g_image_store) + (size_t)gray.cols * gray.rows > budget) return false;
+	if (dvp_images_put(g_image_store, image_id, gray.ptr<uint8_t>(0), gray.cols, gray.rows, (long long)gray.step) != 0)
+		DvpFatal(std::string("dvp_images_put failed: ") + dvp_images_last_error());
+	if (width) *width = gray.cols;
+	if (height) *height = gray.rows;
+	return true;
+}
+long long APD::StoredImageBytes() {
+	std::lock_guard<std::mutex> lock(g_image_store_mutex);
+	return g_image_store ? dvp_images_bytes(g_image_store) : 0;
+}
 // all images of the job decoded on a few threads while the first passes run (the coarse levels are decode-bound otherwise)
 void APD::PrefetchDecoded(const std::vector<path>& files) {
 	const int n = std::max(1, std::min(HostThreads() / 2, 16));   // (ten 25-Mpx files on eight threads were two rounds of 0.26 s before the first kernel)
@@ -302,6 +359,10 @@ void APD::PrefetchDecoded(const std::vector<path>& files) {
 					if (g_decoded_full) break;
 				}
 				(void)APD::DecodedGray((*queue)[i]);
+				if (g_images_on_device) {   // ... and resident on the device from now on, every level is made from it there
+					const int id = image_id_of((*queue)[i]);
+					if (id >= 0) (void)APD::StoreDecoded(id, (*queue)[i]);
+				}
 			}
 			--g_prefetch_threads;
 		}).detach();
@@ -413,8 +474,31 @@ void APD::InuputInitialization() {
 	auto load = [&](int image_id, int pad_w, int pad_h, bool is_ref) -> ImageEntry {
 		return load_image(problem, image_id, pad_w, pad_h, is_ref);
 	};
-	std::vector<std::pair<int, int>> orig_sizes;   // (cols, rows) before scaling, per image
-	{
+	std::vector<std::pair<int, int>> orig_sizes;    // (cols, rows) before scaling, per image
+	std::vector<std::pair<int, int>> level_sizes;   // ... and at this pass' level
+	images_on_device = false;
+	if (g_images_on_device) {   // every image of the view in the store: the levels are made on the device, no float image here
+		std::string reason;
+		int rw = 0, rh = 0;
+		if (problem.src_image_ids.size() + 1 > MAX_IMAGES) reason = "too many images";
+		for (size_t i = 0; i <= problem.src_image_ids.size() && reason.empty(); ++i) {
+			const int id = i == 0 ? problem.ref_image_id : problem.src_image_ids[i - 1];
+			if (!StoreDecoded(id, image_folder / path(ToFormatIndex(id) + ".jpg"), i == 0 ? &rw : nullptr, i == 0 ? &rh : nullptr))
+				reason = "image " + std::to_string(id) + " is not in the store";
+		}
+		images_on_device = reason.empty();
+		if (images_on_device) {
+			// a source is padded / cropped to the reference's size before it is resized (load_image): every image has that size
+			const float factor = 1.0f / (float)(problem.scale_size);
+			const int lw = problem.scale_size != 1 ? (int)std::round(rw * factor) : rw, lh = problem.scale_size != 1 ? (int)std::round(rh * factor) : rh;
+			width = ref_orig_width = rw;
+			height = ref_orig_height = rh;
+			orig_sizes.assign(problem.src_image_ids.size() + 1, std::make_pair(rw, rh));
+			level_sizes.assign(problem.src_image_ids.size() + 1, std::make_pair(lw, lh));
+			ViewLog() << "Images: levels made on the device" << std::endl;
+		} else ViewLog() << "Images: host path (" << reason << ")" << std::endl;
+	}
+	if (!images_on_device) {
 		const ImageEntry ci = load(problem.ref_image_id, 0, 0, true);
 		images.push_back(ci.image);
 		orig_sizes.emplace_back(ci.orig_cols, ci.orig_rows);
@@ -422,14 +506,15 @@ void APD::InuputInitialization() {
 		height = ci.orig_rows;
 		ref_orig_width = ci.orig_cols;
 		ref_orig_height = ci.orig_rows;
+		for (const auto& src_idx : problem.src_image_ids) {
+			const ImageEntry si = load(src_idx, width, height, false);
+			images.push_back(si.image);
+			orig_sizes.emplace_back(si.orig_cols, si.orig_rows);
+		}
+		for (const Mat& m : images) level_sizes.emplace_back(m.cols, m.rows);
 	}
-	for (const auto& src_idx : problem.src_image_ids) {
-		const ImageEntry ci = load(src_idx, width, height, false);
-		images.push_back(ci.image);
-		orig_sizes.emplace_back(ci.orig_cols, ci.orig_rows);
-	}
-	if (images.size() > MAX_IMAGES) {
-		DvpFatal("Can't process so much images: " + std::to_string(images.size()));
+	if (orig_sizes.size() > MAX_IMAGES) {
+		DvpFatal("Can't process so much images: " + std::to_string(orig_sizes.size()));
 	}
 	{
 		Camera cam;
@@ -447,14 +532,14 @@ void APD::InuputInitialization() {
 	}
 	params_host.depth_min = cameras[0].depth_min * 0.6f;   // APD.cpp:1109-1110
 	params_host.depth_max = cameras[0].depth_max * 1.2f;
-	params_host.num_images = (int)images.size();
-	num_images = (int)images.size();
+	params_host.num_images = (int)orig_sizes.size();
+	num_images = (int)orig_sizes.size();
 	ViewLog() << "Read images and camera done\n";
 	ViewLog() << "Depth range: " << params_host.depth_min << " " << params_host.depth_max << std::endl;
 	ViewLog() << "Num images: " << params_host.num_images << std::endl;
 	if (problem.scale_size != 1) {   // APD.cpp:1119-1143 (the images were rescaled by load())
 		for (int i = 0; i < num_images; ++i) {
-			const int new_cols = images[i].cols, new_rows = images[i].rows;
+			const int new_cols = level_sizes[i].first, new_rows = level_sizes[i].second;
 			const float scale_x = new_cols / static_cast<float>(orig_sizes[i].first);
 			const float scale_y = new_rows / static_cast<float>(orig_sizes[i].second);
 			width = new_cols;
@@ -729,7 +814,11 @@ void APD::CudaSpaceInitialization() {
 		if (resident_images) ptrs[i] = it->second.ptr;
 	}
 	}
-	if (resident_images) DVP_SAFE_CALL(ctx, dvp_upload_images_device(ctx, ptrs.data(), width));
+	if (images_on_device) {   // (sources of another original size included: the canvas is part of the level's definition)
+		std::vector<int> ids(1, problem.ref_image_id);
+		ids.insert(ids.end(), problem.src_image_ids.begin(), problem.src_image_ids.end());
+		DVP_SAFE_CALL(ctx, dvp_upload_images_u8(ctx, g_image_store, ids.data(), ref_orig_width, ref_orig_height));
+	} else if (resident_images) DVP_SAFE_CALL(ctx, dvp_upload_images_device(ctx, ptrs.data(), width));
 	else {
 		for (int i = 0; i < num_images; ++i) ptrs[i] = images[i].ptr<float>(0);
 		DVP_SAFE_CALL(ctx, dvp_upload_images(ctx, ptrs.data(), width));

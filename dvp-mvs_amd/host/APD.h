@@ -146,6 +146,18 @@ public:
 	// Announcing, publishing, file names and SetUseLabelFiles are untouched.  Same values.  Default false.
 	static void SetLabelsOnDevice(bool on);
 	static bool LabelsOnDevice();
+	// `apd --images-on gpu`.  true: the process keeps the job's decoded 8-bit images in one dvp_images store on the driver's device
+	// (put by the decode prefetch threads or at a view's first use, within DVP_RESIDENT_IMAGES_GB), and a view whose images are all
+	// there builds no host float image: InuputInitialization takes the sizes from the store and the std::round(n * factor) rule,
+	// CudaSpaceInitialization has the engine make the level of every image from the bytes (dvp_upload_images_u8: padding /
+	// cropping to the reference's size, cv::resize(INTER_LINEAR)).  A view with an image missing from the store takes the host
+	// path, whole.  Either way the view logs one line, "Images: levels made on the device" or "Images: host path (<reason>)".
+	// Same texels, same dvp_image_format.  Default false.
+	static void SetImagesOnDevice(bool on);
+	static bool ImagesOnDevice();
+	static bool StoreDecoded(int image_id, const path& image_file, int* width = nullptr, int* height = nullptr);   // false: unreadable, or no room in the store
+	static long long StoredImageBytes();   // device bytes the store holds
+	static void InsertDecoded(const path& image_file, const Mat& gray);   // a decoded image that came from another rank
 	// true (default): a pass that starts from maps of another size (REFINE_INIT on a finer pyramid level) hands them to the
 	// engine at their own size and RescaleMatToTargetSize runs there (dvp_upload_state_rescaled); false: the five host-side
 	// rescales + the plane assembly of the reference's flow (APD.cpp:1176-1180, 1440-1456, 1656-1659).  Same maps either way.
@@ -199,6 +211,7 @@ private:
 	int ctx_device = 0;
 	DvpTimings timings{};
 	int image_format = 0;
+	bool images_on_device = false;   // this view's level images are made by the engine from the store (SetImagesOnDevice)
 	bool edge_on_device = false;   // the edge map is made by the engine (SetEdgesOnDevice) and its file still has to be published
 	path edge_file, rawedge_file;
 };

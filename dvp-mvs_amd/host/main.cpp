@@ -3,6 +3,7 @@
 //   apd <dense_folder> [gpu_index] [--max-src N] [--iters N] [--min-scale S] [--passes P] [--seed X]
 //       [--rank R --world N --job ID [--transport rccl|host] [--collective-timeout SEC]] [--jacobi] [--labels]
 //       [--no-fusion | --fusion eth|tat-intermediate|tat-advanced] [--fusion-on device|host]
+//       [--edges-on host|gpu] [--labels-on host|gpu] [--cleanup-on host|gpu] [--images-on host|gpu]
 //
 // Schedule.  The image pyramid has round_num levels (the longer side is halved until <= 800).  Level i
 // runs one "A" pass without geometric consistency — FIRST_INIT from scratch / the Depth-Anything prior
@@ -46,6 +47,7 @@ struct Options {
 	bool edges_on_gpu = false;             // --edges-on gpu: the Canny edge prior is made by the engine from the resident image (APD::SetEdgesOnDevice)
 	bool labels_on_gpu = false;            // --labels-on gpu: GetProblemEdges makes the label maps with a dvp_labels job on the rank's device (APD::SetLabelsOnDevice)
 	bool cleanup_on_gpu = false;           // --cleanup-on gpu: the visibility-mask clean-up runs in the engine on the staged selected-view words (APD::SetCleanupOnDevice)
+	bool images_on_gpu = false;            // --images-on gpu: every view's level images are made by the engine from the decoded bytes, uploaded once per job (APD::SetImagesOnDevice)
 	bool previews = false;                 // --previews: the reference's show_medium_result preview images (depth/normal/weak_<it>.jpg, weak.png, rawedge_<s>.jpg)
 	int views_in_flight = 0;               // --views-in-flight N: that many views of a pass at once (default 2) where the order allows it and the level is small; 1 = never
 	long long in_flight_pixels = 2 << 20;  // ... "small" = at most this many pixels (--in-flight-pixels)
@@ -485,6 +487,28 @@ void ShareLevelImages(RankComm& comm, std::vector<Problem>& problems, const std:
 	}
 }
 
+// --images-on gpu: the owner of a view broadcasts the DECODED file once per job — meta, then 1 byte per pixel — and the others
+// keep it in their decoded cache, from where every level of it is made on their device; no float image travels per level.
+void ShareDecodedImages(RankComm& comm, const std::vector<Problem>& problems, const std::vector<int>& owner_of) {
+	if (comm.world() <= 1) return;
+	for (const Problem& p : problems) {
+		const path file = p.dense_folder / "images" / (ToFormatIndex(p.ref_image_id) + ".jpg");
+		const int owner = owner_of[(size_t)p.index];
+		int meta[2] = { 0, 0 };   // cols, rows (0 x 0: the owner cannot read the file and will stop the job when it loads it)
+		Mat gray;
+		if (comm.rank() == owner) {
+			gray = APD::DecodedGray(file);
+			meta[0] = gray.cols;
+			meta[1] = gray.rows;
+		}
+		comm.BroadcastHost(meta, sizeof(meta), owner);
+		if (meta[0] <= 0 || meta[1] <= 0) continue;
+		if (comm.rank() != owner) gray = Mat(meta[1], meta[0], CV_8UC1);
+		comm.BroadcastHost(gray.data, (size_t)meta[0] * meta[1], owner);
+		if (comm.rank() != owner) APD::InsertDecoded(file, gray);
+	}
+}
+
 Options ParseOptions(int argc, char** argv) {
 	Options o;
 	o.dense_folder = argv[1];
@@ -525,6 +549,11 @@ Options ParseOptions(int argc, char** argv) {
 			if (where != "host" && where != "gpu") { std::cerr << "--cleanup-on takes host or gpu\n"; std::exit(1); }
 			o.cleanup_on_gpu = where == "gpu";
 		}
+		else if (s == "--images-on" && a + 1 < argc) {
+			const std::string where = argv[++a];
+			if (where != "host" && where != "gpu") { std::cerr << "--images-on takes host or gpu\n"; std::exit(1); }
+			o.images_on_gpu = where == "gpu";
+		}
 		else if (s == "--host-rescale") o.host_rescale = true;     // the coarser level's maps are up-sampled on the host (APD::SetDeviceRescale(false))
 		else if (s == "--fusion") { if (a + 1 < argc) o.fusion_kind = argv[++a]; }
 		else if (s == "--fusion-on") { if (a + 1 < argc) o.fusion_on_host = std::string(argv[++a]) == "host"; }   // device (default) | host
@@ -540,7 +569,7 @@ Options ParseOptions(int argc, char** argv) {
 
 int main(int argc, char** argv) {
 	if (argc < 2) {
-		std::cerr << "USAGE: apd dense_folder [gpu_index] [--previews] [--max-src N] [--iters N] [--min-scale S] [--passes P] [--seed X] [--rank R --world N [--job ID]] [--jacobi] [--no-fusion | --fusion KIND] [--fusion-on device|host] [--edges-on host|gpu] [--labels-on host|gpu] [--cleanup-on host|gpu] [--views-in-flight N]\n";
+		std::cerr << "USAGE: apd dense_folder [gpu_index] [--previews] [--max-src N] [--iters N] [--min-scale S] [--passes P] [--seed X] [--rank R --world N [--job ID]] [--jacobi] [--no-fusion | --fusion KIND] [--fusion-on device|host] [--edges-on host|gpu] [--labels-on host|gpu] [--cleanup-on host|gpu] [--images-on host|gpu] [--views-in-flight N]\n";
 		return EXIT_FAILURE;
 	}
 	const Options opt = ParseOptions(argc, argv);
@@ -574,6 +603,7 @@ int main(int argc, char** argv) {
 	APD::SetEdgesOnDevice(opt.edges_on_gpu);
 	APD::SetCleanupOnDevice(opt.cleanup_on_gpu);
 	APD::SetLabelsOnDevice(opt.labels_on_gpu);
+	APD::SetImagesOnDevice(opt.images_on_gpu);
 	SetResultCache(!opt.sync_io);
 	APD::SetDeviceRescale(!opt.sync_io && !opt.host_rescale);
 	g_device_maps = !opt.sync_io && !opt.host_rescale;
@@ -623,12 +653,16 @@ int main(int argc, char** argv) {
 	else if (!opt.sync_io) inplace.reset(new InPlaceDepths());
 	int shared_scale = -1;
 	LevelImages level_images;
+	if (opt.images_on_gpu) {
+		ShareDecodedImages(comm, problems, owner_of);
+		main_lap("decoded images shared");
+	}
 	for (size_t it = 0; it < plan.size(); ++it) {
 		const Pass& pass = plan[it];
 		const bool new_level = pass.scale != shared_scale;
 		main_t = std::chrono::steady_clock::now();
 		if (new_level) {
-			ShareLevelImages(comm, problems, owner_of, pass.scale);
+			if (!opt.images_on_gpu) ShareLevelImages(comm, problems, owner_of, pass.scale);
 			shared_scale = pass.scale;
 			if (exchange) exchange->Release();   // maps of the coarser level do not fit this one (and its A pass has no geometric term)
 		}
@@ -638,7 +672,7 @@ int main(int argc, char** argv) {
 			ConfigurePass(problem, pass, (int)it, opt.iters, round_num);
 			if (owner_of[(size_t)problem.index] == opt.rank) owned.push_back(&problem);
 		}
-		if (new_level && !opt.sync_io) level_images.Fill(owned, pass.scale);
+		if (new_level && !opt.sync_io && !opt.images_on_gpu) level_images.Fill(owned, pass.scale);   // (--images-on gpu: the views make their levels from the store)
 		if (new_level) main_lap("level " + std::to_string(pass.level) + ": images shared + resident on the device");
 		// last pass of a level: the next level's context and float images are made by helper threads while the GPU works
 		if (!opt.sync_io && it + 1 < plan.size() && plan[it + 1].scale != pass.scale && !owned.empty()) {
@@ -646,7 +680,7 @@ int main(int argc, char** argv) {
 			if (APD::LevelSize(*owned[0], plan[it + 1].scale, &nw, &nh)) APD::PrewarmContext(nw, nh, (int)owned[0]->src_image_ids.size() + 1, plan[it + 1].scale);
 			std::vector<Problem> mine_next;
 			for (const Problem* p : owned) mine_next.push_back(*p);
-			APD::PrefetchLevelImages(mine_next, plan[it + 1].scale);
+			if (!opt.images_on_gpu) APD::PrefetchLevelImages(mine_next, plan[it + 1].scale);
 		}
 		// The edge / label maps of an A pass (main.cpp:480: GetProblemEdges before every view).  Round 4 made the NEXT view's maps
 		// while the GPU worked on the current one — on the one background worker, behind that view's clean-up job: at the coarse
@@ -772,6 +806,7 @@ int main(int argc, char** argv) {
 		main_lap("pass " + std::to_string(it) + ": helpers joined, exchange / barrier");
 		if (pass.geom_index == opt.geom_passes - 1 || (opt.geom_passes == 0 && pass.geom_index < 0)) std::cout << "Round: " << pass.level << " done\n";
 	}
+	if (opt.images_on_gpu && main_timing) std::cout << "[main] decoded images on the device: " << APD::StoredImageBytes() << " bytes" << std::endl;
 	main_t = std::chrono::steady_clock::now();
 	if (exchange) exchange->Release();
 	exchange.reset();

@@ -366,6 +366,39 @@ int dvp_labels_timings(const dvp_labels* job, double* ms, long long* counts);
 int dvp_label_map(int device, const uint8_t* grey, int width, int height, long long pitch_bytes, int scale, int32_t* label_out);
 const char* dvp_labels_last_error(void);   /* the calling thread's last dvp_labels_* / dvp_label_map error */
 
+/* ---- level images made on the device from the decoded 8-bit files (load_image, host/APD.cpp; APD.cpp:1057-1131) -----------------
+ * A store keeps decoded grey images on one device, 1 byte per pixel, under ids the caller chooses.  A level image is a function of
+ * such an image: the bytes lie at the origin of a pad_w x pad_h canvas (zero beyond the image, cropped beyond the canvas: what the
+ * reference does to a source of another size than its reference image), the canvas becomes float, and cv::resize(INTER_LINEAR)
+ * takes it to the level size — source coordinate (float)((d + 0.5) * s - 0.5) with s = (double)pad_n / level_n, floor, the
+ * second tap clamped to the canvas, the horizontal blend on two rows and then the vertical one, each p * (1.f - a) + q * a in
+ * binary32 without fused operations.  Equal sizes give the bytes as floats.  Equal to the host mirror's load_image value for value,
+ * so a caller needs no cv::resize of its own to feed a context.
+ * The store is locked internally: uploads from several contexts and threads and dvp_images_level calls are reads and run side by
+ * side, and a dvp_images_put of another id may run beside them.  Dropping an id (or destroying the store) while an upload or a
+ * level call uses it is the caller's error. */
+typedef struct dvp_images dvp_images;
+int dvp_images_create(int device, dvp_images** out);
+int dvp_images_destroy(dvp_images* store);
+/* grey: width x height bytes, `pitch_bytes` per row; copied to the device, returns when the copy is done.  An id already present is
+ * an error (dvp_images_drop it first); widths and heights of 1 ... 32767. */
+int dvp_images_put(dvp_images* store, int id, const uint8_t* grey, int width, int height, long long pitch_bytes);
+int dvp_images_drop(dvp_images* store, int id);                                  /* != 0: not in the store */
+int dvp_images_size(const dvp_images* store, int id, int* width, int* height);   /* != 0: not in the store; NULL pointers are skipped */
+long long dvp_images_bytes(const dvp_images* store);                             /* device bytes held */
+/* One level to the host: host_out receives level_w x level_h floats, dense.  pad_w = pad_h = 0: the image's own size.  Any sizes of
+ * 1 ... 32767, up-sampling included. */
+int dvp_images_level(dvp_images* store, int id, int pad_w, int pad_h, int level_w, int level_h, float* host_out);
+const char* dvp_images_last_error(void);   /* the calling thread's last dvp_images_* error */
+/* Fills the context's num_images images with the levels of ids[0 .. num_images-1] at the context's width x height, every image on
+ * a pad_w x pad_h canvas: the reference image's original size, which ids[0] must have exactly.  Everything is checked before the
+ * context is touched — the store is on the context's device, every id is present, the sizes are valid — so after an error
+ * (dvp_last_error) the context still holds its previous images.  Afterwards the context is in the state dvp_upload_images of
+ * those float images leaves it in, buffer for buffer and bit for bit, dvp_image_format included. */
+int dvp_upload_images_u8(dvp_ctx* ctx, const dvp_images* store, const int* ids, int pad_w, int pad_h);
+/* The width x height float image `index` the context holds since its last dvp_upload_images*, `pitch_floats` (>= width) per row. */
+int dvp_download_image(dvp_ctx* ctx, int index, float* out, int pitch_floats);
+
 #ifdef __cplusplus
 }
 #endif

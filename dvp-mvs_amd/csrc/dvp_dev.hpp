@@ -14,6 +14,7 @@
 #include <float.h>
 #include <string.h>
 #include "../../include/dvp_mvs.h"
+#include "dvp_forms.hpp"
 
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>

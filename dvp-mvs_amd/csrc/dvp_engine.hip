@@ -285,10 +285,7 @@ extern "C" __global__ void __launch_bounds__(256) dvp_sweep_decide2(const Dev d,
 // > 0 — are compacted into a list in LDS (ballot ranks, row after row) and taken 64 per round, so that every lane of a round
 // evaluates (71 % of the pixels select a given view at cfg3: 2.8 rounds of 64 instead of 4 rows with 29 % of the lanes idle).
 // a.iter = stage (0: central window + LocalRefine's extra slot, 1: the rest of the line for pixels with a central peak).
-#ifndef DVP_SWEEP_ROWS
-#define DVP_SWEEP_ROWS 14
-#endif
-constexpr int kSweepRows = DVP_SWEEP_ROWS;   // rows of a dvp_sweep_eval tile (64 x kSweepRows pixels; 14: patch table 18 KB + list 1.75 KB + two cameras = 20 KB, 8 workgroups per CU)
+// (a tile is 64 x kSweepRows pixels: dvp_forms.hpp)
 template <int SMP>
 __device__ __forceinline__ void sweep_eval_body(const Dev& d, const LaunchArgs& a) {
 	const int lane = threadIdx.x;
@@ -1124,6 +1121,9 @@ enum { EV_TOTAL = -1, EV_ITER_LOOP = -2 };
 
 struct dvp_ctx {
 	int device = 0;
+	// The DVP_* switches as read when the context was created, and — the `*_fits` members below — whether the optional buffers
+	// of a form could be had.  Which form a launch site takes is decided from the two by dvp_forms.hpp.
+	FormSwitches sw;
 	int W = 0, H = 0, NI = 0, pitch = 0;
 	size_t L = 0;
 	hipStream_t stream = nullptr;
@@ -1135,8 +1135,7 @@ struct dvp_ctx {
 	// RandomInit and the strong update instead and cost them 28 ms); at the 1-3 % WEAK of the real schedule's full-size passes the
 	// anchor search is over after 12-38 ms and the full launch was 50-60 ms exposed per view (profiles/r06_e2e_apd.txt).
 	// DVP_CAND_MASK=1 / 0 forces a form; default: masked below 4 % WEAK.
-	int cand_mask_mode = -1;
-	bool cand_mask_on = true;
+	bool cand_mask_fits = true;    // false: the mark bytes did not fit
 	uint8_t* cand_mask = nullptr;
 	unsigned *cand_list = nullptr, *cand_n = nullptr;
 	uint32_t* sel_snap = nullptr;
@@ -1149,10 +1148,8 @@ struct dvp_ctx {
 	uint8_t* images8 = nullptr;     // the same as bytes; images8_ok says whether the last upload was 8-bit exact
 	int* images8_flag = nullptr;
 	bool images8_ok = false;
-	bool no_images8 = false;        // DVP_NO_IMAGES8 in the environment: keep the float planes for every kernel (A/B measurements)
 	uint32_t* images16 = nullptr;   // the same as binary16 pairs (Dev::images16), allocated at the first upload (or dvp_ctx_reserve) that wants them
 	bool images16_ok = false;       // the last upload is binary16-exact and not 8-bit exact: the weak update reads images16
-	bool no_images16 = false;       // DVP_NO_IMAGES16 in the environment: such sets keep the float planes (A/B measurements)
 	float* image_stage = nullptr;   // plain padded planes the uploads land in before dvp_interleave_rows
 	float* depths = nullptr;
 	uint32_t* edge_bits = nullptr;  // bit-tiled copy of `edge`, rebuilt before the launches that walk lines
@@ -1166,18 +1163,12 @@ struct dvp_ctx {
 	float* strong_rec = nullptr; // [SR_FIELDS][half_w * H]
 	// plane cache of the split strong update (Dev::reuse_*), allocated with slot_costs' stand-in at the first launch
 	float* reuse_costs = nullptr; PlaneKey* reuse_keys = nullptr; ReuseHdr* reuse_hdr = nullptr;
-	bool strong_reuse = true;    // DVP_STRONG_REUSE=0, or the records did not fit: the per-launch half-size cost buffer
+	bool reuse_fits = true;      // false: the records did not fit — the per-launch half-size cost buffer
 	uint32_t reuse_epoch = 0;    // bump_reuse_epoch
-	bool strong_split = true;    // DVP_STRONG_SPLIT=0 in the environment: the monolithic kernel (A/B measurements)
-	bool eval_items = true;      // DVP_EVAL_ITEMS=0: dvp_strong_eval with a pixel per lane instead of (pixel, slot) items over the lanes
-	bool refine_lanes = true;    // DVP_REFINE_LANES=0: dvp_strong_refine with the wave in lock step over hypotheses and views
+	bool split_fits = true;      // false: slot_costs did not fit — the monolithic kernel
 	f4* sweep_rec = nullptr; float* sweep_cost = nullptr; float* sweep_pc = nullptr;   // DepthToWeak + LocalRefine as view-compacted passes (allocated at the first fused launch)
-	bool ransac_wave = false;    // DVP_RANSAC_WAVE=1: RANSACToGetFitPlane one wave per WEAK pixel, lane = draw (round 6: measured no faster, 16.1 vs 15.9 ms at cfg3, 55.6 vs 49.0 at 25 % WEAK)
-	bool sweep_split = true;     // DVP_SWEEP_SPLIT=0, or the buffers did not fit: the fused per-pixel kernel
-	bool sweep_force = false;    // DVP_SWEEP_SPLIT=2: the passes also without the geometric term (tests)
-	double sweep_band_gb = 0.0;  // DVP_SWEEP_BAND_GB=g: sweep_cost holds a band of rows of at most g GB and the passes run band after band (0: the whole image, 67 GB at 6208x4128 with 9 sources)
-	int sweep_band_rows = 0;     // rows of a band (a multiple of the evaluation tile's rows); 0 = not banded
-	bool gn_wave = false;        // DVP_GN_WAVE=1: GenNeighbours' search as one wave per WEAK pixel (dvp_gen_neighbours_search; measured slower)
+	bool sweep_fits = true;      // false: the buffers did not fit — the fused per-pixel kernel
+	int sweep_band_rows = 0;     // rows of a band of sweep_cost (DVP_SWEEP_BAND_GB; 67 GB for the whole image at 6208x4128 with 9 sources); 0 = not banded
 	float* costs = nullptr; float* costs_snap = nullptr; float* complex_ = nullptr;
 	uint32_t* selected_views = nullptr;
 	uint8_t* view_weight = nullptr; uint8_t* weak_info = nullptr; uint8_t* weak_reliable = nullptr; uint8_t* edge = nullptr;
@@ -1189,14 +1180,11 @@ struct dvp_ctx {
 	AnchorRec* anchor_tab = nullptr;   // [WEAK][S][11] reference sides of the anchor sub-patches (dvp_weak_wave.hpp), allocated at the first weak update
 	size_t anchor_tab_alloc = 0;       // capacity in records
 	bool anchor_tab_valid = false;     // built for the current anchors / offsets / images (any launch or upload that can change them clears it)
-	bool anchor_tab_off = false;       // DVP_WEAK_ANCHOR_TAB=0, or the table did not fit: the weak update forms the reference side per item
+	bool anchor_tab_fits = true;       // false: the table did not fit — the weak update forms the reference side per item
 	// the weak update as seven launches (dvp_weak_phased.hpp): per-WEAK-pixel hand-over, allocated at the first weak update
 	WeakRec* weak_rec = nullptr; f2* weak_ctab = nullptr; float* weak_ev = nullptr;
 	size_t weak_phase_alloc = 0;       // capacity in WEAK pixels
-	bool weak_phased = true;           // DVP_WEAK_PHASED=0, no anchor table, or the buffers did not fit: the one-wave form
-	int weak_phased_min = 8192;        // WEAK pixels of a launch below which the one-wave kernel is used (DVP_WEAK_PHASED_MIN; tests: 0)
-	int weak_run[4] = { 64, 256, 1024, 1024 };   // WEAK pixels per XCD run of the same launches (DVP_WEAK_RUNS=a,b,c,d)
-	int weak_group[4] = { 1, 4, 4, 2 };   // WEAK pixels per wave of E0 / E1 / E2a / E2b (DVP_WEAK_GROUPS=a,b,c,d: A/B measurements)
+	bool weak_phase_fits = true;       // false: the buffers did not fit — the one-wave form
 	int* weak_list = nullptr;    // compacted WEAK pixel indices (black first, then red)
 	size_t weak_list_alloc = 0;
 	int* weak_counts = nullptr;  // scratch of the device-side compaction: per-slot black / red counts, per-chunk counts, then 3 totals
@@ -1282,6 +1270,11 @@ static void dfree(dvp_ctx* c, T** p) {
 	*p = nullptr;
 }
 
+// one block of a group of optional buffers (alloc_group_or_fall_back)
+struct AllocReq { void** p; size_t bytes; bool zero; };   // p == nullptr: nothing to allocate
+template <class T>
+static AllocReq areq(T** p, size_t bytes, bool zero = false) { return { reinterpret_cast<void**>(p), bytes, zero }; }
+
 // The plane cache's records (Dev::reuse_*) hold cost vectors from one strong update of a pass to the next.  A vector depends on
 // the images, the cameras, the parameters, the sampler and the radius map (the header checks the pixel's own radius): every call
 // that can change one of them, and the start of every dvp_run_patchmatch, makes all records empty by moving on to a new epoch.
@@ -1294,6 +1287,8 @@ static void bump_reuse_epoch(dvp_ctx* c) {
 }
 
 static size_t img16_plane_bytes(int W, int H) { return (size_t)img16_tiles_x(W) * img16_tiles_y(H) * 128; }
+
+static bool anchor_table_off(const dvp_ctx* c) { return c->sw.anchor_tab_off || !c->anchor_tab_fits; }
 
 static void sync_dev_struct(dvp_ctx* c) {
 	Dev& d = c->d;
@@ -1310,7 +1305,7 @@ static void sync_dev_struct(dvp_ctx* c) {
 	d.planes = c->planes; d.planes_snap = c->planes_snap; d.costs = c->costs; d.costs_snap = c->costs_snap;
 	d.selected_views = c->selected_views; d.view_weight = c->view_weight; d.weak_info = c->weak_info;
 	d.weak_reliable = c->weak_reliable; d.weak_nearest_strong = c->weak_nearest_strong;
-	d.anchor_tab = (c->anchor_tab_off || !c->anchor_tab_valid) ? nullptr : c->anchor_tab; d.neighbours_map = c->neighbours_map; d.neighbours = c->neighbours; d.gn_points = c->gn_points; d.gn_count = c->gn_count; d.fit_planes = c->fit_planes;
+	d.anchor_tab = (anchor_table_off(c) || !c->anchor_tab_valid) ? nullptr : c->anchor_tab; d.neighbours_map = c->neighbours_map; d.neighbours = c->neighbours; d.gn_points = c->gn_points; d.gn_count = c->gn_count; d.fit_planes = c->fit_planes;
 	d.candidate = c->candidate; d.edge = c->edge; d.edge_bits = c->edge_bits; d.strong_bits = c->strong_bits; d.strong_bits_t = c->strong_bits_t; d.edge_sat = c->edge_sat; d.sat_cells_x = sat_cells(c->W); d.sat_cells_y = sat_cells(c->H); d.edge_tiles_x = edge_tiles_x(c->W); d.edge_neigh = c->edge_neigh; d.label = c->label;
 	d.label_boundary = c->label_boundary; d.label_stop = c->label_stop; d.complex_ = c->complex_; d.radius = c->radius;
 	d.weak_list = c->weak_list;
@@ -1347,31 +1342,8 @@ int dvp_ctx_create(int device, int width, int height, int num_images, dvp_ctx** 
 	}
 	dvp_ctx* c = new dvp_ctx();
 	c->device = device; c->W = width; c->H = height; c->NI = num_images;
-	c->no_images8 = getenv("DVP_NO_IMAGES8") != nullptr;
-	c->no_images16 = getenv("DVP_NO_IMAGES16") != nullptr;
-	if (const char* e = getenv("DVP_STRONG_SPLIT")) c->strong_split = atoi(e) != 0;
-	if (const char* e = getenv("DVP_STRONG_REUSE")) c->strong_reuse = atoi(e) != 0;
+	c->sw = read_form_switches();
 	bump_reuse_epoch(c);
-	if (const char* e = getenv("DVP_REFINE_LANES")) c->refine_lanes = atoi(e) != 0;
-	if (const char* e = getenv("DVP_EVAL_ITEMS")) c->eval_items = atoi(e) != 0;
-	if (const char* e = getenv("DVP_SWEEP_SPLIT")) { c->sweep_split = atoi(e) != 0; c->sweep_force = atoi(e) == 2; }
-	if (const char* e = getenv("DVP_SWEEP_BAND_GB")) c->sweep_band_gb = atof(e);
-	if (const char* e = getenv("DVP_WEAK_ANCHOR_TAB")) c->anchor_tab_off = atoi(e) == 0;   // A/B measurements and the tests of the per-item form
-	if (const char* e = getenv("DVP_GN_WAVE")) c->gn_wave = atoi(e) != 0;
-	if (const char* e = getenv("DVP_RANSAC_WAVE")) c->ransac_wave = atoi(e) != 0;
-	if (const char* e = getenv("DVP_CAND_MASK")) c->cand_mask_mode = atoi(e) != 0 ? 1 : 0;
-	if (const char* e = getenv("DVP_WEAK_PHASED")) c->weak_phased = atoi(e) != 0;
-	if (const char* e = getenv("DVP_WEAK_PHASED_MIN")) c->weak_phased_min = atoi(e);
-	if (const char* e = getenv("DVP_WEAK_RUNS")) {
-		int g[4];
-		if (sscanf(e, "%d,%d,%d,%d", &g[0], &g[1], &g[2], &g[3]) == 4)
-			for (int i = 0; i < 4; ++i) c->weak_run[i] = g[i] < 1 ? 1 : g[i];
-	}
-	if (const char* e = getenv("DVP_WEAK_GROUPS")) {
-		int g[4];
-		if (sscanf(e, "%d,%d,%d,%d", &g[0], &g[1], &g[2], &g[3]) == 4)
-			for (int i = 0; i < 4; ++i) c->weak_group[i] = g[i] < 1 ? 1 : (g[i] > kGrp ? kGrp : g[i]);   // (E0: at most kGrpWide, applied at the launch)
-	}
 	c->pitch = (width + 2 * kImgPad + 63) / 64 * 64;
 	c->L = (size_t)width * height;
 	auto fail = [&](int) { g_create_error = c->error; dvp_ctx_destroy(c); return 1; };
@@ -1523,8 +1495,9 @@ static int finish_planes(dvp_ctx* c, float* dst, float* pairs) {
 		int inexact = 3;
 		HIP_TRY(c, hipMemcpyAsync(&inexact, c->images8_flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
 		HIP_TRY(c, hipStreamSynchronize(c->stream));
-		c->images8_ok = inexact == 0 && !c->no_images8;
-		c->images16_ok = inexact == 1 && !c->no_images8 && !c->no_images16;
+		const int fmt = image_format(c->sw, (unsigned)inexact);
+		c->images8_ok = fmt == 1;
+		c->images16_ok = fmt == 2;
 		if (c->images16_ok) {
 			if (ensure_images16(c)) { c->images16_ok = false; sync_dev_struct(c); return 1; }
 			const int t16x = img16_tiles_x(c->W), t16y = img16_tiles_y(c->H);
@@ -1819,57 +1792,65 @@ int dvp_set_seed(dvp_ctx* c, uint64_t seed) { c->d.seed = seed; return 0; }
 int dvp_set_sampler(dvp_ctx* c, int s) { c->d.sampler = s ? 1 : 0; bump_reuse_epoch(c); return 0; }
 int dvp_set_profiling(dvp_ctx* c, int on) { c->profiling = on != 0; sync_dev_struct(c); return 0; }
 
-// ---- launches ---------------------------------------------------------------------------------
-// `fused` (dvp_run_patchmatch only): DepthToWeak does LocalRefine too; GenEdgeInform leaves the visibility-prior
-// candidates to dvp_run_patchmatch (side stream; not computed at all when the pass has no WEAK pixel: their only
-// reader is the weak update's anchor_cost)
+// ---- optional buffers ---------------------------------------------------------------------------
+// The buffers only one form of a launch site needs are allocated at the first launch that wants them, or ahead of it by
+// dvp_ctx_reserve, off the critical path (a multi-GB hipMalloc inside a launch site took 0.5-1 s of a view on some boxes:
+// profiles/r06_ab_notes.txt).  A group that does not fit is not an error: the site takes the form that does without — the same bits.
+
+// All of `reqs` (four at most), in order, or none of them.  On success the pointers are set, owned by the context and in c->d.
+// Otherwise *fits goes false and `msg`, a format with one %f for `gb`, says so.  `hook`: the tests' environment variable that
+// takes the fall-back without trying.  `retry_bytes`: a smaller size to try for the first block when the asked one is refused.
+// Returns the bytes of the first block, 0 for the fall-back.
+static size_t alloc_group_or_fall_back(dvp_ctx* c, std::initializer_list<AllocReq> reqs, const char* hook, bool* fits, const char* msg, double gb, size_t retry_bytes = 0) {
+	void* got[4] = { nullptr, nullptr, nullptr, nullptr };
+	const AllocReq* r = reqs.begin();
+	const size_t n = reqs.size();
+	size_t first = r[0].bytes;
+	bool ok = n <= 4 && !(hook && getenv(hook));
+	for (size_t i = 0; i < n && ok; ++i) {
+		if (!r[i].p) continue;
+		ok = hipMalloc(&got[i], r[i].bytes) == hipSuccess;
+		if (!ok && i == 0 && retry_bytes) { (void)hipGetLastError(); first = retry_bytes; ok = hipMalloc(&got[0], first) == hipSuccess; }
+		if (!ok) got[i] = nullptr;
+		else if (r[i].zero) ok = hipMemsetAsync(got[i], 0, r[i].bytes, c->stream) == hipSuccess;   // (never the block with a retry size)
+	}
+	if (!ok) {
+		(void)hipGetLastError();   // clear the sticky out-of-memory status
+		for (void* q : got) if (q) (void)hipFree(q);
+		*fits = false;
+		if (msg) fprintf(stderr, msg, gb);
+	}
+	else for (size_t i = 0; i < n; ++i) if (r[i].p) { *r[i].p = got[i]; c->allocs.push_back(got[i]); }
+	sync_dev_struct(c);   // (also after a refusal: the callers have freed the blocks they were replacing)
+	return ok ? first : 0;
+}
+
 // The pass' table of anchor reference sides (dvp_weak_wave.hpp: build_anchor_record) — built at the first weak update after
 // anything that can change the anchors (GenNeighbours, NeigbourUpdate), the offsets (GenEdgeInform), the images or the WEAK
-// list; the iterations of a pass then share it.  A table that does not fit is not an error: the kernels that form the
-// reference side per item give the same bits.
+// list; the iterations of a pass then share it.
 // room in the anchor table for `wc` WEAK pixels (grown with half as much again on top: the views of a level differ in their WEAK
 // counts, and every regrow is a device-wide free + a multi-GB allocation)
 static int grow_anchor_table(dvp_ctx* c, size_t wc) {
 	const size_t need = wc * (size_t)(c->NI - 1) * kAnchors;
-	if (c->anchor_tab_off || need <= c->anchor_tab_alloc) return 0;
-	{
-		HIP_TRY(c, hipStreamSynchronize(c->stream));
-		dfree(c, &c->anchor_tab);
-		c->anchor_tab_alloc = 0;
-		const size_t cap = need + need / 2;
-		void* q = nullptr;
-		size_t got = cap;
-		if (hipMalloc(&q, cap * sizeof(AnchorRec)) != hipSuccess) {
-			(void)hipGetLastError();
-			got = need;
-			if (hipMalloc(&q, need * sizeof(AnchorRec)) != hipSuccess) q = nullptr;
-		}
-		if (!q) {
-			(void)hipGetLastError();
-			c->anchor_tab_off = true;
-			sync_dev_struct(c);
-			fprintf(stderr, "dvp: no room for the weak update's anchor table (%.1f GB); forming the reference side per item\n", (double)need * sizeof(AnchorRec) / 1e9);
-			return 0;
-		}
-		c->allocs.push_back(q);
-		c->anchor_tab = (AnchorRec*)q;
-		c->anchor_tab_alloc = got;
-		sync_dev_struct(c);
-	}
+	if (anchor_table_off(c) || need <= c->anchor_tab_alloc) return 0;
+	HIP_TRY(c, hipStreamSynchronize(c->stream));
+	dfree(c, &c->anchor_tab);
+	c->anchor_tab_alloc = 0;
+	c->anchor_tab_alloc = alloc_group_or_fall_back(c, { areq(&c->anchor_tab, (need + need / 2) * sizeof(AnchorRec)) }, nullptr, &c->anchor_tab_fits,
+		"dvp: no room for the weak update's anchor table (%.1f GB); forming the reference side per item\n", (double)need * sizeof(AnchorRec) / 1e9,
+		need * sizeof(AnchorRec)) / sizeof(AnchorRec);
 	return 0;
 }
 static int ensure_anchor_table(dvp_ctx* c, int covered_rows) {
-	if (c->anchor_tab_off) return 0;
-	if (c->anchor_tab_valid) return 0;
+	if (anchor_table_off(c) || c->anchor_tab_valid) return 0;
 	const int wc = c->d.weak_black + c->d.weak_red;
-	const size_t need = (size_t)wc * (size_t)(c->NI - 1) * kAnchors;
 	if (grow_anchor_table(c, (size_t)wc)) return 1;
-	if (c->anchor_tab_off) return 0;
+	if (anchor_table_off(c)) return 0;
 	c->anchor_tab_valid = true;
 	sync_dev_struct(c);
 	ListArgs la;
 	la.base = 0; la.count = wc; la.iter = 0; la.covered_rows = covered_rows;
-	const long long n = (long long)need;
+	const long long n = (long long)wc * (c->NI - 1) * kAnchors;
 	if (n > 0) {
 		hipLaunchKernelGGL(dvp_weak_anchor_table, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, c->d, la);
 		HIP_TRY(c, hipGetLastError());
@@ -1877,41 +1858,32 @@ static int ensure_anchor_table(dvp_ctx* c, int covered_rows) {
 	return 0;
 }
 
-// hand-over buffers of the phased weak update (624 + 32 S bytes per WEAK pixel: 1.6 GB at 6208x4128 with 7 % WEAK, S = 9).  A
-// context that cannot have them keeps the one-wave kernel: the same bits.
-static int grow_weak_phase_buffers(dvp_ctx* c, size_t wc);
-static int ensure_weak_phase_buffers(dvp_ctx* c) { return grow_weak_phase_buffers(c, (size_t)(c->d.weak_black + c->d.weak_red)); }
+// hand-over buffers of the phased weak update (624 + 32 S bytes per WEAK pixel: 1.6 GB at 6208x4128 with 7 % WEAK, S = 9)
 static int grow_weak_phase_buffers(dvp_ctx* c, size_t wc) {
-	if (!c->weak_phased) return 0;
-	if (wc <= c->weak_phase_alloc) return 0;
+	if (!c->sw.weak_phased || !c->weak_phase_fits || wc <= c->weak_phase_alloc) return 0;
 	HIP_TRY(c, hipStreamSynchronize(c->stream));
 	dfree(c, &c->weak_rec); dfree(c, &c->weak_ctab); dfree(c, &c->weak_ev);
 	c->weak_phase_alloc = 0;
 	const size_t cap = std::min<size_t>(c->L, wc + wc / 2), S = (size_t)c->NI - 1;
-	void *r = nullptr, *t = nullptr, *e = nullptr;
-	if (getenv("DVP_TEST_WEAK_PHASE_ALLOC_FAIL") /* test hook: take the fallback */ || hipMalloc(&r, cap * sizeof(WeakRec)) != hipSuccess ||
-	    hipMalloc(&t, cap * kTaps * kTaps * sizeof(f2)) != hipSuccess || hipMalloc(&e, cap * 8 * S * sizeof(float)) != hipSuccess) {
-		(void)hipGetLastError();
-		if (r) (void)hipFree(r);
-		if (t) (void)hipFree(t);
-		c->weak_phased = false;
-		fprintf(stderr, "dvp: no room for the phased weak update's hand-over buffers (%.2f GB); using the one-wave kernel\n", (double)cap * (sizeof(WeakRec) + 288 + 32 * S) / 1e9);
-		sync_dev_struct(c);
-		return 0;
-	}
-	c->allocs.push_back(r); c->allocs.push_back(t); c->allocs.push_back(e);
-	c->weak_rec = (WeakRec*)r; c->weak_ctab = (f2*)t; c->weak_ev = (float*)e;
-	c->weak_phase_alloc = cap;
-	sync_dev_struct(c);
+	if (alloc_group_or_fall_back(c, { areq(&c->weak_rec, cap * sizeof(WeakRec)), areq(&c->weak_ctab, cap * kTaps * kTaps * sizeof(f2)), areq(&c->weak_ev, cap * 8 * S * sizeof(float)) },
+			"DVP_TEST_WEAK_PHASE_ALLOC_FAIL", &c->weak_phase_fits, "dvp: no room for the phased weak update's hand-over buffers (%.2f GB); using the one-wave kernel\n", (double)cap * (sizeof(WeakRec) + 288 + 32 * S) / 1e9))
+		c->weak_phase_alloc = cap;
 	return 0;
 }
 
-// The optional buffers of the split strong update and of the view-compacted sweep passes: allocated at the first launch that
-// wants them — or ahead of it by dvp_ctx_reserve, off the critical path (a multi-GB hipMalloc inside a launch site took 0.5-1 s
-// of a view on some boxes: profiles/r06_ab_notes.txt).  A context that cannot have them keeps the monolithic / fused kernels.
-static void ensure_strong_reuse_buffers(dvp_ctx* c);
+// The plane cache's records: 17 x S floats + 17 keys + a header per pixel of the whole image (15.7 + 7.0 + 0.4 GB at 6208x4128,
+// S = 9), in place of the half-size slot_costs (7.8 GB), which such a context never allocates.  A context that cannot have them
+// keeps slot_costs and evaluates every distinct plane at every visit.
+static void ensure_strong_reuse_buffers(dvp_ctx* c) {
+	if (c->reuse_costs || !c->sw.strong_reuse || !c->reuse_fits || strong_form(c->sw, c->NI - 1, c->split_fits, false, 0).kernel != STRONG_SPLIT) return;
+	const size_t L = c->L, vec = (size_t)kSlotCount * (c->NI - 1) * L * sizeof(float) + 64 /* load_slot_costs reads whole 16-byte pieces */;
+	const size_t Lh = (size_t)((c->W + 1) / 2) * c->H;
+	alloc_group_or_fall_back(c, { areq(&c->reuse_costs, vec), areq(&c->reuse_keys, L * kSlotCount * sizeof(PlaneKey)), areq(&c->reuse_hdr, L * sizeof(ReuseHdr), true),
+			c->strong_rec ? AllocReq{} : areq(&c->strong_rec, (size_t)SR_FIELDS * Lh * sizeof(*c->strong_rec)) },
+		"DVP_TEST_REUSE_ALLOC_FAIL", &c->reuse_fits, "dvp: no room for the strong update's plane cache (%.1f GB); every visit evaluates all its planes\n", (double)(vec + L * (kSlotCount * sizeof(PlaneKey) + sizeof(ReuseHdr))) / 1e9);
+}
 static void ensure_strong_split_buffers(dvp_ctx* c) {
-	if (c->slot_costs || !c->strong_split || c->NI - 1 > 16) return;
+	if (c->slot_costs || strong_form(c->sw, c->NI - 1, c->split_fits, false, 0).kernel != STRONG_SPLIT) return;
 	if (!getenv("DVP_TEST_SPLIT_ALLOC_FAIL")) {
 		ensure_strong_reuse_buffers(c);
 		if (c->reuse_costs) return;   // the full-size records stand in for slot_costs
@@ -1919,121 +1891,130 @@ static void ensure_strong_split_buffers(dvp_ctx* c) {
 	// 17 x S floats per pixel of one colour (7.8 GB at 6208x4128, S = 9): a part that cannot spare them runs the
 	// monolithic kernel instead, which gives the same bits (test_strong_update_forms_equal_the_oracle)
 	const size_t Lh = (size_t)((c->W + 1) / 2) * c->H;
-	void *sc = nullptr, *sr = nullptr;
-	if (getenv("DVP_TEST_SPLIT_ALLOC_FAIL") /* test hook: take the fallback */ || hipMalloc(&sc, (size_t)kSlotCount * (c->NI - 1) * Lh * sizeof(*c->slot_costs) + 64 /* load_slot_costs reads whole 16-byte pieces */) != hipSuccess || hipMalloc(&sr, (size_t)SR_FIELDS * Lh * sizeof(*c->strong_rec)) != hipSuccess) {
-		(void)hipGetLastError();   // clear the sticky out-of-memory status
-		if (sc) (void)hipFree(sc);
-		c->strong_split = false;
-		fprintf(stderr, "dvp: no room for the split strong update's cost buffer (%.1f GB); using the monolithic kernel\n", (double)kSlotCount * (c->NI - 1) * Lh * 4 / 1e9);
-	} else {
-		c->allocs.push_back(sc); c->allocs.push_back(sr);
-		c->slot_costs = (decltype(c->slot_costs))sc; c->strong_rec = (decltype(c->strong_rec))sr;
-		sync_dev_struct(c);
-	}
+	alloc_group_or_fall_back(c, { areq(&c->slot_costs, (size_t)kSlotCount * (c->NI - 1) * Lh * sizeof(*c->slot_costs) + 64 /* load_slot_costs reads whole 16-byte pieces */),
+			areq(&c->strong_rec, (size_t)SR_FIELDS * Lh * sizeof(*c->strong_rec)) },
+		"DVP_TEST_SPLIT_ALLOC_FAIL", &c->split_fits, "dvp: no room for the split strong update's cost buffer (%.1f GB); using the monolithic kernel\n", (double)kSlotCount * (c->NI - 1) * Lh * 4 / 1e9);
 }
-// The plane cache's records: 17 x S floats + 17 keys + a header per pixel of the whole image (15.7 + 7.0 + 0.4 GB at 6208x4128,
-// S = 9), in place of the half-size slot_costs (7.8 GB), which such a context never allocates.  A context that cannot have them
-// keeps slot_costs and evaluates every distinct plane at every visit.
-static void ensure_strong_reuse_buffers(dvp_ctx* c) {
-	if (c->reuse_costs || !c->strong_reuse || !c->strong_split || c->NI - 1 > 16) return;
-	const size_t L = c->L, vec = (size_t)kSlotCount * (c->NI - 1) * L * sizeof(float) + 64 /* load_slot_costs reads whole 16-byte pieces */;
-	void *rc = nullptr, *rk = nullptr, *rh = nullptr, *sr = nullptr;
-	const size_t Lh = (size_t)((c->W + 1) / 2) * c->H;
-	const bool need_rec = !c->strong_rec;
-	if (getenv("DVP_TEST_REUSE_ALLOC_FAIL") /* test hook: take the fallback */ || hipMalloc(&rc, vec) != hipSuccess || hipMalloc(&rk, L * kSlotCount * sizeof(PlaneKey)) != hipSuccess ||
-	    hipMalloc(&rh, L * sizeof(ReuseHdr)) != hipSuccess || (need_rec && hipMalloc(&sr, (size_t)SR_FIELDS * Lh * sizeof(*c->strong_rec)) != hipSuccess) ||
-	    hipMemsetAsync(rh, 0, L * sizeof(ReuseHdr), c->stream) != hipSuccess) {
-		(void)hipGetLastError();
-		for (void* q : { rc, rk, rh, sr }) if (q) (void)hipFree(q);
-		c->strong_reuse = false;
-		fprintf(stderr, "dvp: no room for the strong update's plane cache (%.1f GB); every visit evaluates all its planes\n", (double)(vec + L * (kSlotCount * sizeof(PlaneKey) + sizeof(ReuseHdr))) / 1e9);
-	} else {
-		for (void* q : { rc, rk, rh }) c->allocs.push_back(q);
-		c->reuse_costs = (float*)rc; c->reuse_keys = (PlaneKey*)rk; c->reuse_hdr = (ReuseHdr*)rh;
-		if (need_rec) { c->allocs.push_back(sr); c->strong_rec = (decltype(c->strong_rec))sr; }
-		sync_dev_struct(c);
-	}
-}
+// 73 floats per (pixel, view) + 61 + 8 per pixel (67 GB at 6208x4128, S = 9); the cost records of the whole image, or of a band of
+// rows when the context is told to keep them small (fresh device memory is 31-40 ms per GB on this part, tools/micro/alloc_time.hip:
+// 2.3 s for a 25-Mpx view's 67 GB)
 static void ensure_sweep_buffers(dvp_ctx* c) {
-	if (c->sweep_cost || !c->sweep_split) return;
-	// 73 floats per (pixel, view) + 61 + 8 per pixel (67 GB at 6208x4128, S = 9): a context that cannot have them keeps the fused kernel
+	if (c->sweep_cost || !c->sw.sweep_split || !c->sweep_fits) return;
 	const size_t L = c->L;
-	void *r = nullptr, *sc = nullptr, *pc = nullptr;
-	// the cost records of the whole image, or of a band of rows when the context is told to keep them small (fresh device memory is 31-40 ms
-	// per GB on this part, tools/micro/alloc_time.hip: 2.3 s for a 25-Mpx view's 67 GB)
-	size_t band_px = L;
-	c->sweep_band_rows = 0;
-	if (c->sweep_band_gb > 0.0) {
-		const double whole = (double)sweep_cost_floats(L, c->NI - 1) * sizeof(float);
-		const int bands = (int)std::ceil(whole / (c->sweep_band_gb * 1e9));
-		if (bands > 1) {
-			int rows = (c->H + bands - 1) / bands;
-			rows = (rows + kSweepRows - 1) / kSweepRows * kSweepRows;
-			if (rows < c->H) { c->sweep_band_rows = rows; band_px = (size_t)rows * c->W; }
-		}
-	}
-	if (getenv("DVP_TEST_SWEEP_ALLOC_FAIL") || hipMalloc(&r, 2 * L * sizeof(f4)) != hipSuccess || hipMalloc(&pc, 61 * L * sizeof(float)) != hipSuccess ||
-	    hipMalloc(&sc, sweep_cost_floats(band_px, c->NI - 1) * sizeof(float)) != hipSuccess) {
-		(void)hipGetLastError();
-		if (r) (void)hipFree(r);
-		if (pc) (void)hipFree(pc);
-		c->sweep_split = false;
-		fprintf(stderr, "dvp: no room for the view-compacted DepthToWeak's cost buffer (%.1f GB); using the fused kernel\n", (double)(c->NI - 1) * kSweepFields * L * 4 / 1e9);
-	} else {
-		c->allocs.push_back(r); c->allocs.push_back(sc); c->allocs.push_back(pc);
-		c->sweep_rec = (f4*)r; c->sweep_cost = (float*)sc; c->sweep_pc = (float*)pc;
-		sync_dev_struct(c);
-	}
+	c->sweep_band_rows = sweep_band_rows(c->sw, c->W, c->H, c->NI - 1);
+	const size_t band_px = c->sweep_band_rows > 0 ? (size_t)c->sweep_band_rows * c->W : L;
+	alloc_group_or_fall_back(c, { areq(&c->sweep_rec, 2 * L * sizeof(f4)), areq(&c->sweep_pc, 61 * L * sizeof(float)), areq(&c->sweep_cost, sweep_cost_floats(band_px, c->NI - 1) * sizeof(float)) },
+		"DVP_TEST_SWEEP_ALLOC_FAIL", &c->sweep_fits, "dvp: no room for the view-compacted DepthToWeak's cost buffer (%.1f GB); using the fused kernel\n", (double)(c->NI - 1) * kSweepFields * L * 4 / 1e9);
 }
 
-static int launch_stage(dvp_ctx* c, int stage, int iter, int colour, bool fused = false) {
-	if (stage < 0 || stage >= DVP_ST_LAUNCHABLE) { c->error = "bad stage id"; return 1; }
-	if (!c->sector_taps) { c->error = "dvp_set_params must be called before running kernels"; return 1; }
-	if (c->d.params.geom_consistency && !c->have_depths) { c->error = "geom_consistency is on but no depth maps were uploaded"; return 1; }
-	const LaunchGeom g = make_geom(c->W, c->H, stage_is_half(stage));
+// ---- launches ---------------------------------------------------------------------------------
+// Which kernels a launch site runs is decided by dvp_forms.hpp; the functions below issue them.
+// `fused` (dvp_run_patchmatch only): DepthToWeak does LocalRefine too; GenEdgeInform leaves the visibility-prior
+// candidates to dvp_run_patchmatch (side stream; not computed at all when the pass has no WEAK pixel: their only
+// reader is the weak update's anchor_cost)
+
+// the instantiation of kernel NAME for the context's sampler, and for the image format `fmt` of the set
+#define DVP_PICK(NAME, SUF) (c->d.sampler ? NAME##_exact##SUF : NAME##SUF)
+#define DVP_PICK_FMT(NAME, TAIL) (fmt == 1 ? DVP_PICK(NAME, _u8##TAIL) : (fmt == 2 ? DVP_PICK(NAME, _f16##TAIL) : DVP_PICK(NAME, TAIL)))
+
+static LaunchArgs make_args(const LaunchGeom& g, int colour, int iter) {
 	LaunchArgs a;
 	a.tiles_x = g.tiles_x; a.tiles = g.tiles; a.rows = g.rows; a.half = g.half ? 1 : 0;
 	a.colour = colour; a.iter = iter;
-	if (c->events.size() >= 2048 && dvp_get_timings(c, nullptr)) return 1;   // fold pending timings: bounds the event pool
-	if (stage != DVP_ST_STRONG_UPDATE && stage != DVP_ST_RANSAC_FIT && stage != DVP_ST_WEAK_UPDATE) c->anchor_tab_valid = false;   // anchors / offsets / WEAK states may change: the next weak update rebuilds its table
-	if (stage == DVP_ST_STRONG_UPDATE) {
-		// pre-launch snapshot: the direction-4 samples of the strong update are same-colour pixels
-		// (APD.cu:2071-2074); every neighbour read of that kernel sees the state before the launch.
-		// Then the light sample-search launch.  Both are timed in their own bucket (DVP_ST_STRONG_PREP)
-		// so that stage_ms[DVP_ST_STRONG_UPDATE] is the update kernel alone.
-		EventPair prep;
-		prep.stage = DVP_ST_STRONG_PREP;
-		HIP_TRY(c, hipEventCreate(&prep.a));
-		HIP_TRY(c, hipEventCreate(&prep.b));
-		HIP_TRY(c, hipEventRecord(prep.a, c->stream));
-		HIP_TRY(c, hipMemcpyAsync(c->planes_snap, c->planes, c->L * 16, hipMemcpyDeviceToDevice, c->stream));
-		HIP_TRY(c, hipMemcpyAsync(c->costs_snap, c->costs, c->L * 4, hipMemcpyDeviceToDevice, c->stream));
-		if (c->strong_split && c->NI - 1 <= 16) ensure_strong_split_buffers(c);   // (before the first launch that takes c->d)
-		hipLaunchKernelGGL(dvp_strong_search, dim3(g.grid()), dim3(256), 0, c->stream, c->d, a);
-		if (c->strong_split && c->NI - 1 <= 16 && c->d.reuse_hdr) hipLaunchKernelGGL(dvp_strong_plan, dim3(g.grid()), dim3(256), 0, c->stream, c->d, a);
-		HIP_TRY(c, hipGetLastError());
-		HIP_TRY(c, hipEventRecord(prep.b, c->stream));
-		c->events.push_back(prep);
-	}
-	EventPair ep;
-	ep.stage = stage;
-	HIP_TRY(c, hipEventCreate(&ep.a));
-	HIP_TRY(c, hipEventCreate(&ep.b));
-	if (c->profiling) HIP_TRY(c, hipMemsetAsync(c->eval_counter, 0, 8, c->stream));
-	HIP_TRY(c, hipEventRecord(ep.a, c->stream));
+	return a;
+}
+
+// the visibility-prior candidates of `blocks` x 256 pixels of the image (a) or of the pixel list, with the state `d` sees
+static void launch_gen_candidates(dvp_ctx* c, hipStream_t stream, const Dev& d, unsigned blocks, const LaunchArgs& a, const unsigned* list = nullptr, const unsigned* n_list = nullptr) {
+	const bool all = gen_candidates_all_views(d);
+	const dim3 grid(blocks, all ? (unsigned)((c->NI - 1 + kCandGroup - 1) / kCandGroup) : (unsigned)(c->NI - 1)), block(256);
+	if (list) hipLaunchKernelGGL(all ? dvp_gen_candidates_views_list : dvp_gen_candidates_list, grid, block, 0, stream, d, list, n_list);
+	else hipLaunchKernelGGL(all ? dvp_gen_candidates_views : dvp_gen_candidates, grid, block, 0, stream, d, a);
+}
+
+// pre-launch snapshot: the direction-4 samples of the strong update are same-colour pixels
+// (APD.cu:2071-2074); every neighbour read of that kernel sees the state before the launch.
+// Then the light sample-search launch.  Both are timed in their own bucket (DVP_ST_STRONG_PREP)
+// so that stage_ms[DVP_ST_STRONG_UPDATE] is the update kernel alone.
+static int launch_strong_prep(dvp_ctx* c, const LaunchGeom& g, const LaunchArgs& a) {
+	EventPair prep;
+	prep.stage = DVP_ST_STRONG_PREP;
+	HIP_TRY(c, hipEventCreate(&prep.a));
+	HIP_TRY(c, hipEventCreate(&prep.b));
+	HIP_TRY(c, hipEventRecord(prep.a, c->stream));
+	HIP_TRY(c, hipMemcpyAsync(c->planes_snap, c->planes, c->L * 16, hipMemcpyDeviceToDevice, c->stream));
+	HIP_TRY(c, hipMemcpyAsync(c->costs_snap, c->costs, c->L * 4, hipMemcpyDeviceToDevice, c->stream));
+	ensure_strong_split_buffers(c);   // (before the first launch that takes c->d)
+	hipLaunchKernelGGL(dvp_strong_search, dim3(g.grid()), dim3(256), 0, c->stream, c->d, a);
+	if (strong_form(c->sw, c->NI - 1, c->split_fits, c->d.reuse_hdr != nullptr, 0).plan) hipLaunchKernelGGL(dvp_strong_plan, dim3(g.grid()), dim3(256), 0, c->stream, c->d, a);
+	HIP_TRY(c, hipGetLastError());
+	HIP_TRY(c, hipEventRecord(prep.b, c->stream));
+	c->events.push_back(prep);
+	return 0;
+}
+
+static int launch_strong_update(dvp_ctx* c, const LaunchGeom& g, const LaunchArgs& a) {
 	const dim3 grid(g.grid()), block(256);
 	const dim3 wave_grid((unsigned)((g.grid() + 7) / 8 * 32)), wave_block(64);   // DVP_KERNEL64 launch sites: four one-wave workgroups per tile
-	const bool list_stage = stage == DVP_ST_FIND_NEAREST_STRONG || stage == DVP_ST_GEN_NEIGHBOURS || stage == DVP_ST_NEIGHBOUR_UPDATE ||
-	                        stage == DVP_ST_RANSAC_FIT || stage == DVP_ST_WEAK_UPDATE;
+	ensure_strong_split_buffers(c);
+	const StrongForm f = strong_form(c->sw, c->NI - 1, c->split_fits, c->d.reuse_hdr != nullptr, (unsigned long long)c->pitch * (c->H + 2 * kImgPad) * 8 * c->NI);
+	switch (f.kernel) {
+	case STRONG_SPLIT:
+		if (f.eval_items) hipLaunchKernelGGL(DVP_PICK(dvp_strong_eval_items, ), wave_grid, wave_block, 0, c->stream, c->d, a);
+		else hipLaunchKernelGGL(DVP_PICK(dvp_strong_eval, ), wave_grid, wave_block, 0, c->stream, c->d, a);
+		hipLaunchKernelGGL(f.decide == 4 ? dvp_strong_decide_v4 : f.decide == 6 ? dvp_strong_decide_v6 : f.decide == 8 ? dvp_strong_decide_v8 : f.decide == 10 ? dvp_strong_decide_v10 :
+		                   f.decide == 12 ? dvp_strong_decide_v12 : dvp_strong_decide_v16, grid, block, 0, c->stream, c->d, a);
+		// lanes: every lane on its own (hypothesis, view) sequence; the lanes' image planes are 32-bit byte offsets from the set's base
+		if (f.refine_lanes) hipLaunchKernelGGL(DVP_PICK(dvp_strong_refine_lanes, ), wave_grid, wave_block, 0, c->stream, c->d, a);
+		else hipLaunchKernelGGL(DVP_PICK(dvp_strong_refine, ), wave_grid, wave_block, 0, c->stream, c->d, a);
+		break;
+	case STRONG_MONO_V8: hipLaunchKernelGGL(DVP_PICK(dvp_strong_update_v8, ), grid, block, 0, c->stream, c->d, a); break;
+	case STRONG_MONO_V16: hipLaunchKernelGGL(DVP_PICK(dvp_strong_update_v16, ), grid, block, 0, c->stream, c->d, a); break;
+	case STRONG_MONO: hipLaunchKernelGGL(DVP_PICK(dvp_strong_update, ), grid, block, 0, c->stream, c->d, a); break;
+	}
+	HIP_TRY(c, hipGetLastError());
+	return 0;
+}
+
+static int launch_weak_update(dvp_ctx* c, ListArgs la) {
+	if (ensure_anchor_table(c, la.covered_rows)) return 1;
+	if (c->d.anchor_tab && grow_weak_phase_buffers(c, (size_t)(c->d.weak_black + c->d.weak_red))) return 1;
+	const WeakForm f = weak_form(c->sw, c->d.anchor_tab != nullptr, c->weak_phase_fits, la.count);
+	const int fmt = dvp_image_format(c);
+	const dim3 lg((la.count + 255) / 256), block(256), w64(64), lg64((la.count + 63) / 64);
+	switch (f.kernel) {
+	case WEAK_PHASED:
+#define DVP_GROUP_LAUNCH(NAME, PHASE) { la.group = f.group[PHASE]; la.run = f.run[PHASE]; hipLaunchKernelGGL(DVP_PICK_FMT(NAME, ), dim3((la.count + la.group - 1) / la.group), w64, 0, c->stream, c->d, la); }
+		DVP_GROUP_LAUNCH(dvp_weak_eval_candidates, 0)
+		hipLaunchKernelGGL(dvp_weak_select_views, lg, block, 0, c->stream, c->d, la);
+		DVP_GROUP_LAUNCH(dvp_weak_eval_planes, 1)
+		hipLaunchKernelGGL(dvp_weak_make_hypotheses, lg, block, 0, c->stream, c->d, la);
+		DVP_GROUP_LAUNCH(dvp_weak_eval_first_view, 2)
+		DVP_GROUP_LAUNCH(dvp_weak_eval_survivors, 3)
+#undef DVP_GROUP_LAUNCH
+		hipLaunchKernelGGL(dvp_weak_adopt, lg, block, 0, c->stream, c->d, la);
+		hipLaunchKernelGGL(DVP_PICK(dvp_weak_final_cost, ), lg64, w64, 0, c->stream, c->d, la);
+		break;
+	case WEAK_WAVE: hipLaunchKernelGGL(DVP_PICK_FMT(dvp_weak_update_wave, ), dim3(la.count), w64, 0, c->stream, c->d, la); break;
+	case WEAK_WAVE_NOTAB: hipLaunchKernelGGL(DVP_PICK_FMT(dvp_weak_update_wave, _notab), dim3(la.count), w64, 0, c->stream, c->d, la); break;
+	}
+	return 0;
+}
+
+// weak-path launch sites: lane-per-WEAK-pixel.  Non-WEAK pixels' outputs of these kernels are
+// constants / copies and are produced by plain fills: weak_nearest_strong = (-1,-1)
+// (APD.cu:4169-4173), fit plane = plane (APD.cu:4208-4211).
+static int launch_list_site(dvp_ctx* c, int stage, int iter, int colour) {
+	const dim3 block(256);
+	const size_t words = edge_bits_words(c->W, c->H);
+	const dim3 wgrid((unsigned)((words + 255) / 256));
 	if (stage == DVP_ST_FIND_NEAREST_STRONG && c->d.weak_black + c->d.weak_red > 0) {   // its ring search reads row and column segments of the STRONG map
-		const size_t words = edge_bits_words(c->W, c->H);
-		hipLaunchKernelGGL(dvp_pack_edge_bits, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, c->stream, c->weak_info, c->strong_bits, c->W, c->H, edge_tiles_x(c->W), words, (int)DVP_STRONG);
-		hipLaunchKernelGGL(dvp_pack_bits_transposed, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, c->stream, c->weak_info, c->strong_bits_t, c->W, c->H, edge_tiles_x(c->W), words, (int)DVP_STRONG);
+		hipLaunchKernelGGL(dvp_pack_edge_bits, wgrid, block, 0, c->stream, c->weak_info, c->strong_bits, c->W, c->H, edge_tiles_x(c->W), words, (int)DVP_STRONG);
+		hipLaunchKernelGGL(dvp_pack_bits_transposed, wgrid, block, 0, c->stream, c->weak_info, c->strong_bits_t, c->W, c->H, edge_tiles_x(c->W), words, (int)DVP_STRONG);
 		HIP_TRY(c, hipGetLastError());
 	}
 	if (stage == DVP_ST_GEN_NEIGHBOURS || stage == DVP_ST_RANSAC_FIT) {   // the launch sites that walk lines over the edge map
-		const size_t words = edge_bits_words(c->W, c->H);
-		hipLaunchKernelGGL(dvp_pack_edge_bits, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, c->stream, c->edge, c->edge_bits, c->W, c->H, edge_tiles_x(c->W), words, -1);
+		hipLaunchKernelGGL(dvp_pack_edge_bits, wgrid, block, 0, c->stream, c->edge, c->edge_bits, c->W, c->H, edge_tiles_x(c->W), words, -1);
 		HIP_TRY(c, hipGetLastError());
 		const int cells = c->d.sat_cells_x * c->d.sat_cells_y;
 		hipLaunchKernelGGL(dvp_edge_cell_counts, dim3((cells + 255) / 256), dim3(256), 0, c->stream, c->d);
@@ -2041,70 +2022,87 @@ static int launch_stage(dvp_ctx* c, int stage, int iter, int colour, bool fused 
 		hipLaunchKernelGGL(dvp_edge_sat_cols, dim3((c->d.sat_cells_x + 1 + 63) / 64), dim3(64), 0, c->stream, c->d);
 		HIP_TRY(c, hipGetLastError());
 		if (stage == DVP_ST_GEN_NEIGHBOURS) {   // its anchor search probes "is this pixel STRONG" all over the image
-			hipLaunchKernelGGL(dvp_pack_edge_bits, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, c->stream, c->weak_info, c->strong_bits, c->W, c->H, edge_tiles_x(c->W), words, (int)DVP_STRONG);
+			hipLaunchKernelGGL(dvp_pack_edge_bits, wgrid, block, 0, c->stream, c->weak_info, c->strong_bits, c->W, c->H, edge_tiles_x(c->W), words, (int)DVP_STRONG);
 			HIP_TRY(c, hipGetLastError());
 		}
 	}
-	if (list_stage) {
-		// weak-path launch sites: lane-per-WEAK-pixel.  Non-WEAK pixels' outputs of these kernels are
-		// constants / copies and are produced by plain fills: weak_nearest_strong = (-1,-1)
-		// (APD.cu:4169-4173), fit plane = plane (APD.cu:4208-4211).
-		if (stage == DVP_ST_FIND_NEAREST_STRONG) HIP_TRY(c, hipMemsetAsync(c->weak_nearest_strong, 0xFF, c->L * sizeof(s2), c->stream));
-		if (stage == DVP_ST_RANSAC_FIT) HIP_TRY(c, hipMemcpyAsync(c->fit_planes, c->planes, c->L * 16, hipMemcpyDeviceToDevice, c->stream));
-		ListArgs la;
-		la.iter = iter;
-		la.covered_rows = 2 * make_geom(c->W, c->H, true).rows;
-		la.base = (stage == DVP_ST_WEAK_UPDATE && colour == 1) ? c->d.weak_black : 0;
-		la.count = (stage == DVP_ST_WEAK_UPDATE) ? (colour == 0 ? c->d.weak_black : (colour == 1 ? c->d.weak_red : c->d.weak_black + c->d.weak_red)) : c->d.weak_black + c->d.weak_red;   // colour 2 (dvp_run_patchmatch): both colours of the weak update in one launch site
-		if (la.count > 0) {
-			const dim3 lg((la.count + 255) / 256);
-			const bool ex = c->d.sampler != 0;
-			switch (stage) {
-			case DVP_ST_FIND_NEAREST_STRONG: hipLaunchKernelGGL(ex ? dvp_find_nearest_strong_list_exact : dvp_find_nearest_strong_list, lg, block, 0, c->stream, c->d, la); break;
-			case DVP_ST_GEN_NEIGHBOURS:
-				if (c->gn_wave) hipLaunchKernelGGL(dvp_gen_neighbours_search, dim3((la.count + 3) / 4), block, 0, c->stream, c->d, la);
-				else hipLaunchKernelGGL(dvp_gen_neighbours_list, lg, block, 0, c->stream, c->d, la);
-				hipLaunchKernelGGL(dvp_gen_neighbours_fit, dim3(la.count), dim3(64), 0, c->stream, c->d, la);
-				break;
-			case DVP_ST_NEIGHBOUR_UPDATE: hipLaunchKernelGGL(ex ? dvp_neighbour_update_list_exact : dvp_neighbour_update_list, lg, block, 0, c->stream, c->d, la); break;
-			case DVP_ST_RANSAC_FIT:
-				if (c->ransac_wave) hipLaunchKernelGGL(dvp_ransac_fit_plane_wave, dim3(la.count), dim3(64), 0, c->stream, c->d, la);
-				else hipLaunchKernelGGL(ex ? dvp_ransac_fit_plane_list_exact : dvp_ransac_fit_plane_list, lg, block, 0, c->stream, c->d, la);
-				break;
-			case DVP_ST_WEAK_UPDATE:
-				if (ensure_anchor_table(c, la.covered_rows)) return 1;
-				if (c->d.anchor_tab && ensure_weak_phase_buffers(c)) return 1;
-				// (a few thousand WEAK pixels do not fill the machine in any form: the eight launches then cost more than they save —
-				// 4.4 against 1.7 ms for the weak updates of a 3104x2064 view with 0.2 % WEAK pixels — and the one-wave kernel takes them)
-				if (c->d.anchor_tab && c->weak_phased && (la.count >= c->weak_phased_min || c->weak_phased_min <= 0)) {
-					const int fmt = dvp_image_format(c);
-					const dim3 w64(64), lg64((la.count + 63) / 64);
-#define DVP_PICK(NAME) (ex ? (fmt == 1 ? NAME##_exact_u8 : (fmt == 2 ? NAME##_exact_f16 : NAME##_exact)) : (fmt == 1 ? NAME##_u8 : (fmt == 2 ? NAME##_f16 : NAME)))
-#define DVP_GROUP_LAUNCH(NAME, PHASE) { la.group = std::min(c->weak_group[PHASE], PHASE == 0 ? kGrpWide : kGrp); la.run = c->weak_run[PHASE]; hipLaunchKernelGGL(DVP_PICK(NAME), dim3((la.count + la.group - 1) / la.group), w64, 0, c->stream, c->d, la); }
-					DVP_GROUP_LAUNCH(dvp_weak_eval_candidates, 0)
-					hipLaunchKernelGGL(dvp_weak_select_views, lg, block, 0, c->stream, c->d, la);
-					DVP_GROUP_LAUNCH(dvp_weak_eval_planes, 1)
-					hipLaunchKernelGGL(dvp_weak_make_hypotheses, lg, block, 0, c->stream, c->d, la);
-					DVP_GROUP_LAUNCH(dvp_weak_eval_first_view, 2)
-					DVP_GROUP_LAUNCH(dvp_weak_eval_survivors, 3)
-#undef DVP_GROUP_LAUNCH
-					hipLaunchKernelGGL(dvp_weak_adopt, lg, block, 0, c->stream, c->d, la);
-					hipLaunchKernelGGL(ex ? dvp_weak_final_cost_exact : dvp_weak_final_cost, lg64, w64, 0, c->stream, c->d, la);
-#undef DVP_PICK
-				} else if (c->d.anchor_tab) {
-					if (c->images8_ok) hipLaunchKernelGGL(ex ? dvp_weak_update_wave_exact_u8 : dvp_weak_update_wave_u8, dim3(la.count), dim3(64), 0, c->stream, c->d, la);
-					else if (c->images16_ok) hipLaunchKernelGGL(ex ? dvp_weak_update_wave_exact_f16 : dvp_weak_update_wave_f16, dim3(la.count), dim3(64), 0, c->stream, c->d, la);
-					else hipLaunchKernelGGL(ex ? dvp_weak_update_wave_exact : dvp_weak_update_wave, dim3(la.count), dim3(64), 0, c->stream, c->d, la);
-				} else {
-					if (c->images8_ok) hipLaunchKernelGGL(ex ? dvp_weak_update_wave_exact_u8_notab : dvp_weak_update_wave_u8_notab, dim3(la.count), dim3(64), 0, c->stream, c->d, la);
-					else if (c->images16_ok) hipLaunchKernelGGL(ex ? dvp_weak_update_wave_exact_f16_notab : dvp_weak_update_wave_f16_notab, dim3(la.count), dim3(64), 0, c->stream, c->d, la);
-					else hipLaunchKernelGGL(ex ? dvp_weak_update_wave_exact_notab : dvp_weak_update_wave_notab, dim3(la.count), dim3(64), 0, c->stream, c->d, la);
-				}
-				break;
+	if (stage == DVP_ST_FIND_NEAREST_STRONG) HIP_TRY(c, hipMemsetAsync(c->weak_nearest_strong, 0xFF, c->L * sizeof(s2), c->stream));
+	if (stage == DVP_ST_RANSAC_FIT) HIP_TRY(c, hipMemcpyAsync(c->fit_planes, c->planes, c->L * 16, hipMemcpyDeviceToDevice, c->stream));
+	ListArgs la;
+	la.iter = iter;
+	la.covered_rows = 2 * make_geom(c->W, c->H, true).rows;
+	la.base = (stage == DVP_ST_WEAK_UPDATE && colour == 1) ? c->d.weak_black : 0;
+	la.count = (stage == DVP_ST_WEAK_UPDATE) ? (colour == 0 ? c->d.weak_black : (colour == 1 ? c->d.weak_red : c->d.weak_black + c->d.weak_red)) : c->d.weak_black + c->d.weak_red;   // colour 2 (dvp_run_patchmatch): both colours of the weak update in one launch site
+	if (la.count <= 0) return 0;
+	const dim3 lg((la.count + 255) / 256);
+	switch (stage) {
+	case DVP_ST_FIND_NEAREST_STRONG: hipLaunchKernelGGL(DVP_PICK(dvp_find_nearest_strong_list, ), lg, block, 0, c->stream, c->d, la); break;
+	case DVP_ST_GEN_NEIGHBOURS:
+		if (c->sw.gn_wave) hipLaunchKernelGGL(dvp_gen_neighbours_search, dim3((la.count + 3) / 4), block, 0, c->stream, c->d, la);
+		else hipLaunchKernelGGL(dvp_gen_neighbours_list, lg, block, 0, c->stream, c->d, la);
+		hipLaunchKernelGGL(dvp_gen_neighbours_fit, dim3(la.count), dim3(64), 0, c->stream, c->d, la);
+		break;
+	case DVP_ST_NEIGHBOUR_UPDATE: hipLaunchKernelGGL(DVP_PICK(dvp_neighbour_update_list, ), lg, block, 0, c->stream, c->d, la); break;
+	case DVP_ST_RANSAC_FIT:
+		if (c->sw.ransac_wave) hipLaunchKernelGGL(dvp_ransac_fit_plane_wave, dim3(la.count), dim3(64), 0, c->stream, c->d, la);
+		else hipLaunchKernelGGL(DVP_PICK(dvp_ransac_fit_plane_list, ), lg, block, 0, c->stream, c->d, la);
+		break;
+	case DVP_ST_WEAK_UPDATE:
+		if (launch_weak_update(c, la)) return 1;
+		break;
+	}
+	HIP_TRY(c, hipGetLastError());
+	return 0;
+}
+
+// DepthToWeak, with LocalRefine when `fused`: the two separate kernels, the fused one, or the view-compacted passes
+static int launch_sweeps(dvp_ctx* c, const LaunchGeom& g, const LaunchArgs& a, bool fused) {
+	const dim3 grid(g.grid()), block(256);
+	if (sweep_form(c->sw, fused, c->d.params, c->sweep_fits, c->W, c->H).kernel == SWEEP_PASSES) ensure_sweep_buffers(c);
+	const SweepForm f = sweep_form(c->sw, fused, c->d.params, c->sweep_fits, c->W, c->H);
+	if (f.kernel == SWEEP_PASSES) {
+		LaunchArgs s0 = a, s1 = a, sb = a;
+		s0.iter = 0; s1.iter = 1; sb.iter = kSweepBorderOnly;
+		const int etx = (c->W + 63) / 64, ety = (c->H + kSweepRows - 1) / kSweepRows;
+		s0.tiles_x = s1.tiles_x = etx; s0.tiles = s1.tiles = etx * ety;
+		const dim3 egrid((unsigned)(etx * ety), (unsigned)(c->NI - 1));
+		hipLaunchKernelGGL(dvp_sweep_prepare, grid, block, 0, c->stream, c->d, a);
+		// evaluate / decide / evaluate / decide over the whole image, or band of rows after band of rows through the one band-sized
+		// cost buffer (every pass is per pixel: same bits)
+		const int band_rows = c->sweep_band_rows > 0 ? c->sweep_band_rows : c->H;
+		for (int row0 = 0; row0 < c->H; row0 += band_rows) {
+			Dev db = c->d;
+			LaunchArgs b0 = s0, b1 = s1;
+			dim3 bgrid = egrid;
+			b0.rows = b1.rows = 0;
+			if (c->sweep_band_rows > 0) {
+				const int row1 = std::min(c->H, row0 + band_rows);
+				db.sweep_px0 = row0 * c->W; db.sweep_row0 = row0; db.sweep_row1 = row1;
+				const int bty = (row1 - row0 + kSweepRows - 1) / kSweepRows;
+				b0.rows = b1.rows = row0 / kSweepRows;
+				b0.tiles = b1.tiles = etx * bty;
+				bgrid = dim3((unsigned)(etx * bty), (unsigned)(c->NI - 1));
 			}
-			HIP_TRY(c, hipGetLastError());
+			hipLaunchKernelGGL(DVP_PICK(dvp_sweep_eval, ), bgrid, dim3(64), 0, c->stream, db, b0);
+			hipLaunchKernelGGL(dvp_sweep_decide1, grid, block, 0, c->stream, db, a);
+			if (f.second_eval) hipLaunchKernelGGL(DVP_PICK(dvp_sweep_eval, ), bgrid, dim3(64), 0, c->stream, db, b1);
+			hipLaunchKernelGGL(dvp_sweep_decide2, grid, block, 0, c->stream, db, a);
 		}
-	} else {
+		if (f.border_kernel) {
+			const long long frame = 12ll * c->W + 12ll * (c->H - 12);
+			hipLaunchKernelGGL(DVP_PICK(dvp_sweep_border, ), dim3((unsigned)((frame + 63) / 64)), dim3(64), 0, c->stream, c->d, sb);
+		}
+		else hipLaunchKernelGGL(DVP_PICK(dvp_depth_to_weak_refine, ), grid, block, 0, c->stream, c->d, sb);
+	}
+	else if (f.kernel == SWEEP_FUSED) hipLaunchKernelGGL(DVP_PICK(dvp_depth_to_weak_refine, ), grid, block, 0, c->stream, c->d, a);
+	else hipLaunchKernelGGL(DVP_PICK(dvp_depth_to_weak, ), grid, block, 0, c->stream, c->d, a);
+	HIP_TRY(c, hipGetLastError());
+	return 0;
+}
+
+// the launch sites of one kernel over the image's pixels
+static int launch_pixel_site(dvp_ctx* c, int stage, const LaunchGeom& g, const LaunchArgs& a, bool fused) {
+	const dim3 grid(g.grid()), block(256);
 	if (stage == DVP_ST_GEN_EDGE_INFORM && c->d.params.use_edge) {
 		hipLaunchKernelGGL(dvp_edge_rays, dim3((c->W + c->H + 255) / 256, 8), dim3(256), 0, c->stream, c->d, 0);
 		HIP_TRY(c, hipGetLastError());
@@ -2119,88 +2117,42 @@ static int launch_stage(dvp_ctx* c, int stage, int iter, int colour, bool fused 
 	}
 	switch (stage) {
 	case DVP_ST_GEN_EDGE_INFORM:
-		if (!fused) {   // fused: dvp_run_patchmatch issued them on the side stream
-			if (gen_candidates_all_views(c->d)) hipLaunchKernelGGL(dvp_gen_candidates_views, dim3(g.grid(), (unsigned)((c->NI - 1 + kCandGroup - 1) / kCandGroup)), block, 0, c->stream, c->d, a);
-			else hipLaunchKernelGGL(dvp_gen_candidates, dim3(g.grid(), (unsigned)(c->NI - 1)), block, 0, c->stream, c->d, a);
-		}
-		hipLaunchKernelGGL(c->d.sampler ? dvp_gen_edge_inform_exact : dvp_gen_edge_inform, grid, block, 0, c->stream, c->d, a);
+		if (!fused) launch_gen_candidates(c, c->stream, c->d, g.grid(), a);   // fused: dvp_run_patchmatch issued them on the side stream
+		hipLaunchKernelGGL(DVP_PICK(dvp_gen_edge_inform, ), grid, block, 0, c->stream, c->d, a);
 		break;
-	case DVP_ST_RANDOM_INIT: hipLaunchKernelGGL(c->d.sampler ? dvp_random_init_exact : dvp_random_init, grid, block, 0, c->stream, c->d, a); break;
-	case DVP_ST_STRONG_UPDATE:
-		if (c->strong_split && c->NI - 1 <= 16) {
-			ensure_strong_split_buffers(c);
-		}
-		if (c->strong_split && c->NI - 1 <= 16) {
-			const int S = c->NI - 1;
-			if (c->eval_items) hipLaunchKernelGGL(c->d.sampler ? dvp_strong_eval_items_exact : dvp_strong_eval_items, wave_grid, wave_block, 0, c->stream, c->d, a);
-			else hipLaunchKernelGGL(c->d.sampler ? dvp_strong_eval_exact : dvp_strong_eval, wave_grid, wave_block, 0, c->stream, c->d, a);
-			if (S <= 4) hipLaunchKernelGGL(dvp_strong_decide_v4, grid, block, 0, c->stream, c->d, a);
-			else if (S <= 6) hipLaunchKernelGGL(dvp_strong_decide_v6, grid, block, 0, c->stream, c->d, a);
-			else if (S <= 8) hipLaunchKernelGGL(dvp_strong_decide_v8, grid, block, 0, c->stream, c->d, a);
-			else if (S <= 10) hipLaunchKernelGGL(dvp_strong_decide_v10, grid, block, 0, c->stream, c->d, a);
-			else if (S <= 12) hipLaunchKernelGGL(dvp_strong_decide_v12, grid, block, 0, c->stream, c->d, a);
-			else hipLaunchKernelGGL(dvp_strong_decide_v16, grid, block, 0, c->stream, c->d, a);
-			// every lane on its own (hypothesis, view) sequence; the lanes' image planes are 32-bit byte offsets from the set's base
-			if (c->refine_lanes && (size_t)c->pitch * (c->H + 2 * kImgPad) * 8 * c->NI < ((size_t)1 << 32))
-				hipLaunchKernelGGL(c->d.sampler ? dvp_strong_refine_lanes_exact : dvp_strong_refine_lanes, wave_grid, wave_block, 0, c->stream, c->d, a);
-			else hipLaunchKernelGGL(c->d.sampler ? dvp_strong_refine_exact : dvp_strong_refine, wave_grid, wave_block, 0, c->stream, c->d, a);
-		}
-		else if (c->NI - 1 <= kNarrowViews) hipLaunchKernelGGL(c->d.sampler ? dvp_strong_update_v8_exact : dvp_strong_update_v8, grid, block, 0, c->stream, c->d, a);
-		else if (c->NI - 1 <= 16) hipLaunchKernelGGL(c->d.sampler ? dvp_strong_update_v16_exact : dvp_strong_update_v16, grid, block, 0, c->stream, c->d, a);
-		else hipLaunchKernelGGL(c->d.sampler ? dvp_strong_update_exact : dvp_strong_update, grid, block, 0, c->stream, c->d, a);
-		break;
-	case DVP_ST_GET_DEPTH_NORMAL: hipLaunchKernelGGL(c->d.sampler ? dvp_get_depth_normal_exact : dvp_get_depth_normal, grid, block, 0, c->stream, c->d, a); break;
-	case DVP_ST_FILTER_STRONG: hipLaunchKernelGGL(c->d.sampler ? dvp_filter_strong_exact : dvp_filter_strong, grid, block, 0, c->stream, c->d, a); break;
-	case DVP_ST_DEPTH_TO_WEAK: {
-		// the passes pay where the views diverge and the geometric term rides along (cfg3: 622 -> 536 ms, cfg5: 48 -> 44); a pass
-		// without the geometric term (FIRST_INIT; cfg2, S = 5) measures 63 ms against the fused kernel's 59: DVP_SWEEP_SPLIT=2 forces the passes there too
-		const bool sweep_passes = fused && c->sweep_split && (c->d.params.geom_consistency || c->sweep_force);
-		if (sweep_passes) ensure_sweep_buffers(c);
-		if (sweep_passes && c->sweep_split) {
-			const bool ex = c->d.sampler != 0;
-			LaunchArgs s0 = a, s1 = a, sb = a;
-			s0.iter = 0; s1.iter = 1; sb.iter = kSweepBorderOnly;
-			const int etx = (c->W + 63) / 64, ety = (c->H + kSweepRows - 1) / kSweepRows;
-			s0.tiles_x = s1.tiles_x = etx; s0.tiles = s1.tiles = etx * ety;
-			const dim3 egrid((unsigned)(etx * ety), (unsigned)(c->NI - 1));
-			hipLaunchKernelGGL(dvp_sweep_prepare, grid, block, 0, c->stream, c->d, a);
-			// evaluate / decide / evaluate / decide over the whole image, or band of rows after band of rows through the one band-sized
-			// cost buffer (every pass is per pixel: same bits)
-			const int band_rows = c->sweep_band_rows > 0 ? c->sweep_band_rows : c->H;
-			for (int row0 = 0; row0 < c->H; row0 += band_rows) {
-				Dev db = c->d;
-				LaunchArgs b0 = s0, b1 = s1;
-				dim3 bgrid = egrid;
-				b0.rows = b1.rows = 0;
-				if (c->sweep_band_rows > 0) {
-					const int row1 = std::min(c->H, row0 + band_rows);
-					db.sweep_px0 = row0 * c->W; db.sweep_row0 = row0; db.sweep_row1 = row1;
-					const int bty = (row1 - row0 + kSweepRows - 1) / kSweepRows;
-					b0.rows = b1.rows = row0 / kSweepRows;
-					b0.tiles = b1.tiles = etx * bty;
-					bgrid = dim3((unsigned)(etx * bty), (unsigned)(c->NI - 1));
-				}
-				hipLaunchKernelGGL(ex ? dvp_sweep_eval_exact : dvp_sweep_eval, bgrid, dim3(64), 0, c->stream, db, b0);
-				hipLaunchKernelGGL(dvp_sweep_decide1, grid, block, 0, c->stream, db, a);
-				if (sweep_window(c->d.params) < 30) {
-					hipLaunchKernelGGL(ex ? dvp_sweep_eval_exact : dvp_sweep_eval, bgrid, dim3(64), 0, c->stream, db, b1);
-				}
-				hipLaunchKernelGGL(dvp_sweep_decide2, grid, block, 0, c->stream, db, a);
-			}
-			if (c->W >= 12 && c->H >= 12) {
-				const long long frame = 12ll * c->W + 12ll * (c->H - 12);
-				hipLaunchKernelGGL(ex ? dvp_sweep_border_exact : dvp_sweep_border, dim3((unsigned)((frame + 63) / 64)), dim3(64), 0, c->stream, c->d, sb);
-			}
-			else hipLaunchKernelGGL(ex ? dvp_depth_to_weak_refine_exact : dvp_depth_to_weak_refine, grid, block, 0, c->stream, c->d, sb);
-		}
-		else if (fused) hipLaunchKernelGGL(c->d.sampler ? dvp_depth_to_weak_refine_exact : dvp_depth_to_weak_refine, grid, block, 0, c->stream, c->d, a);
-		else hipLaunchKernelGGL(c->d.sampler ? dvp_depth_to_weak_exact : dvp_depth_to_weak, grid, block, 0, c->stream, c->d, a);
-		break;
-	}
-	case DVP_ST_LOCAL_REFINE: hipLaunchKernelGGL(c->d.sampler ? dvp_local_refine_exact : dvp_local_refine, grid, block, 0, c->stream, c->d, a); break;
+	case DVP_ST_RANDOM_INIT: hipLaunchKernelGGL(DVP_PICK(dvp_random_init, ), grid, block, 0, c->stream, c->d, a); break;
+	case DVP_ST_GET_DEPTH_NORMAL: hipLaunchKernelGGL(DVP_PICK(dvp_get_depth_normal, ), grid, block, 0, c->stream, c->d, a); break;
+	case DVP_ST_FILTER_STRONG: hipLaunchKernelGGL(DVP_PICK(dvp_filter_strong, ), grid, block, 0, c->stream, c->d, a); break;
+	case DVP_ST_LOCAL_REFINE: hipLaunchKernelGGL(DVP_PICK(dvp_local_refine, ), grid, block, 0, c->stream, c->d, a); break;
 	}
 	HIP_TRY(c, hipGetLastError());
+	return 0;
+}
+
+static int launch_stage(dvp_ctx* c, int stage, int iter, int colour, bool fused = false) {
+	if (stage < 0 || stage >= DVP_ST_LAUNCHABLE) { c->error = "bad stage id"; return 1; }
+	if (!c->sector_taps) { c->error = "dvp_set_params must be called before running kernels"; return 1; }
+	if (c->d.params.geom_consistency && !c->have_depths) { c->error = "geom_consistency is on but no depth maps were uploaded"; return 1; }
+	const LaunchGeom g = make_geom(c->W, c->H, stage_is_half(stage));
+	const LaunchArgs a = make_args(g, colour, iter);
+	if (c->events.size() >= 2048 && dvp_get_timings(c, nullptr)) return 1;   // fold pending timings: bounds the event pool
+	if (stage != DVP_ST_STRONG_UPDATE && stage != DVP_ST_RANSAC_FIT && stage != DVP_ST_WEAK_UPDATE) c->anchor_tab_valid = false;   // anchors / offsets / WEAK states may change: the next weak update rebuilds its table
+	if (stage == DVP_ST_STRONG_UPDATE && launch_strong_prep(c, g, a)) return 1;
+	EventPair ep;
+	ep.stage = stage;
+	HIP_TRY(c, hipEventCreate(&ep.a));
+	HIP_TRY(c, hipEventCreate(&ep.b));
+	if (c->profiling) HIP_TRY(c, hipMemsetAsync(c->eval_counter, 0, 8, c->stream));
+	HIP_TRY(c, hipEventRecord(ep.a, c->stream));
+	int r;
+	switch (stage) {
+	case DVP_ST_FIND_NEAREST_STRONG: case DVP_ST_GEN_NEIGHBOURS: case DVP_ST_NEIGHBOUR_UPDATE: case DVP_ST_RANSAC_FIT: case DVP_ST_WEAK_UPDATE:
+		r = launch_list_site(c, stage, iter, colour); break;
+	case DVP_ST_STRONG_UPDATE: r = launch_strong_update(c, g, a); break;
+	case DVP_ST_DEPTH_TO_WEAK: r = launch_sweeps(c, g, a, fused); break;
+	default: r = launch_pixel_site(c, stage, g, a, fused); break;
 	}
+	if (r) return 1;
 	HIP_TRY(c, hipEventRecord(ep.b, c->stream));
 	c->events.push_back(ep);
 	if (c->profiling) {
@@ -2217,10 +2169,6 @@ int dvp_run_stage(dvp_ctx* c, int stage, int iter, int colour) {
 	return launch_stage(c, stage, iter, colour);
 }
 
-// Optional buffers ahead of their first use (a helper thread of the driver calls this on the context it prepares for the next
-// pyramid level): flags bit 0 = the split strong update's cost block, bit 1 = the view-compacted sweep passes' buffers;
-// weak_pixels > 0: anchor table and hand-over buffers of the weak update for that many WEAK pixels.  Nothing here is required —
-// every launch site allocates what it lacks — and a buffer that does not fit selects the fall-back form exactly as there.
 // scratch + the first `slots` output maps of dvp_edge_map_begin
 static int ensure_edge_buffers(dvp_ctx* c, int slots) {
 	if (dvpedge::scratch_reserve(c->eg, c->L)) { c->error = "dvp_edge_map: out of device memory"; return 1; }
@@ -2232,11 +2180,15 @@ static int ensure_edge_buffers(dvp_ctx* c, int slots) {
 	return 0;
 }
 
+// Optional buffers ahead of their first use (a helper thread of the driver calls this on the context it prepares for the next
+// pyramid level): flags bit 0 = the split strong update's cost block, bit 1 = the view-compacted sweep passes' buffers;
+// weak_pixels > 0: anchor table and hand-over buffers of the weak update for that many WEAK pixels.  Nothing here is required —
+// every launch site allocates what it lacks — and a buffer that does not fit selects the fall-back form exactly as there.
 int dvp_ctx_reserve(dvp_ctx* c, int weak_pixels, int flags) {
 	if (set_device(c)) return 1;
 	if (flags & 1) ensure_strong_split_buffers(c);
 	if (flags & 2) ensure_sweep_buffers(c);
-	if ((flags & 4) && !c->no_images8 && !c->no_images16 && ensure_images16(c)) return 1;
+	if ((flags & 4) && !c->sw.no_images8 && !c->sw.no_images16 && ensure_images16(c)) return 1;
 	if ((flags & 8) && ensure_edge_buffers(c, 2)) return 1;
 	if ((flags & 16) && dvpvc::scratch_reserve(c->vc, c->L, c->NI - 1)) { c->error = "dvp_ctx_reserve: out of device memory (view clean-up)"; return 1; }
 	if (weak_pixels > 0) {
@@ -2267,27 +2219,16 @@ int dvp_run_patchmatch(dvp_ctx* c) {
 	// The candidates read the images, the sector tables and selected_views (which RandomInitialization is the first
 	// to write) and are read by the weak updates: they run on the side stream from here to just before RandomInit.
 	const bool side_work = c->d.weak_count > 0;
-	bool masked = side_work && c->cand_mask_on && (c->cand_mask_mode == 1 || (c->cand_mask_mode < 0 && (size_t)c->d.weak_count * 25 < c->L));
-	if (masked && !c->cand_mask) {   // mark bytes, anchor list, snapshot of the selected-view map: 9 bytes per pixel
-		void *m = nullptr, *l = nullptr, *n = nullptr, *sv = nullptr;
-		if (hipMalloc(&m, c->L) != hipSuccess || hipMalloc(&l, c->L * 4) != hipSuccess || hipMalloc(&n, 4) != hipSuccess || hipMalloc(&sv, (c->L + c->W) * 4) != hipSuccess) {
-			(void)hipGetLastError();
-			for (void* p : { m, l, n, sv }) if (p) (void)hipFree(p);
-			c->cand_mask_on = masked = false;   // no room: every pixel, as before
-		} else {
-			for (void* p : { m, l, n, sv }) c->allocs.push_back(p);
-			c->cand_mask = (uint8_t*)m; c->cand_list = (unsigned*)l; c->cand_n = (unsigned*)n; c->sel_snap = (uint32_t*)sv;
-		}
-	}
+	if (candidates_masked(c->sw, c->d.weak_count, c->L, c->cand_mask_fits) && !c->cand_mask)   // mark bytes, anchor list, snapshot of the selected-view map: 9 bytes per pixel
+		alloc_group_or_fall_back(c, { areq(&c->cand_mask, c->L), areq(&c->cand_list, c->L * 4), areq(&c->cand_n, 4), areq(&c->sel_snap, (c->L + c->W) * 4) },
+			nullptr, &c->cand_mask_fits, nullptr, 0.0);   // no room: every pixel, as before
+	const bool masked = candidates_masked(c->sw, c->d.weak_count, c->L, c->cand_mask_fits);
 	if (side_work && !masked) {
 		if (!c->sector_taps) { c->error = "dvp_set_params must be called before running kernels"; return 1; }
 		HIP_TRY(c, hipEventRecord(c->side_fork, c->stream));
 		HIP_TRY(c, hipStreamWaitEvent(c->side, c->side_fork, 0));
 		const LaunchGeom g = make_geom(c->W, c->H, false);
-		LaunchArgs a;
-		a.tiles_x = g.tiles_x; a.tiles = g.tiles; a.rows = g.rows; a.half = 0; a.colour = 0; a.iter = 0;
-		if (gen_candidates_all_views(c->d)) hipLaunchKernelGGL(dvp_gen_candidates_views, dim3(g.grid(), (unsigned)((c->NI - 1 + kCandGroup - 1) / kCandGroup)), dim3(256), 0, c->side, c->d, a);
-		else hipLaunchKernelGGL(dvp_gen_candidates, dim3(g.grid(), (unsigned)(c->NI - 1)), dim3(256), 0, c->side, c->d, a);
+		launch_gen_candidates(c, c->side, c->d, g.grid(), make_args(g, 0, 0));
 		HIP_TRY(c, hipGetLastError());
 		HIP_TRY(c, hipEventRecord(c->side_join, c->side));
 	}
@@ -2313,8 +2254,7 @@ int dvp_run_patchmatch(dvp_ctx* c) {
 		const size_t most = std::min(c->L, (size_t)la.count * (DVP_NEIGHBOUR_NUM - 1));
 		Dev dsnap = c->d;
 		dsnap.selected_views = c->sel_snap;
-		if (most > 0 && gen_candidates_all_views(dsnap)) hipLaunchKernelGGL(dvp_gen_candidates_views_list, dim3((unsigned)((most + 255) / 256), (unsigned)((c->NI - 1 + kCandGroup - 1) / kCandGroup)), dim3(256), 0, c->side, dsnap, c->cand_list, c->cand_n);
-		else if (most > 0) hipLaunchKernelGGL(dvp_gen_candidates_list, dim3((unsigned)((most + 255) / 256), (unsigned)(c->NI - 1)), dim3(256), 0, c->side, dsnap, c->cand_list, c->cand_n);
+		if (most > 0) launch_gen_candidates(c, c->side, dsnap, (unsigned)((most + 255) / 256), LaunchArgs{}, c->cand_list, c->cand_n);
 		HIP_TRY(c, hipGetLastError());
 		HIP_TRY(c, hipEventRecord(c->side_join, c->side));
 	}
@@ -2333,7 +2273,7 @@ int dvp_run_patchmatch(dvp_ctx* c) {
 			// Black then red (APD.cu:4487-4489).  A WEAK pixel's update reads other pixels' state only at its anchors, which are STRONG
 			// (GenNeighbours) and which no weak update writes: the two launches commute, and as the eight launches of the phased form
 			// they are issued once over the whole WEAK list (half the launches and their tails).  dvp_run_stage keeps the colours apart.
-			if (c->weak_phased && !c->anchor_tab_off && !getenv("DVP_WEAK_SPLIT_COLOURS")) {
+			if (weak_joins_colours(c->sw, c->anchor_tab_fits, c->weak_phase_fits)) {
 				if (launch_stage(c, DVP_ST_WEAK_UPDATE, i, 2)) return 1;
 			} else {
 				if (launch_stage(c, DVP_ST_WEAK_UPDATE, i, 0)) return 1;

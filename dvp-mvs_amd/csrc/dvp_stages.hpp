@@ -68,7 +68,6 @@ DVP_HD bool block_to_pixel(int block, int lane, int wave, int tiles_x, int tiles
 }
 
 // per-pixel predicate + body of launch site `STAGE` (DVP_ST_*), APD.cu:3091-3165, 3296-3328
-constexpr int kNarrowViews = 8;   // view capacity of the narrow strong-update instantiation
 // internal launch site: DepthToWeak with LocalRefine done by the same thread (dvp_run_patchmatch issues the two
 // back to back; depth_to_weak_px<SMP, true>).  dvp_run_stage keeps the two separate launches.
 constexpr int kStageSweeps = 100;
@@ -92,8 +91,7 @@ DVP_HD void run_pixel(const Dev& d, int px, int py, int iter, unsigned long long
 		// Host emulation: the same choice.
 #if !defined(__HIPCC__)
 		if (d.weak_info[center] == DVP_WEAK) {
-			const char* gw_env = getenv("DVP_GN_WAVE");
-			if (gw_env && atoi(gw_env) != 0) { GnShared gs; gen_neighbours_search_wave(d, px, py, gs); }
+			if (read_form_switches().gn_wave) { GnShared gs; gen_neighbours_search_wave(d, px, py, gs); }
 			else { s2 pts[kGnDirSlots]; gen_neighbours_px(d, px, py, pts, 1); }
 			FitShared sh;
 			gen_neighbours_fit_wave(d, px, py, sh);
@@ -109,8 +107,7 @@ DVP_HD void run_pixel(const Dev& d, int px, int py, int iter, unsigned long long
 	else if (STAGE == DVP_ST_RANSAC_FIT) {
 		// device: one lane per WEAK pixel, or (DVP_RANSAC_WAVE=1) one wave per WEAK pixel (dvp_ransac_fit_plane_wave); the host emulation follows the switch
 #if !defined(__HIPCC__)
-		const char* rw = getenv("DVP_RANSAC_WAVE");
-		if (rw && atoi(rw) != 0) { RansacShared sh; ransac_fit_plane_wave(d, px, py, iter, sh); }
+		if (read_form_switches().ransac_wave) { RansacShared sh; ransac_fit_plane_wave(d, px, py, iter, sh); }
 		else
 #endif
 		ransac_fit_plane_px(d, px, py, iter);

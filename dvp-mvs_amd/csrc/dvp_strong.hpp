@@ -1430,9 +1430,8 @@ DVP_HD void local_refine_px(const Dev& d, int px, int py, PatchTab tab, unsigned
 //   sweep_decide2_px   per pixel with a central peak: folds the rest of the line, peak statistics -> weak_info
 // Border pixels (DepthToWeak marks them UNKNOWN, LocalRefine has no border rule) go through the fused kernel.
 constexpr int kSweepExtra = 72;     // sweep_cost field of the current depth: ncc + factor * geom (APD.cu:4085-4089)
-constexpr int kSweepFields = 73;    // [0, 61): slot pd + 30 — ncc for |pd| <= 5, ncc + factor * geom otherwise; [61, 72): geom of slot |pd| <= 5
+// (kSweepFields, sweep_window and sweep_cost_floats: dvp_forms.hpp — the host's band arithmetic needs them too)
 enum { SWF_VALID = 1, SWF_REFINE = 2, SWF_PEAK = 4 };
-DVP_HD int sweep_window(const DvpParams& P) { int cw = P.weak_peak_radius + 1; if (cw < 5) cw = 5; if (cw > 30) cw = 30; return cw; }
 // sweep_cost, the per (view, field, pixel) record.  DVP_SWEEP_LAYOUT 1 (default): [group of 64 pixels][view][field][64] — the 73 fields
 // of a (group, view) are 18.7 KB in a row: an evaluation launch (one view) fills them slot after slot, a decision pass reads a view's 50
 // slots from 50 neighbouring 256-byte lines.  0: [view][field][pixel] (rounds 4-5): the same slots lie L floats apart — 9 x 50 streams
@@ -1440,7 +1439,6 @@ DVP_HD int sweep_window(const DvpParams& P) { int cw = P.weak_peak_radius + 1; i
 #ifndef DVP_SWEEP_LAYOUT
 #define DVP_SWEEP_LAYOUT 1
 #endif
-DVP_HD size_t sweep_cost_floats(size_t L, int S) { return ((L + 63) / 64) * 64 * (size_t)S * kSweepFields; }
 DVP_HD size_t sweep_field_stride(const Dev& d) {   // between field f and f + 1 of the same (view, pixel)
 #if DVP_SWEEP_LAYOUT == 1
 	(void)d;

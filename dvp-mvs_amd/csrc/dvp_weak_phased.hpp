@@ -91,8 +91,7 @@ DVP_HD void weak_ev_load8(const float* ev, int v, float* out) {
 //   MODE 1  E1: the record's planes against its views
 //   MODE 2  E2a: the hypotheses in range against the FIRST selected view; decides which survive
 //   MODE 3  E2b: the survivors against the other selected views
-constexpr int kGrp = 4;   // pixels per wave at most (E0: kGrpWide)
-constexpr int kGrpWide = 2;
+// (kGrp pixels per wave at most, E0: kGrpWide — dvp_forms.hpp)
 template <int GRP>
 struct WeakGroupSharedT {
 	// per pixel of the group

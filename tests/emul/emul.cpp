@@ -21,8 +21,8 @@ struct Emu {
 	std::vector<uint8_t> images8;       // tiled byte pairs (Dev::images8), read when the set is format 1
 	std::vector<uint32_t> images16;     // tiled binary16 pairs (Dev::images16), read when the set is format 2
 	std::vector<unsigned> image_bits;   // per image: the bits of tile_pair_rule over its plane (3 until it is uploaded)
-	bool no_images8 = false, no_images16 = false;   // DVP_NO_IMAGES8 / DVP_NO_IMAGES16 when the context was created (dvp_ctx_create)
-	int format = 0;                     // the set's image format, the engine's rule (dvp_engine.hip: upload_planes)
+	FormSwitches created;               // the switches when the context was created (dvp_ctx_create): DVP_NO_IMAGES8 / DVP_NO_IMAGES16
+	int format = 0;                     // the set's image format (dvp_forms.hpp: image_format)
 	std::vector<float> nan_plane;       // what the anchor table reads as float planes where the set is format 1 or 2
 	std::vector<DvpCamera> cameras;
 	std::vector<ViewConst> views;
@@ -40,7 +40,7 @@ struct Emu {
 	std::vector<s2> weak_nearest_strong, neighbours, candidate, edge_neigh, label_boundary, label_stop, gn_points;
 	std::vector<int> gn_count;
 	std::vector<AnchorRec> anchor_tab;   // the weak update's per-pass table (dvp_weak_wave.hpp), same validity rule as the engine's
-	bool anchor_tab_valid = false, anchor_tab_off = false;
+	bool anchor_tab_valid = false, anchor_tab_off = false;   // off: DVP_WEAK_ANCHOR_TAB=0 at the last weak update
 	std::vector<WeakRec> weak_rec;       // the weak update as seven launches (dvp_weak_phased.hpp)
 	std::vector<f2> weak_ctab;
 	std::vector<float> weak_ev;
@@ -63,7 +63,7 @@ void refresh(Emu& e) {
 	{   // the whole set takes one format: 1 if every texel is 8-bit exact, 2 if not but every texel is binary16-exact
 		unsigned bits = 0;
 		for (unsigned b : e.image_bits) bits |= b;
-		e.format = (bits == 0 && !e.no_images8) ? 1 : ((bits == 1 && !e.no_images8 && !e.no_images16) ? 2 : 0);
+		e.format = image_format(e.created, bits);
 		d.images8 = e.format == 1 ? e.images8.data() : nullptr;
 		d.images16 = e.format == 2 ? e.images16.data() : nullptr;
 	}
@@ -143,8 +143,7 @@ void* emu_create(int W, int H, int NI) {
 	e->images8.assign((size_t)img8_tiles_x(W) * img8_tiles_y(H) * 128 * NI, 0);
 	e->images16.assign((size_t)img16_tiles_x(W) * img16_tiles_y(H) * 32 * NI, 0u);
 	e->image_bits.assign(NI, 3u);
-	e->no_images8 = getenv("DVP_NO_IMAGES8") != nullptr;
-	e->no_images16 = getenv("DVP_NO_IMAGES16") != nullptr;
+	e->created = read_form_switches();
 	e->nan_plane.assign((size_t)e->pitch * (H + 2 * kImgPad) * 2, std::nanf(""));
 	e->depths.assign((size_t)e->pitch * (H + 2 * kImgPad) * NI, 0.0f);
 	e->cameras.resize(NI);
@@ -371,12 +370,15 @@ static void pack_edge(Emu& e) {
 
 int emu_run_stage(void* c, int stage, int iter, int colour) {
 	Emu& e = *(Emu*)c;
+	// The form of every launch is the engine's (dvp_forms.hpp), decided from the switches as they stand NOW — the engine reads
+	// them when a context is created, the tests set them between the launches of one emulation object — with every optional
+	// buffer there, so that each form is checked against the oracle.
+	const FormSwitches sw = read_form_switches();
 	// the engine's rule (dvp_engine.hip: launch_stage / ensure_anchor_table): any launch other than the three of the iteration
 	// loop may change anchors, offsets or WEAK states; the first weak update after it rebuilds the table
 	if (stage != DVP_ST_STRONG_UPDATE && stage != DVP_ST_RANSAC_FIT && stage != DVP_ST_WEAK_UPDATE) e.anchor_tab_valid = false;
 	if (stage == DVP_ST_WEAK_UPDATE) {
-		const char* off = getenv("DVP_WEAK_ANCHOR_TAB");
-		e.anchor_tab_off = off && atoi(off) == 0;
+		e.anchor_tab_off = sw.anchor_tab_off;
 		if (!e.anchor_tab_off && !e.anchor_tab_valid) {
 			const int S = e.NI - 1;
 			e.anchor_tab.assign((size_t)std::max(e.d.weak_count, 1) * S * kAnchors, AnchorRec{});
@@ -439,13 +441,10 @@ int emu_run_stage(void* c, int stage, int iter, int colour) {
 					int px, py;
 					if (block_to_pixel(b, lane, wave, g.tiles_x, g.tiles, g.rows, 1, colour, e.W, e.H, &px, &py)) strong_search_px(e.d, px, py);
 				}
-		// the engine issues the update as three launches for S <= 16 (dvp_strong_eval / _decide / _refine) unless
-		// DVP_STRONG_SPLIT=0; the emulation follows the same switch, so both forms are checked against the oracle
-		const char* sp = getenv("DVP_STRONG_SPLIT");
-		const char* rl = getenv("DVP_REFINE_LANES");
-		const bool refine_lanes = !(rl && atoi(rl) == 0);   // dvp_strong_refine_lanes / dvp_strong_refine
+		// three launches (dvp_strong_eval / _decide / _refine) or the monolithic kernel
 		const int S = e.NI - 1;
-		if (S <= 16 && !(sp && atoi(sp) == 0)) {
+		const StrongForm f = strong_form(sw, S, true, false, (unsigned long long)e.d.plane_stride * 8 * e.NI);   // (no plane cache here: f.plan is not used)
+		if (f.kernel == STRONG_SPLIT) {
 			unsigned long long total = 0;
 			for (int part = 0; part < 3; ++part) {
 #pragma omp parallel for schedule(dynamic, 1) reduction(+ : total)
@@ -460,14 +459,16 @@ int emu_run_stage(void* c, int stage, int iter, int colour) {
 							const PatchTab tab{tab_mem, 1};
 							if (part == 0) { if (e.d.sampler) strong_eval_px<1>(e.d, px, py, tab, e.count ? &n : nullptr); else strong_eval_px<0>(e.d, px, py, tab, e.count ? &n : nullptr); }
 							else if (part == 1) {
-								if (S <= 4) strong_decide_px<4>(e.d, px, py, iter);
-								else if (S <= 6) strong_decide_px<6>(e.d, px, py, iter);
-								else if (S <= 8) strong_decide_px<8>(e.d, px, py, iter);
-								else if (S <= 10) strong_decide_px<10>(e.d, px, py, iter);
-								else if (S <= 12) strong_decide_px<12>(e.d, px, py, iter);
-								else strong_decide_px<16>(e.d, px, py, iter);
+								switch (f.decide) {
+								case 4: strong_decide_px<4>(e.d, px, py, iter); break;
+								case 6: strong_decide_px<6>(e.d, px, py, iter); break;
+								case 8: strong_decide_px<8>(e.d, px, py, iter); break;
+								case 10: strong_decide_px<10>(e.d, px, py, iter); break;
+								case 12: strong_decide_px<12>(e.d, px, py, iter); break;
+								default: strong_decide_px<16>(e.d, px, py, iter); break;
+								}
 							}
-							else if (refine_lanes) { if (e.d.sampler) strong_refine_px<1, true>(e.d, px, py, tab, e.count ? &n : nullptr); else strong_refine_px<0, true>(e.d, px, py, tab, e.count ? &n : nullptr); }
+							else if (f.refine_lanes) { if (e.d.sampler) strong_refine_px<1, true>(e.d, px, py, tab, e.count ? &n : nullptr); else strong_refine_px<0, true>(e.d, px, py, tab, e.count ? &n : nullptr); }
 							else { if (e.d.sampler) strong_refine_px<1>(e.d, px, py, tab, e.count ? &n : nullptr); else strong_refine_px<0>(e.d, px, py, tab, e.count ? &n : nullptr); }
 							total += n;
 						}
@@ -480,10 +481,11 @@ int emu_run_stage(void* c, int stage, int iter, int colour) {
 	}
 	case DVP_ST_RANSAC_FIT: pack_edge(e); launch<DVP_ST_RANSAC_FIT>(e, iter, colour); break;
 	case DVP_ST_WEAK_UPDATE: {
-		// the engine issues the update as seven launches (dvp_weak_phased.hpp) where the anchor table is on, unless
-		// DVP_WEAK_PHASED=0; the emulation follows the same switch, so both forms are checked against the oracle
-		const char* ph = getenv("DVP_WEAK_PHASED");
-		if (!e.d.anchor_tab || (ph && atoi(ph) == 0)) { launch<DVP_ST_WEAK_UPDATE>(e, iter, colour); break; }
+		// the eight launches of the phased form (dvp_weak_phased.hpp) at every WEAK count, or one wave per WEAK pixel
+		FormSwitches any_count = sw;
+		any_count.weak_phased_min = 0;
+		const WeakForm f = weak_form(any_count, e.d.anchor_tab != nullptr, true, e.d.weak_count);
+		if (f.kernel != WEAK_PHASED) { launch<DVP_ST_WEAK_UPDATE>(e, iter, colour); break; }
 		const int S = e.NI - 1;
 		const size_t n = (size_t)std::max(e.d.weak_count, 1);
 		WeakRec poison;
@@ -502,18 +504,12 @@ int emu_run_stage(void* c, int stage, int iter, int colour) {
 					int px, py;
 					if (block_to_pixel(b, lane, wave, g.tiles_x, g.tiles, g.rows, 1, colour, e.W, e.H, &px, &py) && e.d.weak_info[px + py * e.W] == DVP_WEAK) list.push_back(px + py * e.W);
 				}
-		int group[4] = { 1, 4, 4, 2 };
-		if (const char* gs = getenv("DVP_WEAK_GROUPS")) {
-			int q[4];
-			if (sscanf(gs, "%d,%d,%d,%d", &q[0], &q[1], &q[2], &q[3]) == 4)
-				for (int i = 0; i < 4; ++i) group[i] = q[i] < 1 ? 1 : (q[i] > kGrp ? kGrp : q[i]);
-		}
 		const bool ex = e.d.sampler != 0;
 		const int fmt = e.format;
 		const long long n_px = (long long)list.size();
 		unsigned long long total = 0;
 		auto eval = [&](int mode) {
-			const int G = std::min(group[mode], mode == 0 ? kGrpWide : kGrp);
+			const int G = f.group[mode];
 #pragma omp parallel for schedule(dynamic, 4) reduction(+ : total)
 			for (long long t0 = 0; t0 < n_px; t0 += G) {
 				unsigned long long k = 0;
@@ -551,9 +547,9 @@ int emu_run_stage(void* c, int stage, int iter, int colour) {
 	case DVP_ST_DEPTH_TO_WEAK: launch<DVP_ST_DEPTH_TO_WEAK>(e, iter, colour); break;
 	case DVP_ST_LOCAL_REFINE: launch<DVP_ST_LOCAL_REFINE>(e, iter, colour); break;
 	case kStageSweeps: {
-		// the engine issues the fused launch site as view-compacted passes unless DVP_SWEEP_SPLIT=0; the emulation follows the switch
-		const char* sp = getenv("DVP_SWEEP_SPLIT");
-		if ((sp && atoi(sp) == 0) || !(e.d.params.geom_consistency || (sp && atoi(sp) == 2))) { launch<kStageSweeps>(e, iter, colour); break; }   // (the engine's rule: the passes where the geometric term is on, DVP_SWEEP_SPLIT=2 everywhere)
+		// the fused launch site: one kernel or the view-compacted passes
+		const SweepForm f = sweep_form(sw, true, e.d.params, true, e.W, e.H);
+		if (f.kernel != SWEEP_PASSES) { launch<kStageSweeps>(e, iter, colour); break; }
 		const size_t L = (size_t)e.W * e.H;
 		const int S = e.NI - 1;
 		e.sweep_rec.assign(2 * L, mk4(0, 0, 0, 0));
@@ -567,7 +563,7 @@ int emu_run_stage(void* c, int stage, int iter, int colour) {
 		};
 		each_pixel([&](int px, int py) { sweep_prepare_px(e.d, px, py); });
 		for (int stage = 0; stage < 2; ++stage) {
-			if (stage == 1 && sweep_window(e.d.params) >= 30) break;
+			if (stage == 1 && !f.second_eval) break;
 			unsigned long long total = 0;
 #pragma omp parallel for schedule(dynamic, 256) reduction(+ : total)
 			for (long long c = 0; c < n; ++c)
@@ -621,6 +617,33 @@ int emu_line_test(void* c, int ax, int ay, int bx, int by, int which) {
 }
 void emu_pack_edges(void* c) { pack_edge(*(Emu*)c); }
 float emu_expf(float x) { return dvp_expf(x); }
+
+// dvp_forms.hpp for tests/test_forms.py: the switches as the environment has them ...
+void emu_forms_switches(int* out, double* sweep_band_gb) {
+	const FormSwitches s = read_form_switches();
+	const int v[] = { s.no_images8, s.no_images16, s.strong_split, s.strong_reuse, s.refine_lanes, s.eval_items, s.sweep_split, s.sweep_force, s.anchor_tab_off,
+		s.gn_wave, s.ransac_wave, s.cand_mask_mode, s.weak_phased, s.weak_phased_min, s.weak_run[0], s.weak_run[1], s.weak_run[2], s.weak_run[3],
+		s.weak_group[0], s.weak_group[1], s.weak_group[2], s.weak_group[3], s.weak_split_colours };
+	std::memcpy(out, v, sizeof(v));
+	*sweep_band_gb = s.sweep_band_gb;
+}
+// ... and every decision under them.  in: S, split_fits, reuse_hdr, big_images (the set is 4 GiB), table_present, table_fits, phase_fits,
+// count, fused, geom, weak_peak_radius, sweep_fits, W, H, weak_count, mask_fits, inexact
+void emu_forms_decide(const int* in, int* out) {
+	const FormSwitches s = read_form_switches();
+	const int S = in[0], W = in[12], H = in[13];
+	const StrongForm st = strong_form(s, S, in[1] != 0, in[2] != 0, in[3] ? 1ull << 32 : (1ull << 32) - 1);
+	const WeakForm wk = weak_form(s, in[4] != 0, in[6] != 0, in[7]);
+	DvpParams P;
+	std::memset(&P, 0, sizeof(P));
+	P.geom_consistency = in[9];
+	P.weak_peak_radius = in[10];
+	const SweepForm sp = sweep_form(s, in[8] != 0, P, in[11] != 0, W, H);
+	const int v[] = { st.kernel, st.eval_items, st.decide, st.refine_lanes, st.plan,
+		wk.kernel, wk.group[0], wk.group[1], wk.group[2], wk.group[3], wk.run[0], wk.run[1], wk.run[2], wk.run[3], weak_joins_colours(s, in[5] != 0, in[6] != 0),
+		sp.kernel, sp.second_eval, sp.border_kernel, sweep_band_rows(s, W, H, S), candidates_masked(s, in[14], (size_t)W * H, in[15] != 0), image_format(s, (unsigned)in[16]) };
+	std::memcpy(out, v, sizeof(v));
+}
 void emu_eval_cost_vectors(void* c, const int* px, const float* planes, int n, float* out) {
 	Emu& e = *(Emu*)c;
 	const int S = e.NI - 1;

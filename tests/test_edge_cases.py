@@ -40,7 +40,7 @@ def scene_with_views(W, H, S, seed=7):
     return out
 
 
-# Image sets for each format the weak update reads (dvp_engine.hip: upload_planes; capi.Context.image_format()):
+# Image sets for each format the weak update reads (dvp_forms.hpp: image_format; capi.Context.image_format()):
 # name -> (the format the engine must report, environment before the context is created)
 IMAGE_SETS = {
     "int": (1, {}),                              # as rendered: integer grey levels, byte tiles

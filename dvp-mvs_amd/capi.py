@@ -39,10 +39,12 @@ EXPORTS = ["dvp_ctx_create", "dvp_ctx_destroy", "dvp_ctx_reserve", "dvp_last_err
            "dvp_clean_selected_views", "dvp_viewclean_last_error", "dvp_set_view_cleanup",
            "dvp_labels_sizes", "dvp_labels_create", "dvp_labels_destroy", "dvp_labels_run", "dvp_labels_stage", "dvp_labels_timings", "dvp_label_map", "dvp_labels_last_error",
            "dvp_images_create", "dvp_images_destroy", "dvp_images_put", "dvp_images_drop", "dvp_images_size", "dvp_images_bytes", "dvp_images_level", "dvp_images_last_error",
-           "dvp_download_image"]
+           "dvp_download_image",
+           "dvp_plane_prior", "dvp_plane_prior_stage", "dvp_plane_prior_timings"]
 # ... and the one whose name holds a digit (a scan of the header for [a-z_] names does not see it)
 EXPORTS_WITH_DIGITS = ["dvp_upload_images_u8"]
 PREVIEW_DEPTH, PREVIEW_NORMAL, PREVIEW_WEAK = 1, 2, 4
+PRIOR_STAGE_OWNER, PRIOR_STAGE_RATE, PRIOR_STAGE_DEPTH = 0, 1, 2
 
 
 class DvpTimings(ctypes.Structure):
@@ -143,6 +145,9 @@ def lib():
         L.dvp_images_last_error.argtypes = []
         L.dvp_upload_images_u8.argtypes = [vp, vp, vp, ci, ci]
         L.dvp_download_image.argtypes = [vp, ci, vp, ci]
+        L.dvp_plane_prior.argtypes = [vp, vp, ci, ci, vp, vp, ci, vp, pi]
+        L.dvp_plane_prior_stage.argtypes = [vp, ci, vp]
+        L.dvp_plane_prior_timings.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ll)]
         _LIB = L
     return _LIB
 
@@ -516,6 +521,39 @@ class Context:
         out = np.empty((self.H, self.W), np.uint8)
         self._ck(self.L.dvp_edge_map_finish(self.h, _p(out)))
         return out
+
+    def plane_prior(self, dep_raw, xy, xyz, file_camera):
+        """the FIRST_INIT plane prior into the context's planes (include/dvp_mvs.h dvp_plane_prior): dep_raw (rows, cols) float32
+        as dep/<id>.dmb holds it, xy (n, 2) / xyz (n, 3) the sparse points, file_camera the unscaled camera record; returns the
+        status: 0 = planes written, 1 = no usable input, planes untouched"""
+        a = np.ascontiguousarray(dep_raw, np.float32)
+        assert a.ndim == 2, a.shape
+        p2 = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
+        p3 = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        assert len(p2) == len(p3), (p2.shape, p3.shape)
+        cam = np.ascontiguousarray(file_camera).reshape(1)
+        assert cam.dtype.itemsize == 112
+        status = ctypes.c_int(-1)
+        self._ck(self.L.dvp_plane_prior(self.h, _p(a) if a.size else None, a.shape[1], a.shape[0], _p(p2) if len(p2) else None, _p(p3) if len(p3) else None,
+                                        len(p2), _p(cam), ctypes.byref(status)))
+        if status.value == 0:
+            self._prior_shape = a.shape
+        return status.value
+
+    def plane_prior_stage(self, which):
+        """an intermediate map of the last plane_prior with status 0: PRIOR_STAGE_OWNER (int32) / _RATE (float32) at the dep map's
+        size, PRIOR_STAGE_DEPTH (float32) at the context's"""
+        shape = (self.H, self.W) if which == PRIOR_STAGE_DEPTH else getattr(self, "_prior_shape", (1, 1))
+        out = np.empty(shape, np.int32 if which == PRIOR_STAGE_OWNER else np.float32)
+        self._ck(self.L.dvp_plane_prior_stage(self.h, int(which), _p(out)))
+        return out
+
+    def plane_prior_timings(self):
+        """dict(ms=[host part, uploads, kernels], triangles=n, sweep_rows=n) of the last plane_prior with status 0"""
+        ms = (ctypes.c_double * 3)()
+        counts = (ctypes.c_longlong * 2)()
+        self._ck(self.L.dvp_plane_prior_timings(self.h, ms, counts))
+        return dict(ms=list(ms), triangles=int(counts[0]), sweep_rows=int(counts[1]))
 
     def get(self, name):
         bid, dt, k = BUFFERS[name]

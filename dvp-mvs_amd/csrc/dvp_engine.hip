@@ -8,6 +8,7 @@
 #include "dvp_jpeg_enc.h"
 #include "dvp_edges_run.h"
 #include "dvp_viewclean_run.h"
+#include "dvp_prior_run.h"
 #include "dvp_pyramid_run.h"
 #include <hip/hip_runtime.h>
 #include <cstdlib>
@@ -1225,6 +1226,9 @@ struct dvp_ctx {
 	dvpvc::Scratch vc;
 	bool vc_on = false;
 	int vc_num_src = 0, vc_min_region = 0;
+	// dvp_plane_prior: the monocular-depth plane prior of a FIRST_INIT pass (dvp_prior.hip).  The scratch exists from the first call on.
+	dvpprior::Scratch pr;
+	bool have_cameras = false;                // dvp_upload_cameras has run
 	// dvp_save_state / dvp_restore_state: device-side copy of the per-pixel input state
 	f4* saved_planes = nullptr; uint32_t* saved_views = nullptr; uint8_t* saved_weak = nullptr; int* saved_radius = nullptr;
 	bool have_saved = false;
@@ -1429,6 +1433,7 @@ int dvp_ctx_destroy(dvp_ctx* c) {
 	for (auto& e : c->pv_enc) dvpjpeg::encoder_free(e);
 	dvpedge::scratch_free(c->eg);
 	dvpvc::scratch_free(c->vc);
+	dvpprior::scratch_free(c->pr);
 	for (auto& sl : c->eg_slot) { if (sl.map) (void)hipFree(sl.map); if (sl.done) (void)hipEventDestroy(sl.done); }
 	if (c->pv_total) (void)hipHostFree(c->pv_total);
 	if (c->pv_done) (void)hipEventDestroy(c->pv_done);
@@ -1583,6 +1588,43 @@ int dvp_upload_cameras(dvp_ctx* c, const DvpCamera* cams, int n) {
 	hipLaunchKernelGGL(dvp_prepare_views, dim3(1), dim3(64), 0, c->stream, c->cameras, c->views, n);
 	HIP_TRY(c, hipGetLastError());
 	HIP_TRY(c, hipStreamSynchronize(c->stream));
+	c->have_cameras = true;
+	return 0;
+}
+
+// The FIRST_INIT plane prior from the Depth-Anything map and the sparse SfM points (dvp_prior.hip): the planes BuildPlanePrior
+// (host/prior.cpp) computes, bit for bit, written by the device into the context's planes.
+int dvp_plane_prior(dvp_ctx* c, const float* dep_raw, int dep_w, int dep_h, const float* xy, const float* xyz, int num_points, const DvpCamera* file_camera, int* status) {
+	if (!c) return 1;
+	if (!status || !file_camera || num_points < 0 || (num_points > 0 && (!xy || !xyz)) || dep_w < 0 || dep_h < 0 || ((long long)dep_w * dep_h > 0 && !dep_raw)) {
+		c->error = "dvp_plane_prior: the status pointer, the camera, the points and the map are required";
+		return 1;
+	}
+	if (!c->have_cameras) { c->error = "dvp_plane_prior: no cameras in the context yet (dvp_upload_cameras)"; return 1; }
+	if (set_device(c)) return 1;
+	const char* what = "";
+	if (dvpprior::run(c->stream, c->pr, dep_raw, dep_w, dep_h, xy, xyz, num_points, file_camera, c->cameras, c->W, c->H, c->planes, status, &what)) { c->error = what; return 1; }
+	if (*status == 0) {
+		c->anchor_tab_valid = false;
+		bump_reuse_epoch(c);
+	}
+	return 0;
+}
+
+int dvp_plane_prior_stage(dvp_ctx* c, int which, void* dst) {
+	if (!c) return 1;
+	if (!dst) { c->error = "dvp_plane_prior_stage: the destination is required"; return 1; }
+	if (set_device(c)) return 1;
+	const char* what = "";
+	if (dvpprior::stage(c->stream, c->pr, which, dst, &what)) { c->error = what; return 1; }
+	return 0;
+}
+
+int dvp_plane_prior_timings(dvp_ctx* c, double* ms, long long* counts) {
+	if (!c) return 1;
+	if (!c->pr.ran) { c->error = "dvp_plane_prior_timings: no dvp_plane_prior with status 0 has finished on this context"; return 1; }
+	if (ms) for (int k = 0; k < 3; ++k) ms[k] = c->pr.ms[k];
+	if (counts) { counts[0] = c->pr.triangles; counts[1] = c->pr.sweep_rows; }
 	return 0;
 }
 

@@ -30,6 +30,9 @@ bool APD::CleanupOnDevice() { return g_cleanup_on_device; }
 static bool g_labels_on_device = false;
 void APD::SetLabelsOnDevice(bool on) { g_labels_on_device = on; }
 bool APD::LabelsOnDevice() { return g_labels_on_device; }
+static bool g_prior_on_device = false;
+void APD::SetPriorOnDevice(bool on) { g_prior_on_device = on; }
+bool APD::PriorOnDevice() { return g_prior_on_device; }
 static bool g_images_on_device = false;
 void APD::SetImagesOnDevice(bool on) { g_images_on_device = on; }
 bool APD::ImagesOnDevice() { return g_images_on_device; }
@@ -626,9 +629,15 @@ void APD::InuputInitialization() {
 	// FIRST_INIT: plane prior from the Depth-Anything map + sparse SfM points (dep/<id>.dmb,
 	// sfm/<id>.txt, APD.cpp:1210-1424; host/prior.cpp).  Without those inputs the planes stay zero
 	// (.w out of range) and RandomInitialization draws random planes (APD.cu:1289-1291).
-	if (params_host.state == FIRST_INIT) {
+	prior_kept = false;
+	if (params_host.state == FIRST_INIT && g_prior_on_device) {   // the engine makes the planes (CudaSpaceInitialization): keep the inputs
+		prior_kept = ReadPlanePriorInputs(problem, prior_dep, prior_xy, prior_xyz, prior_cam);
+		if (!prior_kept) ViewLog() << "No dep/ + sfm/ prior: random plane initialisation\n";
+		lap("plane prior (inputs read, planes made on the device)");
+	} else if (params_host.state == FIRST_INIT) {
 		if (BuildPlanePrior(problem, cameras[0], width, height, plane_hypotheses_host)) ViewLog() << "Plane prior from dep/ and sfm/\n";
 		else ViewLog() << "No dep/ + sfm/ prior: random plane initialisation\n";
+		lap("plane prior (host)");
 	}
 	if (params_host.state == FIRST_INIT) selected_views_host = Mat::zeros(height, width, CV_32SC1);   // (else loaded below)
 	if (params_host.state != FIRST_INIT) {   // APD.cpp:1428-1456: the previous pass' maps are this pass' start
@@ -849,7 +858,28 @@ void APD::CudaSpaceInitialization() {
 		lap("state upload (coarse maps, rescaled on the device)");
 		return;
 	}
-	DVP_SAFE_CALL(ctx, dvp_upload_state(ctx, reinterpret_cast<const float*>(plane_hypotheses_host),
+	bool planes_on_device = false;   // --prior-on gpu: the planes are in the context already
+	if (prior_kept) {
+		int status = 1;
+		DVP_SAFE_CALL(ctx, dvp_plane_prior(ctx, prior_dep.ptr<float>(0), prior_dep.cols, prior_dep.rows, reinterpret_cast<const float*>(prior_xy.data()),
+			reinterpret_cast<const float*>(prior_xyz.data()), (int)prior_xy.size(), reinterpret_cast<const DvpCamera*>(&prior_cam), &status));
+		planes_on_device = status == 0;
+		if (planes_on_device) ViewLog() << "Plane prior from dep/ and sfm/\n";
+		else ViewLog() << "No dep/ + sfm/ prior: random plane initialisation\n";
+		if (planes_on_device && std::getenv("DVP_HOST_TIMING")) {
+			double ms[3] = { 0, 0, 0 };
+			long long counts[2] = { 0, 0 };
+			DVP_SAFE_CALL(ctx, dvp_plane_prior_timings(ctx, ms, counts));
+			ViewLog() << "  [host]   . plane prior parts: points + triangulation " << ms[0] << " ms, uploads " << ms[1] << " ms, kernels " << ms[2] << " ms ("
+			          << counts[0] << " triangles, " << counts[1] << " sweep rows)" << std::endl;
+		}
+		prior_kept = false;
+		prior_dep = Mat();
+		prior_xy.clear();
+		prior_xyz.clear();
+		lap("plane prior (device)");
+	}
+	DVP_SAFE_CALL(ctx, dvp_upload_state(ctx, planes_on_device ? nullptr : reinterpret_cast<const float*>(plane_hypotheses_host),
 		selected_views_host.ptr<uint32_t>(0), weak_info_host.ptr<uint8_t>(0),
 		((problem.params.use_edge || problem.params.use_limit) && !edge_on_device) ? edge_host.ptr<uint8_t>(0) : nullptr,
 		(problem.params.use_label && !label_host.empty()) ? label_host.ptr<int32_t>(0) : nullptr,

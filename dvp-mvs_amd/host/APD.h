@@ -45,6 +45,7 @@ void ProjectCamera(const float3 PointX, const Camera camera, float2& point, floa
 bool MetricDepthFromPrior(Mat& dep, const std::vector<float2>& xy, const std::vector<float3>& xyz, const Camera& cam);   // APD.cpp:1221-1356
 void PlanesFromDepth(const Mat& dep, const Camera& cam, float4* planes);                              // APD.cpp:1365-1422
 bool BuildPlanePrior(const Problem& problem, const Camera& scaled_ref_camera, int width, int height, float4* planes);
+bool ReadPlanePriorInputs(const Problem& problem, Mat& dep, std::vector<float2>& xy, std::vector<float3>& xyz, Camera& cam);   // dep/ + sfm/ + cams/ of the view, as read
 // image I/O without OpenCV: images/<id>.jpg through the built-in baseline decoder (host/jpeg.cpp), else
 // <id>.pgm|.ppm (binary P5/P6); returns an empty Mat if nothing readable is found.
 Mat DecodeJpeg(const path& file, int channels);     // 1: luma plane (libjpeg JCS_GRAYSCALE), 3: BGR
@@ -146,6 +147,13 @@ public:
 	// Announcing, publishing, file names and SetUseLabelFiles are untouched.  Same values.  Default false.
 	static void SetLabelsOnDevice(bool on);
 	static bool LabelsOnDevice();
+	// `apd --prior-on gpu`.  true: the FIRST_INIT plane prior (dep/<id>.dmb + sfm/<id>.txt, APD.cpp:1210-1424) is made by the engine
+	// (include/dvp_mvs.h dvp_plane_prior: the points and the triangulation on the host, the sweep, the rate map, the rescale and
+	// the planes on the device, into the context's planes): InuputInitialization only reads the three files and keeps them,
+	// CudaSpaceInitialization calls the engine after the cameras' upload and uploads no planes.  Same planes, same two log lines.
+	// Default false.
+	static void SetPriorOnDevice(bool on);
+	static bool PriorOnDevice();
 	// `apd --images-on gpu`.  true: the process keeps the job's decoded 8-bit images in one dvp_images store on the driver's device
 	// (put by the decode prefetch threads or at a view's first use, within DVP_RESIDENT_IMAGES_GB), and a view whose images are all
 	// there builds no host float image: InuputInitialization takes the sizes from the store and the std::round(n * factor) rule,
@@ -205,6 +213,12 @@ private:
 	// device rescale: the previous pass' maps at the coarser level's size, handed to the engine by CudaSpaceInitialization
 	bool coarse_state = false;
 	Mat coarse_depth, coarse_normal, coarse_views, coarse_weak, coarse_radius;
+	// --prior-on gpu: the prior's inputs as read, kept from InuputInitialization to CudaSpaceInitialization
+	bool prior_kept = false;
+	Mat prior_dep;
+	std::vector<float2> prior_xy;
+	std::vector<float3> prior_xyz;
+	Camera prior_cam;
 	void CountWeak();
 	void CoarseStateToHost();   // undo: rescale on the host after all (a map is missing or sizes disagree)
 	dvp_ctx* ctx = nullptr;

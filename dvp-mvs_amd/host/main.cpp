@@ -4,6 +4,7 @@
 //       [--rank R --world N --job ID [--transport rccl|host] [--collective-timeout SEC]] [--jacobi] [--labels]
 //       [--no-fusion | --fusion eth|tat-intermediate|tat-advanced] [--fusion-on device|host]
 //       [--edges-on host|gpu] [--labels-on host|gpu] [--cleanup-on host|gpu] [--images-on host|gpu]
+//       [--prior-on host|gpu]
 //
 // Schedule.  The image pyramid has round_num levels (the longer side is halved until <= 800).  Level i
 // runs one "A" pass without geometric consistency — FIRST_INIT from scratch / the Depth-Anything prior
@@ -45,6 +46,7 @@ struct Options {
 	bool sync_io = false;
 	bool host_rescale = false;
 	bool edges_on_gpu = false;             // --edges-on gpu: the Canny edge prior is made by the engine from the resident image (APD::SetEdgesOnDevice)
+	bool prior_on_gpu = false;             // --prior-on gpu: the FIRST_INIT plane prior from dep/ + sfm/ is made by the engine into the context's planes (APD::SetPriorOnDevice)
 	bool labels_on_gpu = false;            // --labels-on gpu: GetProblemEdges makes the label maps with a dvp_labels job on the rank's device (APD::SetLabelsOnDevice)
 	bool cleanup_on_gpu = false;           // --cleanup-on gpu: the visibility-mask clean-up runs in the engine on the staged selected-view words (APD::SetCleanupOnDevice)
 	bool images_on_gpu = false;            // --images-on gpu: every view's level images are made by the engine from the decoded bytes, uploaded once per job (APD::SetImagesOnDevice)
@@ -544,6 +546,11 @@ Options ParseOptions(int argc, char** argv) {
 			if (where != "host" && where != "gpu") { std::cerr << "--labels-on takes host or gpu\n"; std::exit(1); }
 			o.labels_on_gpu = where == "gpu";
 		}
+		else if (s == "--prior-on" && a + 1 < argc) {
+			const std::string where = argv[++a];
+			if (where != "host" && where != "gpu") { std::cerr << "--prior-on takes host or gpu\n"; std::exit(1); }
+			o.prior_on_gpu = where == "gpu";
+		}
 		else if (s == "--cleanup-on" && a + 1 < argc) {
 			const std::string where = argv[++a];
 			if (where != "host" && where != "gpu") { std::cerr << "--cleanup-on takes host or gpu\n"; std::exit(1); }
@@ -569,7 +576,7 @@ Options ParseOptions(int argc, char** argv) {
 
 int main(int argc, char** argv) {
 	if (argc < 2) {
-		std::cerr << "USAGE: apd dense_folder [gpu_index] [--previews] [--max-src N] [--iters N] [--min-scale S] [--passes P] [--seed X] [--rank R --world N [--job ID]] [--jacobi] [--no-fusion | --fusion KIND] [--fusion-on device|host] [--edges-on host|gpu] [--labels-on host|gpu] [--cleanup-on host|gpu] [--images-on host|gpu] [--views-in-flight N]\n";
+		std::cerr << "USAGE: apd dense_folder [gpu_index] [--previews] [--max-src N] [--iters N] [--min-scale S] [--passes P] [--seed X] [--rank R --world N [--job ID]] [--jacobi] [--no-fusion | --fusion KIND] [--fusion-on device|host] [--edges-on host|gpu] [--labels-on host|gpu] [--cleanup-on host|gpu] [--images-on host|gpu] [--prior-on host|gpu] [--views-in-flight N]\n";
 		return EXIT_FAILURE;
 	}
 	const Options opt = ParseOptions(argc, argv);
@@ -603,6 +610,7 @@ int main(int argc, char** argv) {
 	APD::SetEdgesOnDevice(opt.edges_on_gpu);
 	APD::SetCleanupOnDevice(opt.cleanup_on_gpu);
 	APD::SetLabelsOnDevice(opt.labels_on_gpu);
+	APD::SetPriorOnDevice(opt.prior_on_gpu);
 	APD::SetImagesOnDevice(opt.images_on_gpu);
 	SetResultCache(!opt.sync_io);
 	APD::SetDeviceRescale(!opt.sync_io && !opt.host_rescale);

@@ -399,6 +399,30 @@ int dvp_upload_images_u8(dvp_ctx* ctx, const dvp_images* store, const int* ids, 
 /* The width x height float image `index` the context holds since its last dvp_upload_images*, `pitch_floats` (>= width) per row. */
 int dvp_download_image(dvp_ctx* ctx, int index, float* out, int pitch_floats);
 
+/* ---- the monocular-depth plane prior of a FIRST_INIT pass (APD.cpp:1210-1424) on the device ---------------------------------------
+ * From the relative depth map of dep/<id>.dmb (dep_w x dep_h floats as read, dense) and the sparse points of sfm/<id>.txt
+ * (xy: 2 floats per point, the image position; xyz: 3 floats, the world point) to the context's planes (DVP_BUF_PLANES), equal
+ * to the host mirror's BuildPlanePrior bit for bit (NaN == NaN): every point is projected with file_camera — the camera as
+ * cams/<id>_cam.txt holds it, unscaled — and counts when it lands at 0 < ix < dep_w, 0 < iy < dep_h; its rate is
+ * (255 - dep(iy, ix)) over the projected depth; the positions are Delaunay-triangulated (csrc/dvp_prior_mid.hpp, on the host) and
+ * the rate map is the barycentric interpolation of the rates inside the triangles, the middle point's rate elsewhere; the metric
+ * depth (255 - dep) / rate is taken to the context's size with RescaleMatToTargetSize's index rule; the planes are the
+ * finite-difference normals of that map with the context's reference camera (dvp_upload_cameras: an error before it), turned
+ * towards the camera and to the world frame, and the depth.  *status = 0: the planes were written; 1: an empty map or no usable
+ * point — the planes are untouched.  A following dvp_upload_state(ctx, NULL, ...) keeps the planes.  The number of launches
+ * does not depend on the inputs.  Scratch: 12 bytes per dep-map pixel + 4 per context pixel, kept with the context;
+ * it grows on demand. */
+int dvp_plane_prior(dvp_ctx* ctx, const float* dep_raw, int dep_w, int dep_h, const float* xy, const float* xyz, int num_points,
+                    const DvpCamera* file_camera, int* status);
+/* After a dvp_plane_prior with status 0: an intermediate map of it.  OWNER: dep_w x dep_h int32, the index (in list order) of the
+ * triangle whose value the pixel holds, -1 = none; RATE: dep_w x dep_h floats; DEPTH: the metric depth at the context's size,
+ * width x height floats. */
+enum { DVP_PRIOR_STAGE_OWNER = 0, DVP_PRIOR_STAGE_RATE = 1, DVP_PRIOR_STAGE_DEPTH = 2 };
+int dvp_plane_prior_stage(dvp_ctx* ctx, int which, void* dst);
+/* ... and ms[3] = wall time of the host part (points + triangulation), the uploads, the kernels; counts[2] = swept triangles,
+ * sweep rows over all of them.  NULL pointers are skipped. */
+int dvp_plane_prior_timings(dvp_ctx* ctx, double* ms, long long* counts);
+
 #ifdef __cplusplus
 }
 #endif

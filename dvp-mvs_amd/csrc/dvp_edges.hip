@@ -121,24 +121,18 @@ __global__ void __launch_bounds__(256) dvp_edge_fixups(const uint8_t* __restrict
 }
 
 int scratch_reserve(Scratch& s, size_t pixels) {
-	if (s.alloc >= pixels && s.grey) return 0;
-	scratch_free(s);
 	const size_t n = pixels ? pixels : 1;
-	void *g = nullptr, *m = nullptr, *k = nullptr, *p = nullptr, *h = nullptr;
-	if (hipMalloc(&g, n) != hipSuccess || hipMalloc(&m, n) != hipSuccess || hipMalloc(&k, n) != hipSuccess || hipMalloc(&p, n * 4) != hipSuccess ||
-	    hipMalloc(&h, 258 * 4) != hipSuccess) {
-		(void)hipGetLastError();
-		for (void* q : { g, m, k, p, h }) if (q) (void)hipFree(q);
-		return 1;
-	}
-	s.grey = (uint8_t*)g; s.map3 = (uint8_t*)m; s.mark = (uint8_t*)k; s.parent = (unsigned*)p; s.hist = (unsigned*)h;
-	s.alloc = n;
+	dvpmem::Carve c;
+	const size_t o_grey = c.take(n), o_map3 = c.take(n), o_mark = c.take(n), o_parent = c.take(n * 4), o_hist = c.take(258 * 4);
+	if (s.block.reserve(c.total)) { scratch_free(s); return 1; }
+	uint8_t* b = s.block.as<uint8_t>();
+	s.grey = b + o_grey; s.map3 = b + o_map3; s.mark = b + o_mark; s.parent = (unsigned*)(b + o_parent); s.hist = (unsigned*)(b + o_hist);
 	return 0;
 }
 void scratch_free(Scratch& s) {
-	for (void* q : { (void*)s.grey, (void*)s.map3, (void*)s.mark, (void*)s.parent, (void*)s.hist })
-		if (q) (void)hipFree(q);
-	s = Scratch();
+	s.block.release();
+	s.grey = s.map3 = s.mark = nullptr;
+	s.parent = s.hist = nullptr;
 }
 
 static unsigned blocks1d(size_t L) { return (unsigned)((L + 255) / 256); }
@@ -178,42 +172,35 @@ int launch_fixups(hipStream_t stream, Scratch& s, int W, int H, uint8_t* out, ui
 }   // namespace dvpedge
 
 // ---- the two context-free calls: host in, host out ---------------------------------------------------------------------------
-static thread_local std::string t_edge_error;
+static thread_local dvpmem::CallError t_edge_error;
 
 extern "C" const char* dvp_edge_last_error(void) { return t_edge_error.c_str(); }
 
 // src: `pitch` bytes per row; full = stages 2-6 on grey bytes, else stage 5 on a three-state map
 static int edge_call(const char* who, int device, const uint8_t* src, int W, int H, long long pitch, uint8_t* dst, bool full) {
 	t_edge_error.clear();
-	auto fail = [who](const char* what) { t_edge_error = std::string(who) + ": " + what; return 1; };
+	auto fail = [who](const char* what) { return t_edge_error.fail(who, what); };
 	if (!src || !dst) return fail("input and output pointers are required");
 	if (full && (W < 3 || H < 3)) return fail("width and height must be at least 3 (the frame fix-ups read columns 1, W - 2 and rows 1, H - 2)");
 	if (W < 1 || H < 1 || (long long)W * H > 0x7fffffffLL || pitch < W) return fail("bad image geometry");
 	if (hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); return fail("hipSetDevice failed"); }
-	hipStream_t st = nullptr;
-	if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); return fail("hipStreamCreate failed"); }
 	dvpedge::Scratch s;
-	uint8_t* d_out = nullptr;
+	dvpmem::DevBlock d_out;
+	dvpmem::StreamScope st;
+	if (st.open()) return fail("hipStreamCreate failed");
 	const size_t L = (size_t)W * H;
-	int rc = 0;
-	do {
-		if (dvpedge::scratch_reserve(s, L)) { rc = fail("out of device memory"); break; }
-		if (hipMemcpy2DAsync(full ? s.grey : s.map3, (size_t)W, src, (size_t)pitch, (size_t)W, (size_t)H, hipMemcpyHostToDevice, st) != hipSuccess) { rc = fail("upload failed"); break; }
-		if (full && dvpedge::launch_suppress(st, s, W, H, false)) { rc = fail("launch failed"); break; }
-		if (dvpedge::launch_hysteresis(st, s, W, H)) { rc = fail("launch failed"); break; }
-		const uint8_t* result = s.grey;
-		if (full) {
-			if (hipMalloc(reinterpret_cast<void**>(&d_out), L) != hipSuccess) { (void)hipGetLastError(); d_out = nullptr; rc = fail("out of device memory"); break; }
-			if (dvpedge::launch_fixups(st, s, W, H, d_out, nullptr)) { rc = fail("launch failed"); break; }
-			result = d_out;
-		}
-		if (hipMemcpyAsync(dst, result, L, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) { rc = fail("download failed"); break; }
-	} while (false);
-	(void)hipStreamSynchronize(st);
-	dvpedge::scratch_free(s);
-	if (d_out) (void)hipFree(d_out);
-	(void)hipStreamDestroy(st);
-	return rc;
+	if (dvpedge::scratch_reserve(s, L)) return fail("out of device memory");
+	if (hipMemcpy2DAsync(full ? s.grey : s.map3, (size_t)W, src, (size_t)pitch, (size_t)W, (size_t)H, hipMemcpyHostToDevice, st) != hipSuccess) return fail("upload failed");
+	if (full && dvpedge::launch_suppress(st, s, W, H, false)) return fail("launch failed");
+	if (dvpedge::launch_hysteresis(st, s, W, H)) return fail("launch failed");
+	const uint8_t* result = s.grey;
+	if (full) {
+		if (d_out.reserve(L)) return fail("out of device memory");
+		if (dvpedge::launch_fixups(st, s, W, H, d_out.as<uint8_t>(), nullptr)) return fail("launch failed");
+		result = d_out.as<uint8_t>();
+	}
+	if (hipMemcpyAsync(dst, result, L, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return fail("download failed");
+	return 0;
 }
 
 extern "C" int dvp_canny_edge_map(int device, const uint8_t* grey, int width, int height, long long pitch_bytes, uint8_t* edge_out) {

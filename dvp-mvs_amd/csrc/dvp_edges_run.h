@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "dvp_devmem.hpp"
 #include "dvp_edges.hpp"
 
 namespace dvpedge {
@@ -29,15 +30,16 @@ struct DevMem {
 	}
 };
 
-// Device scratch of one map, 7 bytes per pixel (+ 1 per output map the caller keeps); grows, and is kept for the next map of
-// the same or a smaller size.
+// Device scratch of one map, 7 bytes per pixel (+ 1 per output map the caller keeps) in one block; grows, and is kept for the next
+// map of the same or a smaller size.
 struct Scratch {
+	dvpmem::DevBlock block;
+	// the block's parts
 	uint8_t* grey = nullptr;     // [L] grey bytes; after the suppression has read them: the 0 / 255 map before the fix-ups
 	uint8_t* map3 = nullptr;     // [L] 0 = candidate, 1 = nothing, 2 = strong
 	uint8_t* mark = nullptr;     // [L] mark[root] = the set holds a strong pixel
 	unsigned* parent = nullptr;  // [L] union-find links
 	unsigned* hist = nullptr;    // [256] grey histogram, then [256] = low, [257] = high (as int)
-	size_t alloc = 0;            // capacity in pixels
 };
 int scratch_reserve(Scratch& s, size_t pixels);   // non-zero: out of device memory
 void scratch_free(Scratch& s);

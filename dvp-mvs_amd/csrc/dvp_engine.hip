@@ -1214,7 +1214,7 @@ struct dvp_ctx {
 	// background job, when the context may have begun the next view's map already; _finish serves begun maps oldest first, and
 	// a third _begin overwrites the oldest map nobody fetched.
 	dvpedge::Scratch eg;
-	struct EdgeSlot { uint8_t* map = nullptr; hipEvent_t done = nullptr; unsigned long long seq = 0; bool pending = false, fetching = false; };
+	struct EdgeSlot { dvpmem::DevBlock map; hipEvent_t done = nullptr; unsigned long long seq = 0; bool pending = false, fetching = false; };
 	EdgeSlot eg_slot[2];
 	unsigned long long eg_seq = 0;
 	hipStream_t eg_copy = nullptr;            // the fetches of dvp_edge_map_finish (any thread)
@@ -1430,11 +1430,10 @@ int dvp_ctx_destroy(dvp_ctx* c) {
 	}
 	if (c->eg_copy) { (void)hipStreamSynchronize(c->eg_copy); (void)hipStreamDestroy(c->eg_copy); }
 	if (c->stream) (void)hipStreamSynchronize(c->stream);
-	for (auto& e : c->pv_enc) dvpjpeg::encoder_free(e);
 	dvpedge::scratch_free(c->eg);
 	dvpvc::scratch_free(c->vc);
-	dvpprior::scratch_free(c->pr);
-	for (auto& sl : c->eg_slot) { if (sl.map) (void)hipFree(sl.map); if (sl.done) (void)hipEventDestroy(sl.done); }
+	// (the other side stages' blocks — pv_enc, eg_slot[].map, pr — are released by `delete c` below)
+	for (auto& sl : c->eg_slot) if (sl.done) (void)hipEventDestroy(sl.done);
 	if (c->pv_total) (void)hipHostFree(c->pv_total);
 	if (c->pv_done) (void)hipEventDestroy(c->pv_done);
 	if (c->maps_host) (void)hipHostFree(c->maps_host);
@@ -2216,7 +2215,7 @@ static int ensure_edge_buffers(dvp_ctx* c, int slots) {
 	if (dvpedge::scratch_reserve(c->eg, c->L)) { c->error = "dvp_edge_map: out of device memory"; return 1; }
 	for (int k = 0; k < slots; ++k) {
 		dvp_ctx::EdgeSlot& sl = c->eg_slot[k];
-		if (!sl.map && hipMalloc(reinterpret_cast<void**>(&sl.map), c->L) != hipSuccess) { (void)hipGetLastError(); sl.map = nullptr; c->error = "dvp_edge_map: out of device memory"; return 1; }
+		if (sl.map.reserve(c->L)) { c->error = "dvp_edge_map: out of device memory"; return 1; }
 		if (!sl.done && hipEventCreateWithFlags(&sl.done, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); sl.done = nullptr; c->error = "dvp_edge_map: hipEventCreate failed"; return 1; }
 	}
 	return 0;
@@ -2461,7 +2460,7 @@ int dvp_edge_map_begin(dvp_ctx* c, int install) {
 	// image 0 of the row-pair planes: texel (x, y) is the first float of pair (x, y) (dvp_dev.hpp img_texel)
 	const float* img0 = c->images + (size_t)c->d.org * 2;
 	if (dvpedge::launch_grey_from_float(c->stream, c->eg, img0, (long long)c->pitch, 2, c->W, c->H) || dvpedge::launch_suppress(c->stream, c->eg, c->W, c->H, true) ||
-	    dvpedge::launch_hysteresis(c->stream, c->eg, c->W, c->H) || dvpedge::launch_fixups(c->stream, c->eg, c->W, c->H, sl.map, install ? c->edge : nullptr)) {
+	    dvpedge::launch_hysteresis(c->stream, c->eg, c->W, c->H) || dvpedge::launch_fixups(c->stream, c->eg, c->W, c->H, sl.map.as<uint8_t>(), install ? c->edge : nullptr)) {
 		c->error = "dvp_edge_map_begin: launch failed"; return 1;
 	}
 	HIP_TRY(c, hipEventRecord(sl.done, c->stream));
@@ -2488,7 +2487,7 @@ int dvp_edge_map_finish(dvp_ctx* c, uint8_t* edge) {
 	}
 	dvp_ctx::EdgeSlot& sl = c->eg_slot[k];
 	// (two fetches at once share eg_copy: they queue behind each other, each waits for its own copy)
-	const bool ok = hipEventSynchronize(sl.done) == hipSuccess && hipMemcpyAsync(edge, sl.map, c->L, hipMemcpyDeviceToHost, c->eg_copy) == hipSuccess &&
+	const bool ok = hipEventSynchronize(sl.done) == hipSuccess && hipMemcpyAsync(edge, sl.map.as<uint8_t>(), c->L, hipMemcpyDeviceToHost, c->eg_copy) == hipSuccess &&
 	                hipStreamSynchronize(c->eg_copy) == hipSuccess;
 	{
 		std::lock_guard<std::mutex> lk(c->eg_m);
@@ -2544,7 +2543,7 @@ int dvp_preview_finish(dvp_ctx* c, int kind, uint8_t* dst, long long capacity, l
 	if (bytes) *bytes = n;
 	if (!dst || capacity < n) { t_finish_error.msg = "dvp_preview_finish: capacity below the encoded size (*bytes)"; return 1; }
 	memcpy(dst, e.header, e.header_len);
-	if (hipMemcpyAsync(dst + e.header_len, e.out, e.data_bytes, hipMemcpyDeviceToHost, c->pv_copy) != hipSuccess || hipStreamSynchronize(c->pv_copy) != hipSuccess) {
+	if (hipMemcpyAsync(dst + e.header_len, e.out.as<uint8_t>(), e.data_bytes, hipMemcpyDeviceToHost, c->pv_copy) != hipSuccess || hipStreamSynchronize(c->pv_copy) != hipSuccess) {
 		t_finish_error.msg = "dvp_preview_finish: copy to the host failed"; return 1;
 	}
 	dst[n - 2] = 0xFF;
@@ -2659,10 +2658,6 @@ int dvp_reset_timings(dvp_ctx* c) {
 
 // ---- KAT / micro-benchmark ---------------------------------------------------------------------
 namespace {
-struct DevBuf {   // hipMalloc'ed scratch released on every exit path
-	void* p = nullptr;
-	~DevBuf() { if (p) (void)hipFree(p); }
-};
 struct EventPairGuard {
 	hipEvent_t a = nullptr, b = nullptr;
 	~EventPairGuard() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
@@ -2674,20 +2669,18 @@ int dvp_eval_cost_vectors(dvp_ctx* c, const int32_t* px, const float* planes, in
 	if (!c->sector_taps) { c->error = "dvp_set_params must be called first"; return 1; }
 	if (n <= 0) return 0;
 	const size_t S = (size_t)c->NI - 1;
-	DevBuf dpx, dpl, dout;
+	dvpmem::DevBlock dpx, dpl, dout;
 	EventPairGuard ev;
-	HIP_TRY(c, hipMalloc(&dpx.p, (size_t)n * 8));
-	HIP_TRY(c, hipMalloc(&dpl.p, (size_t)n * 16));
-	HIP_TRY(c, hipMalloc(&dout.p, (size_t)n * S * 4));
-	HIP_TRY(c, hipMemcpyAsync(dpx.p, px, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
-	HIP_TRY(c, hipMemcpyAsync(dpl.p, planes, (size_t)n * 16, hipMemcpyHostToDevice, c->stream));
+	if (dpx.reserve((size_t)n * 8) || dpl.reserve((size_t)n * 16) || dout.reserve((size_t)n * S * 4)) { c->error = "dvp_eval_cost_vectors: out of device memory"; return 1; }
+	HIP_TRY(c, hipMemcpyAsync(dpx.as<void>(), px, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+	HIP_TRY(c, hipMemcpyAsync(dpl.as<void>(), planes, (size_t)n * 16, hipMemcpyHostToDevice, c->stream));
 	HIP_TRY(c, hipEventCreate(&ev.a));
 	HIP_TRY(c, hipEventCreate(&ev.b));
 	HIP_TRY(c, hipEventRecord(ev.a, c->stream));
-	hipLaunchKernelGGL(dvp_cost_vectors, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->d, (const int*)dpx.p, (const f4*)dpl.p, n, (float*)dout.p);
+	hipLaunchKernelGGL(dvp_cost_vectors, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->d, dpx.as<const int>(), dpl.as<const f4>(), n, dout.as<float>());
 	HIP_TRY(c, hipGetLastError());
 	HIP_TRY(c, hipEventRecord(ev.b, c->stream));
-	HIP_TRY(c, hipMemcpyAsync(out, dout.p, (size_t)n * S * 4, hipMemcpyDeviceToHost, c->stream));
+	HIP_TRY(c, hipMemcpyAsync(out, dout.as<float>(), (size_t)n * S * 4, hipMemcpyDeviceToHost, c->stream));
 	HIP_TRY(c, hipStreamSynchronize(c->stream));
 	if (kernel_ms) HIP_TRY(c, hipEventElapsedTime(kernel_ms, ev.a, ev.b));
 	return 0;

@@ -25,12 +25,14 @@
 //   3. fuse_emit     accepted pixels in raster order (block counts + ranks inside a block): position, mean colour of the
 //                    pixel and its witnesses, and the witnesses' claim flags.
 // Same points, same order, same bits as the sequential scan (tests/test_host_oracles.py).
+#include "dvp_devmem.hpp"
 #include "dvp_fuse_math.hpp"
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <utility>
 #include <vector>
 
 using namespace dvp;
@@ -475,56 +477,62 @@ __global__ void __launch_bounds__(1024) graded_emit(const GradedEmitArgs a) {
 // ------------------------------------------------------------------------------------------------
 // the job
 // ------------------------------------------------------------------------------------------------
+using dvpmem::DevBlock;
+
+// scratch arrays sized by (pixels, sources): reserved all or none, and never for less than an earlier call asked for
+struct FuseGroup { size_t cap_L = 0; int cap_ns = 0; };
+using FuseParts = std::vector<std::pair<DevBlock*, size_t>>;   // a group's blocks and their sizes in bytes
+
 struct dvp_fuse {
 	int device = 0;
 	int num_views = 0;
 	hipStream_t stream = nullptr;
 	std::vector<FuseView> views;          // host copies (device pointers inside)
 	std::vector<char> have;
-	FuseView* views_dev = nullptr;
+	DevBlock views_dev;                   // FuseView [num_views]
 	bool views_dirty = true;
-	std::vector<void*> allocs;
+	std::vector<DevBlock> allocs;         // the views' maps
 	// per-call scratch (grown on demand)
-	size_t cap_L = 0;
-	int cap_ns = 0;
-	int *cand_view = nullptr, *cand_pix = nullptr, *src_dev = nullptr;
-	float* cand_vote = nullptr;
-	signed char* count = nullptr;
-	uint8_t* decision = nullptr;
-	unsigned long long* live = nullptr;
-	unsigned *list_a = nullptr, *list_b = nullptr, *counters = nullptr, *block_count = nullptr;
-	unsigned long long* block_base = nullptr;
+	FuseGroup cap;
+	DevBlock cand_view, cand_pix, src_dev;        // int
+	DevBlock cand_vote;                           // float
+	DevBlock count;                               // signed char
+	DevBlock decision;                            // uint8_t
+	DevBlock live;                                // unsigned long long
+	DevBlock list_a, list_b, counters, block_count;   // unsigned
+	DevBlock block_base;                          // unsigned long long
 	// the graded variants' extra arrays
-	float *g_rel = nullptr, *g_ang = nullptr;
-	int *g_last = nullptr, *g_block_last = nullptr, *g_block_carry = nullptr;
-	size_t g_cap_L = 0;
-	int g_cap_ns = 0;
+	FuseGroup g_cap;
+	DevBlock g_rel, g_ang;                        // float
+	DevBlock g_last, g_block_last, g_block_carry; // int
 	unsigned round_serial = 0, view_serial = 0;
 	// the cloud: one device block per fused view
-	struct Segment { float* dev; long long n; };
+	struct Segment { DevBlock dev; long long n; };
 	std::vector<Segment> segments;
 	long long total = 0;
 	int last_rounds = 0, last_rest = 0;
 	std::string error;
 };
 
-static std::string g_fuse_create_error;
+static thread_local dvpmem::CallError t_fuse_create_error;
 #define FUSE_TRY(f, expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { (f)->error = std::string(#expr) + ": " + hipGetErrorString(e_); return 1; } } while (0)
 
 extern "C" {
 
 int dvp_fuse_create(int device, int num_views, dvp_fuse** out) {
-	if (!out || num_views <= 0) { g_fuse_create_error = "dvp_fuse_create: bad arguments"; return 1; }
-	if (hipSetDevice(device) != hipSuccess) { g_fuse_create_error = "dvp_fuse_create: hipSetDevice failed (no GPU?)"; return 1; }
+	const char* who = "dvp_fuse_create";
+	if (!out || num_views <= 0) return t_fuse_create_error.fail(who, "bad arguments");
+	if (hipSetDevice(device) != hipSuccess) return t_fuse_create_error.fail(who, "hipSetDevice failed (no GPU?)");
 	dvp_fuse* f = new dvp_fuse;
 	f->device = device;
 	f->num_views = num_views;
 	f->views.resize(num_views);
 	f->have.assign(num_views, 0);
-	if (hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking) != hipSuccess || hipMalloc((void**)&f->views_dev, sizeof(FuseView) * num_views) != hipSuccess) {
-		g_fuse_create_error = "dvp_fuse_create: stream / allocation failed";
+	if (hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); f->stream = nullptr; }
+	if (!f->stream || f->views_dev.reserve(sizeof(FuseView) * num_views)) {
+		if (f->stream) (void)hipStreamDestroy(f->stream);
 		delete f;
-		return 1;
+		return t_fuse_create_error.fail(who, "stream / allocation failed");
 	}
 	*out = f;
 	return 0;
@@ -533,24 +541,17 @@ int dvp_fuse_create(int device, int num_views, dvp_fuse** out) {
 int dvp_fuse_destroy(dvp_fuse* f) {
 	if (!f) return 0;
 	(void)hipSetDevice(f->device);
-	if (f->stream) (void)hipStreamSynchronize(f->stream);
-	for (void* p : f->allocs) (void)hipFree(p);
-	for (auto& s : f->segments) (void)hipFree(s.dev);
-	(void)hipFree(f->views_dev);
-	for (void* p : { (void*)f->g_rel, (void*)f->g_ang, (void*)f->g_last, (void*)f->g_block_last, (void*)f->g_block_carry })
-		if (p) (void)hipFree(p);
-	for (void* p : { (void*)f->cand_view, (void*)f->cand_pix, (void*)f->cand_vote, (void*)f->count, (void*)f->decision, (void*)f->live, (void*)f->list_a, (void*)f->list_b,
-	                 (void*)f->counters, (void*)f->block_count, (void*)f->block_base, (void*)f->src_dev })
-		if (p) (void)hipFree(p);
-	if (f->stream) (void)hipStreamDestroy(f->stream);
-	delete f;
+	(void)hipStreamSynchronize(f->stream);
+	(void)hipStreamDestroy(f->stream);
+	delete f;   // frees every block
 	return 0;
 }
 
-const char* dvp_fuse_last_error(const dvp_fuse* f) { return f ? f->error.c_str() : g_fuse_create_error.c_str(); }
+const char* dvp_fuse_last_error(const dvp_fuse* f) { return f ? f->error.c_str() : t_fuse_create_error.c_str(); }
 
 // The maps of view slot `v` (host pointers; copied).  `cam` is the camera AS THE FUSION SEES IT: intrinsics already rescaled to
 // the maps' size (RescaleImageAndCamera, APD.cpp:1750-1771).  weak == null: every pixel STRONG; block == null: no mask.
+// After a failure the slot is still unset and may be set again.
 int dvp_fuse_set_view(dvp_fuse* f, int v, const DvpCamera* cam, int cols, int rows, const float* depth, const float* normal_xyz,
                       const uint8_t* weak, const uint8_t* bgr, const uint8_t* block) {
 	if (!f) return 1;
@@ -565,10 +566,17 @@ int dvp_fuse_set_view(dvp_fuse* f, int v, const DvpCamera* cam, int cols, int ro
 	for (int k = 0; k < 3; ++k) fv.centre[k] = -(cam->R[0 + k] * cam->t[0] + cam->R[3 + k] * cam->t[1] + cam->R[6 + k] * cam->t[2]);
 	fv.cols = cols;
 	fv.rows = rows;
+	// this call's blocks: the job's once all of them stand, else freed when the stream has let go of them
+	struct Mine { hipStream_t stream; std::vector<DevBlock> blocks; ~Mine() { if (!blocks.empty()) (void)hipStreamSynchronize(stream); } } mine{ f->stream, {} };
+	auto block_of = [&](size_t bytes) -> void* {
+		DevBlock b;
+		if (b.reserve(bytes)) { f->error = "dvp_fuse_set_view: out of device memory"; return nullptr; }
+		mine.blocks.push_back(std::move(b));
+		return mine.blocks.back().as<void>();
+	};
 	auto up = [&](const void* src, size_t bytes, const void** dst) -> int {
-		void* p = nullptr;
-		if (hipMalloc(&p, bytes) != hipSuccess) { f->error = "dvp_fuse_set_view: out of device memory"; return 1; }
-		f->allocs.push_back(p);
+		void* p = block_of(bytes);
+		if (!p) return 1;
 		if (hipMemcpyAsync(p, src, bytes, hipMemcpyHostToDevice, f->stream) != hipSuccess) { f->error = "dvp_fuse_set_view: upload failed"; return 1; }
 		*dst = p;
 		return 0;
@@ -576,9 +584,8 @@ int dvp_fuse_set_view(dvp_fuse* f, int v, const DvpCamera* cam, int cols, int ro
 	if (up(depth, L * 4, (const void**)&fv.depth) || up(normal_xyz, L * 12, (const void**)&fv.normal) || up(bgr, L * 3, (const void**)&fv.bgr)) return 1;
 	if (weak && up(weak, L, (const void**)&fv.weak)) return 1;
 	if (block && up(block, L, (const void**)&fv.block)) return 1;
-	void *cl = nullptr, *und = nullptr, *acc = nullptr;
-	if (hipMalloc(&cl, L) != hipSuccess || hipMalloc(&und, L * 8) != hipSuccess || hipMalloc(&acc, L * 8) != hipSuccess) { f->error = "dvp_fuse_set_view: out of device memory"; return 1; }
-	f->allocs.push_back(cl); f->allocs.push_back(und); f->allocs.push_back(acc);
+	void *cl = block_of(L), *und = cl ? block_of(L * 8) : nullptr, *acc = und ? block_of(L * 8) : nullptr;
+	if (!acc) return 1;
 	FUSE_TRY(f, hipMemsetAsync(cl, 0, L, f->stream));
 	FUSE_TRY(f, hipMemsetAsync(und, 0xFF, L * 8, f->stream));
 	FUSE_TRY(f, hipMemsetAsync(acc, 0xFF, L * 8, f->stream));
@@ -586,38 +593,98 @@ int dvp_fuse_set_view(dvp_fuse* f, int v, const DvpCamera* cam, int cols, int ro
 	fv.und = (unsigned long long*)und;
 	fv.acc = (unsigned long long*)acc;
 	FUSE_TRY(f, hipStreamSynchronize(f->stream));   // the caller's buffers are free again
+	for (DevBlock& b : mine.blocks) f->allocs.push_back(std::move(b));
+	mine.blocks.clear();
 	f->views[v] = fv;
 	f->have[v] = 1;
 	f->views_dirty = true;
 	return 0;
 }
 
-static int fuse_reserve(dvp_fuse* f, size_t L, int ns) {
-	if (L <= f->cap_L && ns <= f->cap_ns) return 0;
-	const size_t nL = std::max(L, f->cap_L);
-	const int nn = std::max(ns, f->cap_ns);
-	for (void** p : { (void**)&f->cand_view, (void**)&f->cand_pix, (void**)&f->cand_vote, (void**)&f->count, (void**)&f->decision, (void**)&f->live, (void**)&f->list_a,
-	                  (void**)&f->list_b, (void**)&f->counters, (void**)&f->block_count, (void**)&f->block_base, (void**)&f->src_dev }) {
-		if (*p) (void)hipFree(*p);
-		*p = nullptr;
-	}
-	f->cap_L = 0;
-	f->cap_ns = 0;
-	const size_t blocks = (nL + 1023) / 1024;
-	if (hipMalloc((void**)&f->cand_view, (size_t)nn * nL * 4) != hipSuccess || hipMalloc((void**)&f->cand_pix, (size_t)nn * nL * 4) != hipSuccess ||
-	    hipMalloc((void**)&f->cand_vote, (size_t)nn * nL * 4) != hipSuccess || hipMalloc((void**)&f->count, nL) != hipSuccess ||
-	    hipMalloc((void**)&f->decision, nL) != hipSuccess || hipMalloc((void**)&f->live, nL * 8) != hipSuccess ||
-	    hipMalloc((void**)&f->list_a, nL * 4) != hipSuccess || hipMalloc((void**)&f->list_b, nL * 4) != hipSuccess ||
-	    hipMalloc((void**)&f->counters, 16) != hipSuccess || hipMalloc((void**)&f->block_count, blocks * 4) != hipSuccess ||
-	    hipMalloc((void**)&f->block_base, blocks * 8) != hipSuccess || hipMalloc((void**)&f->src_dev, (size_t)std::max(nn, 1) * 4) != hipSuccess) {
-		(void)hipGetLastError();
-		f->error = "dvp_fuse_view: out of device memory for the candidate lists";
-		return 1;
-	}
-	f->cap_L = nL;
-	f->cap_ns = nn;
+}  // extern "C"
+
+static FuseParts plain_parts(dvp_fuse* f, size_t nL, int nn) {
+	const size_t blocks = (nL + 1023) / 1024, per_src = (size_t)nn * nL * 4;
+	return { { &f->cand_view, per_src }, { &f->cand_pix, per_src }, { &f->cand_vote, per_src }, { &f->count, nL }, { &f->decision, nL }, { &f->live, nL * 8 },
+	         { &f->list_a, nL * 4 }, { &f->list_b, nL * 4 }, { &f->counters, 16 }, { &f->block_count, blocks * 4 }, { &f->block_base, blocks * 8 },
+	         { &f->src_dev, (size_t)std::max(nn, 1) * 4 } };
+}
+static FuseParts graded_parts(dvp_fuse* f, size_t nL, int nn) {
+	const size_t nb = (nL + kGradedBlock - 1) / kGradedBlock, per_src = (size_t)nn * nL * 4;
+	return { { &f->g_rel, per_src }, { &f->g_ang, per_src }, { &f->g_last, per_src }, { &f->g_block_last, nb * nn * 4 }, { &f->g_block_carry, nb * nn * 4 } };
+}
+
+// A group that is too small is freed as a whole and made again for the larger of (what is asked, what it held); a refusal leaves
+// the whole group empty.
+static int fuse_reserve(dvp_fuse* f, FuseGroup& g, FuseParts (*parts_of)(dvp_fuse*, size_t, int), size_t L, int ns, const char* refused) {
+	if (L <= g.cap_L && ns <= g.cap_ns) return 0;
+	const size_t nL = std::max(L, g.cap_L);
+	const int nn = std::max(ns, g.cap_ns);
+	const FuseParts parts = parts_of(f, nL, nn);
+	g = FuseGroup();
+	for (const auto& p : parts) p.first->release();
+	for (const auto& p : parts)
+		if (p.first->reserve(p.second)) {
+			for (const auto& q : parts) q.first->release();
+			f->error = refused;
+			return 1;
+		}
+	g = FuseGroup{ nL, nn };
 	return 0;
 }
+
+// What dvp_fuse_view and dvp_fuse_view_graded begin with: the argument checks (graded: a source slot may be negative, "no maps"),
+// the views' descriptors when a view was set since the last call, the scratch (graded: its extra arrays too), then the source
+// list — queued after every reserve, so a refusal leaves no copy from the caller's memory pending.  *L = the view's pixels.
+static int fuse_begin(dvp_fuse* f, const char* who, int v, const int* src, int num_src, bool graded, size_t* L) {
+	auto fail = [f, who](const char* what) { f->error = std::string(who) + ": " + what; return 1; };
+	if (v < 0 || v >= f->num_views || !f->have[v] || num_src < 0 || (num_src > 0 && !src)) return fail("bad arguments");
+	if (num_src > 64) return fail("more than 64 source views");
+	for (int j = 0; j < num_src; ++j)
+		if (src[j] >= f->num_views || (src[j] < 0 ? !graded : !f->have[src[j]])) return fail("bad source slot");
+	FUSE_TRY(f, hipSetDevice(f->device));
+	if (f->views_dirty) {
+		FUSE_TRY(f, hipMemcpyAsync(f->views_dev.as<void>(), f->views.data(), sizeof(FuseView) * f->num_views, hipMemcpyHostToDevice, f->stream));
+		FUSE_TRY(f, hipStreamSynchronize(f->stream));
+		f->views_dirty = false;
+	}
+	*L = (size_t)f->views[v].cols * f->views[v].rows;
+	if (fuse_reserve(f, f->cap, plain_parts, *L, std::max(num_src, 1), "dvp_fuse_view: out of device memory for the candidate lists")) return 1;
+	if (graded && fuse_reserve(f, f->g_cap, graded_parts, *L, std::max(num_src, 1), "dvp_fuse_view_graded: out of device memory")) return 1;
+	if (num_src > 0) FUSE_TRY(f, hipMemcpyAsync(f->src_dev.as<void>(), src, (size_t)num_src * 4, hipMemcpyHostToDevice, f->stream));
+	return 0;
+}
+
+// What they end with, once f->decision is final: the accepted pixels per block of 1024, their prefix sum (on the host), the
+// view's segment of the cloud, and `emit` writing the points in raster order.  args.block_base and args.out are set here.
+template <class Args>
+static int fuse_finish(dvp_fuse* f, const char* who, size_t L, void (*emit)(const Args), Args args) {
+	EmitArgs ca{};
+	ca.decision = f->decision.as<uint8_t>(); ca.L = L; ca.block_count = f->block_count.as<unsigned>();
+	const unsigned blocks = (unsigned)((L + 1023) / 1024);
+	hipLaunchKernelGGL(fuse_count, dim3(blocks), dim3(1024), 0, f->stream, ca);
+	FUSE_TRY(f, hipGetLastError());
+	std::vector<unsigned> bc(blocks);
+	FUSE_TRY(f, hipMemcpyAsync(bc.data(), ca.block_count, (size_t)blocks * 4, hipMemcpyDeviceToHost, f->stream));
+	FUSE_TRY(f, hipStreamSynchronize(f->stream));   // (also: the host arrays of earlier copies on the stream have been read)
+	std::vector<unsigned long long> base(blocks);
+	unsigned long long n_points = 0;
+	for (unsigned b = 0; b < blocks; ++b) { base[b] = n_points; n_points += bc[b]; }
+	if (n_points == 0) return 0;
+	DevBlock seg;
+	if (seg.reserve((size_t)n_points * 24)) { f->error = std::string(who) + ": out of device memory for the points"; return 1; }
+	args.out = seg.as<float>();
+	args.block_base = f->block_base.as<unsigned long long>();
+	f->segments.push_back(dvp_fuse::Segment{ std::move(seg), (long long)n_points });
+	FUSE_TRY(f, hipMemcpyAsync(f->block_base.as<void>(), base.data(), (size_t)blocks * 8, hipMemcpyHostToDevice, f->stream));
+	hipLaunchKernelGGL(emit, dim3(blocks), dim3(1024), 0, f->stream, args);
+	FUSE_TRY(f, hipGetLastError());
+	FUSE_TRY(f, hipStreamSynchronize(f->stream));   // `base` is read by the copy above
+	f->total += (long long)n_points;
+	return 0;
+}
+
+extern "C" {
 
 // A round is two small launches and one 4-byte read-back (~30 us); a long dependency chain — pixels along a row sharing witnesses
 // pairwise — shrinks the undecided list slowly in its tail.  The rounds go on while the list is worth a launch; a short rest
@@ -635,41 +702,29 @@ static int fuse_reserve(dvp_fuse* f, size_t L, int ns) {
 // a witness and is claimed with the point.  Nothing here needs to know: the pixel is the only lister of that candidate.
 int dvp_fuse_view(dvp_fuse* f, int v, const int* src, int num_src) {
 	if (!f) return 1;
-	if (v < 0 || v >= f->num_views || !f->have[v] || num_src < 0 || (num_src > 0 && !src)) { f->error = "dvp_fuse_view: bad arguments"; return 1; }
-	if (num_src > 64) { f->error = "dvp_fuse_view: more than 64 source views"; return 1; }
-	for (int j = 0; j < num_src; ++j)
-		if (src[j] < 0 || src[j] >= f->num_views || !f->have[src[j]]) { f->error = "dvp_fuse_view: bad source slot"; return 1; }
-	FUSE_TRY(f, hipSetDevice(f->device));
-	if (f->views_dirty) {
-		FUSE_TRY(f, hipMemcpyAsync(f->views_dev, f->views.data(), sizeof(FuseView) * f->num_views, hipMemcpyHostToDevice, f->stream));
-		FUSE_TRY(f, hipStreamSynchronize(f->stream));
-		f->views_dirty = false;
-	}
-	const FuseView& R = f->views[v];
-	const size_t L = (size_t)R.cols * R.rows;
-	if (fuse_reserve(f, L, std::max(num_src, 1))) return 1;
-	if (num_src > 0) FUSE_TRY(f, hipMemcpyAsync(f->src_dev, src, (size_t)num_src * 4, hipMemcpyHostToDevice, f->stream));
-	const size_t capL = f->cap_L;   // stride of the candidate arrays is the view's own L (passed as a.L below), the capacity only bounds it
-	(void)capL;
+	size_t L = 0;
+	if (fuse_begin(f, "dvp_fuse_view", v, src, num_src, false, &L)) return 1;
+	const FuseView* views_dev = f->views_dev.as<FuseView>();
+	unsigned* counters = f->counters.as<unsigned>();
 	GatherArgs ga;
-	ga.views = f->views_dev; ga.ref = v; ga.ns = num_src; ga.src = f->src_dev;
-	ga.cand_view = f->cand_view; ga.cand_pix = f->cand_pix; ga.cand_vote = f->cand_vote; ga.count = f->count;
+	ga.views = views_dev; ga.ref = v; ga.ns = num_src; ga.src = f->src_dev.as<int>();
+	ga.cand_view = f->cand_view.as<int>(); ga.cand_pix = f->cand_pix.as<int>(); ga.cand_vote = f->cand_vote.as<float>(); ga.count = f->count.as<signed char>();
 	const unsigned gL = (unsigned)((L + 255) / 256);
 	hipLaunchKernelGGL(fuse_gather, dim3(gL), dim3(256), 0, f->stream, ga);
-	FUSE_TRY(f, hipMemsetAsync(f->decision, 0, L, f->stream));
-	FUSE_TRY(f, hipMemsetAsync(f->counters, 0, 16, f->stream));
-	hipLaunchKernelGGL(fuse_first_list, dim3(gL), dim3(256), 0, f->stream, f->count, L, f->list_a, f->counters);
+	FUSE_TRY(f, hipMemsetAsync(f->decision.as<void>(), 0, L, f->stream));
+	FUSE_TRY(f, hipMemsetAsync(counters, 0, 16, f->stream));
+	hipLaunchKernelGGL(fuse_first_list, dim3(gL), dim3(256), 0, f->stream, ga.count, L, f->list_a.as<unsigned>(), counters);
 	FUSE_TRY(f, hipGetLastError());
 	unsigned n_list = 0;
-	FUSE_TRY(f, hipMemcpyAsync(&n_list, f->counters, 4, hipMemcpyDeviceToHost, f->stream));
+	FUSE_TRY(f, hipMemcpyAsync(&n_list, counters, 4, hipMemcpyDeviceToHost, f->stream));
 	FUSE_TRY(f, hipStreamSynchronize(f->stream));
 	ResolveArgs ra;
-	ra.views = f->views_dev; ra.ref = v; ra.ns = num_src;
-	ra.cand_view = f->cand_view; ra.cand_pix = f->cand_pix; ra.cand_vote = f->cand_vote; ra.count = f->count;
-	ra.decision = f->decision; ra.live = f->live; ra.L = L;
+	ra.views = views_dev; ra.ref = v; ra.ns = num_src;
+	ra.cand_view = ga.cand_view; ra.cand_pix = ga.cand_pix; ra.cand_vote = ga.cand_vote; ra.count = ga.count;
+	ra.decision = f->decision.as<uint8_t>(); ra.live = f->live.as<unsigned long long>(); ra.L = L;
 	ra.view_hi = ~(++f->view_serial);
-	unsigned* cur = f->list_a;
-	unsigned* nxt = f->list_b;
+	unsigned* cur = f->list_a.as<unsigned>();
+	unsigned* nxt = f->list_b.as<unsigned>();
 	int rounds = 0;
 	f->last_rest = 0;
 	while (n_list > 0) {
@@ -687,14 +742,14 @@ int dvp_fuse_view(dvp_fuse* f, int v, const int* src, int num_src) {
 			break;
 		}
 		ra.round_hi = ~(++f->round_serial);
-		ra.list = cur; ra.n_list = n_list; ra.next = nxt; ra.n_next = f->counters + 1;
-		FUSE_TRY(f, hipMemsetAsync(f->counters + 1, 0, 4, f->stream));
+		ra.list = cur; ra.n_list = n_list; ra.next = nxt; ra.n_next = counters + 1;
+		FUSE_TRY(f, hipMemsetAsync(counters + 1, 0, 4, f->stream));
 		const unsigned g = (n_list + 255) / 256;
 		hipLaunchKernelGGL(fuse_mark, dim3(g), dim3(256), 0, f->stream, ra);
 		hipLaunchKernelGGL(fuse_decide, dim3(g), dim3(256), 0, f->stream, ra);
 		FUSE_TRY(f, hipGetLastError());
 		unsigned n_next = 0;
-		FUSE_TRY(f, hipMemcpyAsync(&n_next, f->counters + 1, 4, hipMemcpyDeviceToHost, f->stream));
+		FUSE_TRY(f, hipMemcpyAsync(&n_next, counters + 1, 4, hipMemcpyDeviceToHost, f->stream));
 		FUSE_TRY(f, hipStreamSynchronize(f->stream));
 		if (n_next >= n_list) { f->error = "dvp_fuse_view: a resolve round decided nothing"; return 1; }   // (cannot happen: the smallest undecided index always decides)
 		std::swap(cur, nxt);
@@ -702,31 +757,10 @@ int dvp_fuse_view(dvp_fuse* f, int v, const int* src, int num_src) {
 		++rounds;
 	}
 	f->last_rounds = rounds;
-	// accepted pixels in raster order
-	EmitArgs ea;
-	ea.views = f->views_dev; ea.ref = v; ea.cand_view = f->cand_view; ea.cand_pix = f->cand_pix; ea.count = f->count;
-	ea.decision = f->decision; ea.live = f->live; ea.L = L; ea.block_count = f->block_count; ea.block_base = f->block_base; ea.out = nullptr;
-	const unsigned blocks = (unsigned)((L + 1023) / 1024);
-	hipLaunchKernelGGL(fuse_count, dim3(blocks), dim3(1024), 0, f->stream, ea);
-	FUSE_TRY(f, hipGetLastError());
-	std::vector<unsigned> bc(blocks);
-	FUSE_TRY(f, hipMemcpyAsync(bc.data(), f->block_count, (size_t)blocks * 4, hipMemcpyDeviceToHost, f->stream));
-	FUSE_TRY(f, hipStreamSynchronize(f->stream));
-	std::vector<unsigned long long> base(blocks);
-	unsigned long long n_points = 0;
-	for (unsigned b = 0; b < blocks; ++b) { base[b] = n_points; n_points += bc[b]; }
-	if (n_points > 0) {
-		float* seg = nullptr;
-		if (hipMalloc((void**)&seg, (size_t)n_points * 24) != hipSuccess) { (void)hipGetLastError(); f->error = "dvp_fuse_view: out of device memory for the points"; return 1; }
-		f->segments.push_back(dvp_fuse::Segment{ seg, (long long)n_points });
-		FUSE_TRY(f, hipMemcpyAsync(f->block_base, base.data(), (size_t)blocks * 8, hipMemcpyHostToDevice, f->stream));
-		ea.out = seg;
-		hipLaunchKernelGGL(fuse_emit, dim3(blocks), dim3(1024), 0, f->stream, ea);
-		FUSE_TRY(f, hipGetLastError());
-		FUSE_TRY(f, hipStreamSynchronize(f->stream));   // `base` is read by the copy above
-		f->total += (long long)n_points;
-	}
-	return 0;
+	EmitArgs ea{};
+	ea.views = views_dev; ea.ref = v; ea.cand_view = ga.cand_view; ea.cand_pix = ga.cand_pix; ea.count = ga.count;
+	ea.decision = ra.decision; ea.live = ra.live; ea.L = L;
+	return fuse_finish(f, "dvp_fuse_view", L, fuse_emit, ea);
 }
 
 // One iteration of the outer loop of RunFusion_TAT_Intermediate (advanced = 0, APD.cpp:1962-2130) / RunFusion_TAT_advanced
@@ -734,46 +768,20 @@ int dvp_fuse_view(dvp_fuse* f, int v, const int* src, int num_src) {
 // part in the count of sources the acceptance loop runs to, but never yields a comparison).
 int dvp_fuse_view_graded(dvp_fuse* f, int v, const int* src, int num_src, int advanced) {
 	if (!f) return 1;
-	if (v < 0 || v >= f->num_views || !f->have[v] || num_src < 0 || (num_src > 0 && !src)) { f->error = "dvp_fuse_view_graded: bad arguments"; return 1; }
-	if (num_src > 64) { f->error = "dvp_fuse_view_graded: more than 64 source views"; return 1; }
-	for (int j = 0; j < num_src; ++j)
-		if (src[j] >= f->num_views || (src[j] >= 0 && !f->have[src[j]])) { f->error = "dvp_fuse_view_graded: bad source slot"; return 1; }
-	FUSE_TRY(f, hipSetDevice(f->device));
-	if (f->views_dirty) {
-		FUSE_TRY(f, hipMemcpyAsync(f->views_dev, f->views.data(), sizeof(FuseView) * f->num_views, hipMemcpyHostToDevice, f->stream));
-		FUSE_TRY(f, hipStreamSynchronize(f->stream));
-		f->views_dirty = false;
-	}
-	const FuseView& R = f->views[v];
-	const size_t L = (size_t)R.cols * R.rows;
+	size_t L = 0;
+	if (fuse_begin(f, "dvp_fuse_view_graded", v, src, num_src, true, &L)) return 1;
 	const int ns = std::max(num_src, 1);
-	if (fuse_reserve(f, L, ns)) return 1;
 	const unsigned gblocks = (unsigned)((L + kGradedBlock - 1) / kGradedBlock);
-	if (L > f->g_cap_L || ns > f->g_cap_ns) {
-		for (void** p : { (void**)&f->g_rel, (void**)&f->g_ang, (void**)&f->g_last, (void**)&f->g_block_last, (void**)&f->g_block_carry }) { if (*p) (void)hipFree(*p); *p = nullptr; }
-		const size_t nL = std::max(L, f->g_cap_L);
-		const int nn = std::max(ns, f->g_cap_ns);
-		const size_t nb = (nL + kGradedBlock - 1) / kGradedBlock;
-		f->g_cap_L = 0; f->g_cap_ns = 0;
-		if (hipMalloc((void**)&f->g_rel, (size_t)nn * nL * 4) != hipSuccess || hipMalloc((void**)&f->g_ang, (size_t)nn * nL * 4) != hipSuccess || hipMalloc((void**)&f->g_last, (size_t)nn * nL * 4) != hipSuccess ||
-		    hipMalloc((void**)&f->g_block_last, nb * nn * 4) != hipSuccess || hipMalloc((void**)&f->g_block_carry, nb * nn * 4) != hipSuccess) {
-			(void)hipGetLastError();
-			f->error = "dvp_fuse_view_graded: out of device memory";
-			return 1;
-		}
-		f->g_cap_L = nL; f->g_cap_ns = nn;
-	}
-	if (num_src > 0) FUSE_TRY(f, hipMemcpyAsync(f->src_dev, src, (size_t)num_src * 4, hipMemcpyHostToDevice, f->stream));
 	GradedArgs ga;
-	ga.views = f->views_dev; ga.ref = v; ga.ns = num_src; ga.advanced = advanced ? 1 : 0; ga.src = f->src_dev;
-	ga.f_err = f->cand_vote; ga.f_rel = f->g_rel; ga.f_ang = f->g_ang; ga.f_pix = f->cand_pix;
-	ga.is_ref = reinterpret_cast<uint8_t*>(f->count); ga.block_last = f->g_block_last; ga.block_carry = f->g_block_carry;
-	ga.last_idx = f->g_last; ga.decision = f->decision; ga.agree = f->live; ga.L = L;
+	ga.views = f->views_dev.as<FuseView>(); ga.ref = v; ga.ns = num_src; ga.advanced = advanced ? 1 : 0; ga.src = f->src_dev.as<int>();
+	ga.f_err = f->cand_vote.as<float>(); ga.f_rel = f->g_rel.as<float>(); ga.f_ang = f->g_ang.as<float>(); ga.f_pix = f->cand_pix.as<int>();
+	ga.is_ref = f->count.as<uint8_t>(); ga.block_last = f->g_block_last.as<int>(); ga.block_carry = f->g_block_carry.as<int>();
+	ga.last_idx = f->g_last.as<int>(); ga.decision = f->decision.as<uint8_t>(); ga.agree = f->live.as<unsigned long long>(); ga.L = L;
 	hipLaunchKernelGGL(graded_gather, dim3(gblocks), dim3(kGradedBlock), 0, f->stream, ga);
 	FUSE_TRY(f, hipGetLastError());
-	std::vector<int> last((size_t)gblocks * ns), carry((size_t)gblocks * ns);
+	std::vector<int> last((size_t)gblocks * ns), carry((size_t)gblocks * ns);   // (carry is read by a copy that fuse_finish waits for)
 	if (num_src > 0) {
-		FUSE_TRY(f, hipMemcpyAsync(last.data(), f->g_block_last, (size_t)gblocks * num_src * 4, hipMemcpyDeviceToHost, f->stream));
+		FUSE_TRY(f, hipMemcpyAsync(last.data(), ga.block_last, (size_t)gblocks * num_src * 4, hipMemcpyDeviceToHost, f->stream));
 		FUSE_TRY(f, hipStreamSynchronize(f->stream));
 		std::vector<int> run(num_src, -1);
 		for (unsigned b = 0; b < gblocks; ++b)
@@ -781,37 +789,15 @@ int dvp_fuse_view_graded(dvp_fuse* f, int v, const int* src, int num_src, int ad
 				carry[(size_t)b * num_src + j] = run[j];
 				run[j] = std::max(run[j], last[(size_t)b * num_src + j]);
 			}
-		FUSE_TRY(f, hipMemcpyAsync(f->g_block_carry, carry.data(), (size_t)gblocks * num_src * 4, hipMemcpyHostToDevice, f->stream));
+		FUSE_TRY(f, hipMemcpyAsync(f->g_block_carry.as<void>(), carry.data(), (size_t)gblocks * num_src * 4, hipMemcpyHostToDevice, f->stream));
 	}
 	hipLaunchKernelGGL(graded_decide, dim3(gblocks), dim3(kGradedBlock), 0, f->stream, ga);
 	FUSE_TRY(f, hipGetLastError());
-	EmitArgs ea;
-	ea.views = f->views_dev; ea.ref = v; ea.cand_view = nullptr; ea.cand_pix = nullptr; ea.count = nullptr;
-	ea.decision = f->decision; ea.live = nullptr; ea.L = L; ea.block_count = f->block_count; ea.block_base = f->block_base; ea.out = nullptr;
-	const unsigned blocks = (unsigned)((L + 1023) / 1024);
-	hipLaunchKernelGGL(fuse_count, dim3(blocks), dim3(1024), 0, f->stream, ea);
-	FUSE_TRY(f, hipGetLastError());
-	std::vector<unsigned> bc(blocks);
-	FUSE_TRY(f, hipMemcpyAsync(bc.data(), f->block_count, (size_t)blocks * 4, hipMemcpyDeviceToHost, f->stream));
-	FUSE_TRY(f, hipStreamSynchronize(f->stream));   // (also: `carry` has been read)
-	std::vector<unsigned long long> base(blocks);
-	unsigned long long n_points = 0;
-	for (unsigned b = 0; b < blocks; ++b) { base[b] = n_points; n_points += bc[b]; }
 	f->last_rounds = 0; f->last_rest = 0;
-	if (n_points > 0) {
-		float* seg = nullptr;
-		if (hipMalloc((void**)&seg, (size_t)n_points * 24) != hipSuccess) { (void)hipGetLastError(); f->error = "dvp_fuse_view_graded: out of device memory for the points"; return 1; }
-		f->segments.push_back(dvp_fuse::Segment{ seg, (long long)n_points });
-		FUSE_TRY(f, hipMemcpyAsync(f->block_base, base.data(), (size_t)blocks * 8, hipMemcpyHostToDevice, f->stream));
-		GradedEmitArgs ge;
-		ge.views = f->views_dev; ge.ref = v; ge.ns = num_src; ge.advanced = advanced ? 1 : 0; ge.src = f->src_dev; ge.last_idx = f->g_last; ge.f_pix = f->cand_pix;
-		ge.decision = f->decision; ge.agree = f->live; ge.L = L; ge.block_base = f->block_base; ge.out = seg;
-		hipLaunchKernelGGL(graded_emit, dim3(blocks), dim3(1024), 0, f->stream, ge);
-		FUSE_TRY(f, hipGetLastError());
-		FUSE_TRY(f, hipStreamSynchronize(f->stream));
-		f->total += (long long)n_points;
-	}
-	return 0;
+	GradedEmitArgs ge{};
+	ge.views = ga.views; ge.ref = v; ge.ns = num_src; ge.advanced = ga.advanced; ge.src = ga.src; ge.last_idx = ga.last_idx; ge.f_pix = ga.f_pix;
+	ge.decision = ga.decision; ge.agree = ga.agree; ge.L = L;
+	return fuse_finish(f, "dvp_fuse_view_graded", L, graded_emit, ge);
 }
 
 long long dvp_fuse_count(const dvp_fuse* f) { return f ? f->total : -1; }
@@ -831,7 +817,7 @@ int dvp_fuse_download(dvp_fuse* f, float* points) {
 	FUSE_TRY(f, hipSetDevice(f->device));
 	size_t off = 0;
 	for (const auto& s : f->segments) {
-		FUSE_TRY(f, hipMemcpyAsync(points + off, s.dev, (size_t)s.n * 24, hipMemcpyDeviceToHost, f->stream));
+		FUSE_TRY(f, hipMemcpyAsync(points + off, s.dev.as<void>(), (size_t)s.n * 24, hipMemcpyDeviceToHost, f->stream));
 		off += (size_t)s.n * 6;
 	}
 	FUSE_TRY(f, hipStreamSynchronize(f->stream));

@@ -100,17 +100,6 @@ int launch_render(hipStream_t stream, const float* planes, const uint8_t* weak, 
 // profiles/preview_jpeg.txt has R = 8).
 int default_restart(int channels) { return channels == 3 ? 8 : 32; }
 
-template <class T>
-static bool grow(T** p, size_t* alloc, size_t count) {
-	if (*p && *alloc >= count) return true;
-	if (*p) (void)hipFree(*p);
-	*p = nullptr;
-	*alloc = 0;
-	if (hipMalloc(reinterpret_cast<void**>(p), count * sizeof(T) > 0 ? count * sizeof(T) : 1) != hipSuccess) { (void)hipGetLastError(); *p = nullptr; return false; }
-	*alloc = count;
-	return true;
-}
-
 int encode_begin(Encoder& e, hipStream_t stream, const uint8_t* pixels, long long pitch, int W, int H, int C, int quality, int restart,
                  unsigned long long* total_host) {
 	e.error = nullptr;
@@ -125,48 +114,36 @@ int encode_begin(Encoder& e, hipStream_t stream, const uint8_t* pixels, long lon
 	e.nseg = (e.nmcu + e.R - 1) / e.R;
 	build_tables(quality, &e.tab);
 	e.header_len = build_header(&e.tab, W, H, C, e.R, e.header);
-	size_t one = 0;
-	if (!e.d_tab && !grow(&e.d_tab, &one, 1)) { e.error = "jpeg: out of device memory"; return 1; }
-	if (!grow(&e.coef, &e.coef_alloc, (size_t)e.nmcu * e.bpm * 64) || !grow(&e.mask, &e.mask_alloc, (size_t)e.nmcu * e.bpm)) { e.error = "jpeg: out of device memory"; return 1; }
-	if (e.seg_alloc < (size_t)e.nseg + 1) {
-		size_t a = e.seg_alloc;
-		if (!grow(&e.seglen, &a, (size_t)e.nseg + 1)) { e.error = "jpeg: out of device memory"; return 1; }
-		if (e.segoff) (void)hipFree(e.segoff);
-		e.segoff = nullptr;
-		e.seg_alloc = 0;
-		if (hipMalloc(reinterpret_cast<void**>(&e.segoff), ((size_t)e.nseg + 1) * 8) != hipSuccess) { (void)hipGetLastError(); e.segoff = nullptr; e.error = "jpeg: out of device memory"; return 1; }
-		e.seg_alloc = a;
-	}
-	if (hipMemcpyAsync(e.d_tab, &e.tab, sizeof(Tables), hipMemcpyHostToDevice, stream) != hipSuccess) { e.error = "jpeg: table upload failed"; return 1; }
+	const size_t blocks = (size_t)e.nmcu * e.bpm, segs = (size_t)e.nseg + 1;
+	if (e.d_tab.reserve(sizeof(Tables)) || e.coef.reserve(blocks * 64 * sizeof(int16_t)) || e.mask.reserve(blocks * sizeof(uint64_t)) ||
+	    e.seglen.reserve(segs * sizeof(unsigned)) || e.segoff.reserve(segs * sizeof(unsigned long long))) { e.error = "jpeg: out of device memory"; return 1; }
+	Tables* d_tab = e.d_tab.as<Tables>(); int16_t* coef = e.coef.as<int16_t>();
+	uint64_t* mask = e.mask.as<uint64_t>();
+	unsigned* seglen = e.seglen.as<unsigned>(); unsigned long long* segoff = e.segoff.as<unsigned long long>();
+	if (hipMemcpyAsync(d_tab, &e.tab, sizeof(Tables), hipMemcpyHostToDevice, stream) != hipSuccess) { e.error = "jpeg: table upload failed"; return 1; }
 	const unsigned g1 = (unsigned)((e.nmcu + 255) / 256), g2 = (unsigned)((e.nseg + 63) / 64);
-	if (C == 3) hipLaunchKernelGGL(dvp_jpeg_coefs_color, dim3(g1), dim3(256), 0, stream, pixels, pitch, W, H, (int)mcx, e.nmcu, e.d_tab, e.coef, e.mask);
-	else hipLaunchKernelGGL(dvp_jpeg_coefs_grey, dim3(g1), dim3(256), 0, stream, pixels, pitch, W, H, (int)mcx, e.nmcu, e.d_tab, e.coef, e.mask);
-	hipLaunchKernelGGL(dvp_jpeg_seg_size, dim3(g2), dim3(64), 0, stream, e.d_tab, e.coef, e.mask, e.nmcu, e.bpm, e.R, e.nseg, e.seglen);
-	hipLaunchKernelGGL(dvp_jpeg_scan, dim3(1), dim3(1024), 0, stream, e.seglen, e.nseg, e.segoff);
+	if (C == 3) hipLaunchKernelGGL(dvp_jpeg_coefs_color, dim3(g1), dim3(256), 0, stream, pixels, pitch, W, H, (int)mcx, e.nmcu, d_tab, coef, mask);
+	else hipLaunchKernelGGL(dvp_jpeg_coefs_grey, dim3(g1), dim3(256), 0, stream, pixels, pitch, W, H, (int)mcx, e.nmcu, d_tab, coef, mask);
+	hipLaunchKernelGGL(dvp_jpeg_seg_size, dim3(g2), dim3(64), 0, stream, d_tab, coef, mask, e.nmcu, e.bpm, e.R, e.nseg, seglen);
+	hipLaunchKernelGGL(dvp_jpeg_scan, dim3(1), dim3(1024), 0, stream, seglen, e.nseg, segoff);
 	if (hipGetLastError() != hipSuccess) { e.error = "jpeg: launch failed"; return 1; }
-	if (hipMemcpyAsync(total_host, e.segoff + e.nseg, 8, hipMemcpyDeviceToHost, stream) != hipSuccess) { e.error = "jpeg: size read-back failed"; return 1; }
+	if (hipMemcpyAsync(total_host, segoff + e.nseg, 8, hipMemcpyDeviceToHost, stream) != hipSuccess) { e.error = "jpeg: size read-back failed"; return 1; }
 	return 0;
 }
 
 int encode_write(Encoder& e, hipStream_t stream, unsigned long long total) {
 	e.error = nullptr;
-	if (!grow(&e.out, &e.out_alloc, (size_t)total)) { e.error = "jpeg: out of device memory"; return 1; }
+	if (e.out.reserve(total ? (size_t)total : 1)) { e.error = "jpeg: out of device memory"; return 1; }
 	e.data_bytes = total;
-	hipLaunchKernelGGL(dvp_jpeg_seg_write, dim3((unsigned)((e.nseg + 63) / 64)), dim3(64), 0, stream, e.d_tab, e.coef, e.mask, e.nmcu, e.bpm, e.R, e.nseg,
-	                   e.segoff, e.out);
+	hipLaunchKernelGGL(dvp_jpeg_seg_write, dim3((unsigned)((e.nseg + 63) / 64)), dim3(64), 0, stream, e.d_tab.as<Tables>(), e.coef.as<int16_t>(),
+	                   e.mask.as<uint64_t>(), e.nmcu, e.bpm, e.R, e.nseg, e.segoff.as<unsigned long long>(), e.out.as<uint8_t>());
 	if (hipGetLastError() != hipSuccess) { e.error = "jpeg: launch failed"; return 1; }
 	return 0;
 }
 
-void encoder_free(Encoder& e) {
-	for (void* p : { (void*)e.d_tab, (void*)e.coef, (void*)e.mask, (void*)e.seglen, (void*)e.segoff, (void*)e.out })
-		if (p) (void)hipFree(p);
-	e = Encoder();
-}
-
 }   // namespace dvpjpeg
 
-static thread_local std::string t_jpeg_error;
+static thread_local dvpmem::CallError t_jpeg_error;
 
 extern "C" const char* dvp_jpeg_last_error(void) { return t_jpeg_error.c_str(); }
 
@@ -181,34 +158,26 @@ extern "C" long long dvp_jpeg_bound(int width, int height, int channels) {
 extern "C" int dvp_jpeg_encode(int device, const uint8_t* pixels, int width, int height, int channels, long long pitch_bytes, int quality,
                                int restart_mcus, uint8_t* dst, long long capacity, long long* bytes) {
 	t_jpeg_error.clear();
-	auto fail = [](const char* what) { t_jpeg_error = what; return 1; };
+	auto fail = [](const char* what) { return t_jpeg_error.fail(nullptr, what); };   // (the messages name the call themselves)
 	if (!pixels || !bytes) return fail("dvp_jpeg_encode: pixels and bytes are required");
 	if (width < 1 || height < 1 || (channels != 1 && channels != 3) || pitch_bytes < (long long)width * channels) return fail("dvp_jpeg_encode: bad image geometry");
 	if (hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); return fail("dvp_jpeg_encode: hipSetDevice failed"); }
-	hipStream_t s = nullptr;
-	if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); return fail("dvp_jpeg_encode: hipStreamCreate failed"); }
+	struct Pinned { unsigned long long* p = nullptr; ~Pinned() { if (p) (void)hipHostFree(p); } } total;   // the data size, copied on the stream
 	dvpjpeg::Encoder e;
-	uint8_t* d_pix = nullptr;
-	unsigned long long* total = nullptr;
-	int rc = 0;
+	dvpmem::DevBlock d_pix;
+	dvpmem::StreamScope s;
+	if (s.open()) return fail("dvp_jpeg_encode: hipStreamCreate failed");
 	const size_t row = (size_t)width * channels;
-	do {
-		if (hipHostMalloc(reinterpret_cast<void**>(&total), 8, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); total = nullptr; rc = fail("dvp_jpeg_encode: out of host memory"); break; }
-		if (hipMalloc(reinterpret_cast<void**>(&d_pix), row * height) != hipSuccess) { (void)hipGetLastError(); d_pix = nullptr; rc = fail("dvp_jpeg_encode: out of device memory"); break; }
-		if (hipMemcpy2DAsync(d_pix, row, pixels, (size_t)pitch_bytes, row, height, hipMemcpyHostToDevice, s) != hipSuccess) { rc = fail("dvp_jpeg_encode: upload failed"); break; }
-		if (dvpjpeg::encode_begin(e, s, d_pix, (long long)row, width, height, channels, quality, restart_mcus, total) ||
-		    hipStreamSynchronize(s) != hipSuccess || dvpjpeg::encode_write(e, s, *total)) { rc = fail(e.error ? e.error : "dvp_jpeg_encode: device step failed"); break; }
-		*bytes = (long long)dvpjpeg::file_bytes(e);
-		if (!dst || capacity < *bytes) { rc = fail("dvp_jpeg_encode: capacity below the encoded size (*bytes)"); break; }
-		memcpy(dst, e.header, e.header_len);
-		if (hipMemcpyAsync(dst + e.header_len, e.out, e.data_bytes, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) { rc = fail("dvp_jpeg_encode: download failed"); break; }
-		dst[*bytes - 2] = 0xFF;
-		dst[*bytes - 1] = 0xD9;
-	} while (false);
-	(void)hipStreamSynchronize(s);
-	dvpjpeg::encoder_free(e);
-	if (d_pix) (void)hipFree(d_pix);
-	if (total) (void)hipHostFree(total);
-	(void)hipStreamDestroy(s);
-	return rc;
+	if (hipHostMalloc(reinterpret_cast<void**>(&total.p), 8, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); total.p = nullptr; return fail("dvp_jpeg_encode: out of host memory"); }
+	if (d_pix.reserve(row * height)) return fail("dvp_jpeg_encode: out of device memory");
+	if (hipMemcpy2DAsync(d_pix.as<uint8_t>(), row, pixels, (size_t)pitch_bytes, row, height, hipMemcpyHostToDevice, s) != hipSuccess) return fail("dvp_jpeg_encode: upload failed");
+	if (dvpjpeg::encode_begin(e, s, d_pix.as<uint8_t>(), (long long)row, width, height, channels, quality, restart_mcus, total.p) ||
+	    hipStreamSynchronize(s) != hipSuccess || dvpjpeg::encode_write(e, s, *total.p)) return fail(e.error ? e.error : "dvp_jpeg_encode: device step failed");
+	*bytes = (long long)dvpjpeg::file_bytes(e);
+	if (!dst || capacity < *bytes) return fail("dvp_jpeg_encode: capacity below the encoded size (*bytes)");
+	memcpy(dst, e.header, e.header_len);
+	if (hipMemcpyAsync(dst + e.header_len, e.out.as<uint8_t>(), e.data_bytes, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return fail("dvp_jpeg_encode: download failed");
+	dst[*bytes - 2] = 0xFF;
+	dst[*bytes - 1] = 0xD9;
+	return 0;
 }

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "dvp_devmem.hpp"
 #include "dvp_jpeg.hpp"
 
 namespace dvpjpeg {
@@ -14,12 +15,12 @@ struct Encoder {
 	int W = 0, H = 0, C = 0, R = 0, bpm = 0;
 	long long nmcu = 0, nseg = 0;
 	Tables tab{};                       // host copy (headers, and the source of the device copy)
-	Tables* d_tab = nullptr;
-	int16_t* coef = nullptr; size_t coef_alloc = 0;          // [nmcu * bpm][64] zig-zag
-	uint64_t* mask = nullptr; size_t mask_alloc = 0;         // [nmcu * bpm]
-	unsigned* seglen = nullptr; size_t seg_alloc = 0;        // [nseg]
-	unsigned long long* segoff = nullptr;                    // [nseg + 1]: exclusive scan, [nseg] = total
-	uint8_t* out = nullptr; size_t out_alloc = 0;            // entropy-coded segments with their RST markers
+	dvpmem::DevBlock d_tab;             // Tables
+	dvpmem::DevBlock coef;              // int16_t [nmcu * bpm][64] zig-zag
+	dvpmem::DevBlock mask;              // uint64_t [nmcu * bpm]
+	dvpmem::DevBlock seglen;            // unsigned [nseg + 1]
+	dvpmem::DevBlock segoff;            // unsigned long long [nseg + 1]: exclusive scan, [nseg] = total
+	dvpmem::DevBlock out;               // entropy-coded segments with their RST markers
 	unsigned long long data_bytes = 0;
 	uint8_t header[1024];
 	int header_len = 0;
@@ -34,7 +35,6 @@ int encode_begin(Encoder& e, hipStream_t stream, const uint8_t* pixels, long lon
                  int restart, unsigned long long* total_host);
 // Step 4 once the total is known on the host: grows the output buffer and codes every segment to its offset.
 int encode_write(Encoder& e, hipStream_t stream, unsigned long long total);
-void encoder_free(Encoder& e);
 // header + data + EOI; the bytes a finished encode occupies in a file
 inline unsigned long long file_bytes(const Encoder& e) { return (unsigned long long)e.header_len + e.data_bytes + 2; }
 

@@ -149,8 +149,7 @@ using dvplab::Geometry;
 struct dvp_labels {
 	int device = 0;
 	hipStream_t stream = nullptr;
-	uint8_t* pool = nullptr;
-	size_t pool_bytes = 0;
+	dvpmem::DevBlock pool;
 	dvpvc::Scratch vc;
 	// the pool's parts for the geometry of the last run
 	uint8_t *src = nullptr, *half = nullptr, *quarter = nullptr, *texture = nullptr, *lines = nullptr, *resized = nullptr, *cleaned = nullptr;
@@ -166,8 +165,8 @@ struct dvp_labels {
 	long long regions = 0, points = 0;    // large regions with an outline, outline points over all of them
 };
 
-static thread_local std::string t_labels_error;
-static int labels_fail(const char* who, const char* what) { t_labels_error = std::string(who) + ": " + what; return 1; }
+static thread_local dvpmem::CallError t_labels_error;
+static int labels_fail(const char* who, const char* what) { return t_labels_error.fail(who, what); }
 
 extern "C" const char* dvp_labels_last_error(void) { return t_labels_error.c_str(); }
 
@@ -204,32 +203,22 @@ extern "C" int dvp_labels_destroy(dvp_labels* job) {
 	if (!job) return 0;
 	(void)hipSetDevice(job->device);
 	(void)hipStreamSynchronize(job->stream);
-	dvpvc::scratch_free(job->vc);
-	if (job->pool) (void)hipFree(job->pool);
 	(void)hipStreamDestroy(job->stream);
-	delete job;
+	delete job;   // frees the pool and the components' scratch
 	return 0;
 }
 
-// carves the pool for g; grows it when it is too small
+// carves the pool for g; grows it when it is too small.  No wait before a regrow: the job's stream is idle here, every
+// dvp_labels_run and dvp_labels_stage ends in a hipStreamSynchronize.
 static int labels_reserve(dvp_labels* job, const Geometry& g) {
 	const size_t Lf = (size_t)g.W * g.H, Lh = (size_t)g.hw * g.hh, Lq = (size_t)g.qw * g.qh, Ll = (size_t)g.lw * g.lh, Lm = Lq > Ll ? Lq : Ll;
 	const size_t blocks = (Ll + dvplab::SCAN_BLOCK - 1) / dvplab::SCAN_BLOCK;
-	size_t at = 0;
-	auto take = [&at](size_t bytes) { const size_t here = at; at += (bytes + 255) & ~(size_t)255; return here; };
-	const size_t o_src = take(Lf), o_half = take(Lh), o_quarter = take(Lq), o_texture = take(Lq), o_lines = take(Lq), o_region = take(Lq * 4), o_words = take(Lm * 4),
-	             o_list = take(Lq * 4), o_resized = take(Ll), o_cleaned = take(Ll), o_rank = take(Ll * 4), o_label = take(Ll * 4), o_sums = take((blocks + 1) * 4);
-	if (at > job->pool_bytes || !job->pool) {
-		if (job->pool) (void)hipFree(job->pool);
-		job->pool = nullptr;
-		job->pool_bytes = 0;
-		void* p = nullptr;
-		if (hipMalloc(&p, at) != hipSuccess) { (void)hipGetLastError(); return 1; }
-		job->pool = (uint8_t*)p;
-		job->pool_bytes = at;
-	}
-	if (dvpvc::scratch_reserve(job->vc, Lm, 1)) return 1;
-	uint8_t* b = job->pool;
+	dvpmem::Carve c;
+	const size_t o_src = c.take(Lf), o_half = c.take(Lh), o_quarter = c.take(Lq), o_texture = c.take(Lq), o_lines = c.take(Lq), o_region = c.take(Lq * 4),
+	             o_words = c.take(Lm * 4), o_list = c.take(Lq * 4), o_resized = c.take(Ll), o_cleaned = c.take(Ll), o_rank = c.take(Ll * 4), o_label = c.take(Ll * 4),
+	             o_sums = c.take((blocks + 1) * 4);
+	if (job->pool.reserve(c.total) || dvpvc::scratch_reserve(job->vc, Lm, 1)) return 1;
+	uint8_t* b = job->pool.as<uint8_t>();
 	job->src = b + o_src; job->half = b + o_half; job->quarter = b + o_quarter; job->texture = b + o_texture; job->lines = b + o_lines;
 	job->region = (int32_t*)(b + o_region); job->words = (uint32_t*)(b + o_words); job->list = (unsigned*)(b + o_list);
 	job->resized = b + o_resized; job->cleaned = b + o_cleaned; job->rank = (unsigned*)(b + o_rank); job->label = (int32_t*)(b + o_label); job->sums = (unsigned*)(b + o_sums);
@@ -258,7 +247,7 @@ extern "C" int dvp_labels_run(dvp_labels* job, const uint8_t* grey, int width, i
 	job->g = g;
 	hipStream_t st = job->stream;
 	const size_t Lq = (size_t)g.qw * g.qh, Ll = (size_t)g.lw * g.lh;
-	unsigned* parent = job->vc.words;
+	unsigned* parent = job->vc.words();
 
 	// ---- part A
 	const clock::time_point t0 = clock::now();
@@ -354,7 +343,7 @@ extern "C" int dvp_label_map(int device, const uint8_t* grey, int width, int hei
 	dvp_labels* job = nullptr;
 	if (dvp_labels_create(device, &job)) return 1;
 	const int rc = dvp_labels_run(job, grey, width, height, pitch_bytes, scale, label_out);
-	const std::string message = t_labels_error;
+	const dvpmem::CallError message = t_labels_error;
 	(void)dvp_labels_destroy(job);
 	t_labels_error = message;
 	return rc;

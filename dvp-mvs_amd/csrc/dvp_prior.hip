@@ -80,28 +80,13 @@ __global__ void __launch_bounds__(256) dvp_prior_planes(const float* __restrict_
 
 static dim3 blocks2d(int W, int H) { return dim3((unsigned)((W + 63) / 64), (unsigned)((H + 3) / 4)); }
 
-void scratch_free(Scratch& s) {
-	if (s.pool) (void)hipFree(s.pool);
-	s = Scratch();
-}
-
 // carves the pool; grows it when it is too small (after a wait: queued work may still use the old block)
 static int reserve(hipStream_t stream, Scratch& s, size_t dep_pixels, size_t work_pixels, size_t triangles, size_t sweep_rows) {
-	size_t at = 0;
-	auto take = [&at](size_t bytes) { const size_t here = at; at += (bytes + 255) & ~(size_t)255; return here; };
-	const size_t o_raw = take(dep_pixels * 4), o_owner = take(dep_pixels * 4), o_rate = take(dep_pixels * 4), o_depth = take(work_pixels * 4),
-	             o_tris = take((triangles + 1) * sizeof(Tri)), o_off = take((triangles + 1) * 4), o_seq = take((sweep_rows + 1) * 4);
-	if (at > s.pool_bytes || !s.pool) {
-		if (hipStreamSynchronize(stream) != hipSuccess) { (void)hipGetLastError(); return 1; }
-		if (s.pool) (void)hipFree(s.pool);
-		s.pool = nullptr;
-		s.pool_bytes = 0;
-		void* p = nullptr;
-		if (hipMalloc(&p, at) != hipSuccess) { (void)hipGetLastError(); return 1; }
-		s.pool = (uint8_t*)p;
-		s.pool_bytes = at;
-	}
-	uint8_t* b = s.pool;
+	dvpmem::Carve c;
+	const size_t o_raw = c.take(dep_pixels * 4), o_owner = c.take(dep_pixels * 4), o_rate = c.take(dep_pixels * 4), o_depth = c.take(work_pixels * 4),
+	             o_tris = c.take((triangles + 1) * sizeof(Tri)), o_off = c.take((triangles + 1) * 4), o_seq = c.take((sweep_rows + 1) * 4);
+	if (s.pool.reserve(c.total, stream)) return 1;
+	uint8_t* b = s.pool.as<uint8_t>();
 	s.raw = (float*)(b + o_raw); s.owner = (int32_t*)(b + o_owner); s.rate = (float*)(b + o_rate); s.depth = (float*)(b + o_depth);
 	s.tris = (Tri*)(b + o_tris); s.row_off = (unsigned*)(b + o_off); s.seq = (float*)(b + o_seq);
 	return 0;

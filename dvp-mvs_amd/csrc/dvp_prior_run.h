@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/dvp_mvs.h"
+#include "dvp_devmem.hpp"
 #include "dvp_prior.hpp"
 
 namespace dvpprior {
@@ -16,8 +17,7 @@ namespace dvpprior {
 // rate map (4 bytes per dep-map pixel each), the working-size depth (4 bytes per context pixel), the triangle list, the row
 // offsets and the counter sequences (one float per sweep row).
 struct Scratch {
-	uint8_t* pool = nullptr;
-	size_t pool_bytes = 0;
+	dvpmem::DevBlock pool;
 	// the pool's parts for the geometry of the last run
 	float* raw = nullptr; int32_t* owner = nullptr; float* rate = nullptr; float* depth = nullptr;
 	Tri* tris = nullptr; unsigned* row_off = nullptr; float* seq = nullptr;
@@ -28,8 +28,6 @@ struct Scratch {
 	double ms[3] = { 0, 0, 0 };             // the host part (points, triangulation, row counts), the uploads, the kernels
 	long long triangles = 0, sweep_rows = 0;
 };
-void scratch_free(Scratch& s);
-
 // The whole prior on `stream`: the host part (dvp_prior_mid.hpp), the uploads, five launches whatever the inputs hold, one wait at
 // the end.  cam: the context's reference camera ON THE DEVICE (intrinsics at the working size W x H); planes: W * H float4 on the
 // device.  *status = 1 (planes untouched, nothing launched): an empty map or no usable point.  Non-zero: *error says why.

@@ -10,6 +10,7 @@
 #include <string>
 
 #include "../../include/dvp_mvs.h"
+#include "dvp_devmem.hpp"
 #include "dvp_pyramid.hpp"
 #include "dvp_pyramid_run.h"
 
@@ -33,7 +34,7 @@ int launch_levels(hipStream_t stream, const Sources& images, int n, int pad_w, i
 }   // namespace dvppyr
 
 struct dvp_images {
-	struct Entry { uint8_t* bytes = nullptr; int w = 0, h = 0; };   // w bytes per row
+	struct Entry { dvpmem::DevBlock bytes; int w = 0, h = 0; };   // w bytes per row; the map owns its images
 	int device = 0;
 	hipStream_t stream = nullptr;   // the copies of put and the work of level
 	mutable std::shared_mutex m;    // entries, bytes
@@ -41,8 +42,8 @@ struct dvp_images {
 	long long bytes = 0;
 };
 
-static thread_local std::string t_images_error;
-static int images_fail(const char* who, const std::string& what) { t_images_error = std::string(who) + ": " + what; return 1; }
+static thread_local dvpmem::CallError t_images_error;
+static int images_fail(const char* who, const std::string& what) { return t_images_error.fail(who, what); }
 static bool size_ok(int n) { return n >= 1 && n <= 32767; }
 
 namespace dvppyr {
@@ -54,7 +55,7 @@ int store_sources(const dvp_images* store, const int* ids, int n, Sources* out, 
 	for (int i = 0; i < n; ++i) {
 		const auto it = store->entries.find(ids[i]);
 		if (it == store->entries.end()) { *error = "image id " + std::to_string(ids[i]) + " is not in the store"; return 1; }
-		out->v[i] = Source{ it->second.bytes, it->second.w, it->second.h, (long long)it->second.w };
+		out->v[i] = Source{ it->second.bytes.as<uint8_t>(), it->second.w, it->second.h, (long long)it->second.w };
 	}
 	return 0;
 }
@@ -84,9 +85,8 @@ extern "C" int dvp_images_destroy(dvp_images* store) {
 	if (!store) return 0;
 	(void)hipSetDevice(store->device);
 	(void)hipStreamSynchronize(store->stream);
-	for (auto& e : store->entries) (void)hipFree(e.second.bytes);
 	(void)hipStreamDestroy(store->stream);
-	delete store;
+	delete store;   // frees the images
 	return 0;
 }
 
@@ -104,19 +104,15 @@ extern "C" int dvp_images_put(dvp_images* store, int id, const uint8_t* grey, in
 	dvp_images::Entry e;
 	e.w = width;
 	e.h = height;
-	void* p = nullptr;
-	if (hipMalloc(&p, (size_t)width * height) != hipSuccess) { (void)hipGetLastError(); return images_fail(who, "out of device memory"); }
-	e.bytes = (uint8_t*)p;
-	if (hipMemcpy2DAsync(e.bytes, (size_t)width, grey, (size_t)pitch_bytes, (size_t)width, (size_t)height, hipMemcpyHostToDevice, store->stream) != hipSuccess ||
+	if (e.bytes.reserve((size_t)width * height)) return images_fail(who, "out of device memory");
+	if (hipMemcpy2DAsync(e.bytes.as<uint8_t>(), (size_t)width, grey, (size_t)pitch_bytes, (size_t)width, (size_t)height, hipMemcpyHostToDevice, store->stream) != hipSuccess ||
 	    hipStreamSynchronize(store->stream) != hipSuccess) {
 		(void)hipGetLastError();
-		(void)hipFree(p);
 		return images_fail(who, "upload failed");
 	}
 	std::unique_lock<std::shared_mutex> lock(store->m);
-	if (!store->entries.emplace(id, e).second) {   // two threads put the same id
-		lock.unlock();
-		(void)hipFree(p);
+	if (!store->entries.try_emplace(id, std::move(e)).second) {   // two threads put the same id: e keeps its block,
+		lock.unlock();                                            // which is freed at the return, without the lock
 		return images_fail(who, "image id " + std::to_string(id) + " is already in the store");
 	}
 	store->bytes += (long long)width * height;
@@ -132,13 +128,12 @@ extern "C" int dvp_images_drop(dvp_images* store, int id) {
 		std::unique_lock<std::shared_mutex> lock(store->m);
 		const auto it = store->entries.find(id);
 		if (it == store->entries.end()) return images_fail(who, "image id " + std::to_string(id) + " is not in the store");
-		e = it->second;
+		e = std::move(it->second);
 		store->entries.erase(it);
 		store->bytes -= (long long)e.w * e.h;
 	}
 	(void)hipSetDevice(store->device);
-	(void)hipFree(e.bytes);
-	return 0;
+	return 0;   // e is freed here, without the lock
 }
 
 extern "C" int dvp_images_size(const dvp_images* store, int id, int* width, int* height) {
@@ -171,11 +166,10 @@ extern "C" int dvp_images_level(dvp_images* store, int id, int pad_w, int pad_h,
 	if (pad_w == 0) { pad_w = src.v[0].sw; pad_h = src.v[0].sh; }
 	if (hipSetDevice(store->device) != hipSuccess) { (void)hipGetLastError(); return images_fail(who, "hipSetDevice failed"); }
 	const size_t L = (size_t)level_w * level_h;
-	void* p = nullptr;
-	if (hipMalloc(&p, L * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); return images_fail(who, "out of device memory"); }
-	int rc = dvppyr::launch_levels(store->stream, src, 1, pad_w, pad_h, level_w, level_h, (float*)p, level_w, L);
-	if (!rc) rc = hipMemcpyAsync(host_out, p, L * sizeof(float), hipMemcpyDeviceToHost, store->stream) != hipSuccess || hipStreamSynchronize(store->stream) != hipSuccess;
+	dvpmem::DevBlock level;
+	if (level.reserve(L * sizeof(float))) return images_fail(who, "out of device memory");
+	int rc = dvppyr::launch_levels(store->stream, src, 1, pad_w, pad_h, level_w, level_h, level.as<float>(), level_w, L);
+	if (!rc) rc = hipMemcpyAsync(host_out, level.as<float>(), L * sizeof(float), hipMemcpyDeviceToHost, store->stream) != hipSuccess || hipStreamSynchronize(store->stream) != hipSuccess;
 	if (rc) (void)hipGetLastError();
-	(void)hipFree(p);
 	return rc ? images_fail(who, "the level could not be made or fetched") : 0;
 }

@@ -82,26 +82,14 @@ __global__ void __launch_bounds__(256) dvp_vc_resolve(const uint32_t* views, int
 	out[i] = resolve_word(views[i], num_src, min_region, parent, size, L, i);
 }
 
-int scratch_reserve(Scratch& s, size_t pixels, int planes) {
-	const size_t want = pixels * (size_t)(planes > 0 ? planes : 0) * 2;
-	if (s.alloc >= want && (s.words || !want)) return 0;
-	scratch_free(s);
-	void* p = nullptr;
-	if (hipMalloc(&p, want * 4) != hipSuccess) { (void)hipGetLastError(); return 1; }
-	s.words = (unsigned*)p;
-	s.alloc = want;
-	return 0;
-}
-void scratch_free(Scratch& s) {
-	if (s.words) (void)hipFree(s.words);
-	s = Scratch();
-}
+int scratch_reserve(Scratch& s, size_t pixels, int planes) { return s.block.reserve(pixels * (size_t)(planes > 0 ? planes : 0) * 2 * 4); }
+void scratch_free(Scratch& s) { s.block.release(); }
 
 // steps 1-3: after them parent leads every clear pixel to its component's root, whose size word holds the component's pixels
 int launch_components(hipStream_t stream, Scratch& s, const uint32_t* views, int W, int H, int num_src) {
 	const size_t L = (size_t)W * H;
-	unsigned* parent = s.words;
-	unsigned* size = s.words + (size_t)num_src * L;
+	unsigned* parent = s.words();
+	unsigned* size = parent + (size_t)num_src * L;
 	const unsigned per_pixel = (unsigned)((L + 255) / 256);
 	if (num_src > 0) {
 		hipLaunchKernelGGL(dvp_vc_tiles, dim3((unsigned)((W + TILE_W - 1) / TILE_W), (unsigned)((H + TILE_H - 1) / TILE_H)), dim3(TILE_W * kWaves), 0, stream, views, W, H, num_src,
@@ -116,39 +104,33 @@ int launch_components(hipStream_t stream, Scratch& s, const uint32_t* views, int
 int launch_clean(hipStream_t stream, Scratch& s, const uint32_t* views, int W, int H, int num_src, int min_region, uint32_t* out) {
 	const size_t L = (size_t)W * H;
 	if (launch_components(stream, s, views, W, H, num_src)) return 1;
-	hipLaunchKernelGGL(dvp_vc_resolve, dim3((unsigned)((L + 255) / 256)), dim3(256), 0, stream, views, num_src, min_region, s.words, s.words + (size_t)num_src * L, L, out);
+	hipLaunchKernelGGL(dvp_vc_resolve, dim3((unsigned)((L + 255) / 256)), dim3(256), 0, stream, views, num_src, min_region, s.words(), s.words() + (size_t)num_src * L, L, out);
 	return hipGetLastError() != hipSuccess;
 }
 
 }   // namespace dvpvc
 
 // ---- the context-free call: host in, host out ---------------------------------------------------------------------------------
-static thread_local std::string t_vc_error;
+static thread_local dvpmem::CallError t_vc_error;
 
 extern "C" const char* dvp_viewclean_last_error(void) { return t_vc_error.c_str(); }
 
 extern "C" int dvp_clean_selected_views(int device, const uint32_t* views, int W, int H, int num_src, int min_region, uint32_t* out) {
 	t_vc_error.clear();
-	auto fail = [](const char* what) { t_vc_error = std::string("dvp_clean_selected_views: ") + what; return 1; };
+	auto fail = [](const char* what) { return t_vc_error.fail("dvp_clean_selected_views", what); };
 	if (!views || !out) return fail("input and output pointers are required");
 	if (num_src < 0 || num_src > 32) return fail("num_src must be 0 ... 32 (one bit of a word per source view)");
 	if (W < 1 || H < 1 || (long long)W * H > 0x7fffffffLL) return fail("bad image geometry");
 	if (hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); return fail("hipSetDevice failed"); }
-	hipStream_t st = nullptr;
-	if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); return fail("hipStreamCreate failed"); }
 	dvpvc::Scratch s;
-	uint32_t* d_views = nullptr;
+	dvpmem::DevBlock d_views;
+	dvpmem::StreamScope st;
+	if (st.open()) return fail("hipStreamCreate failed");
 	const size_t L = (size_t)W * H;
-	int rc = 0;
-	do {
-		if (dvpvc::scratch_reserve(s, L, num_src) || hipMalloc(reinterpret_cast<void**>(&d_views), L * 4) != hipSuccess) { (void)hipGetLastError(); rc = fail("out of device memory"); break; }
-		if (hipMemcpyAsync(d_views, views, L * 4, hipMemcpyHostToDevice, st) != hipSuccess) { rc = fail("upload failed"); break; }
-		if (dvpvc::launch_clean(st, s, d_views, W, H, num_src, min_region, d_views)) { rc = fail("launch failed"); break; }
-		if (hipMemcpyAsync(out, d_views, L * 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) { rc = fail("download failed"); break; }
-	} while (false);
-	(void)hipStreamSynchronize(st);
-	dvpvc::scratch_free(s);
-	if (d_views) (void)hipFree(d_views);
-	(void)hipStreamDestroy(st);
-	return rc;
+	if (dvpvc::scratch_reserve(s, L, num_src) || d_views.reserve(L * 4)) return fail("out of device memory");
+	uint32_t* words = d_views.as<uint32_t>();
+	if (hipMemcpyAsync(words, views, L * 4, hipMemcpyHostToDevice, st) != hipSuccess) return fail("upload failed");
+	if (dvpvc::launch_clean(st, s, words, W, H, num_src, min_region, words)) return fail("launch failed");
+	if (hipMemcpyAsync(out, words, L * 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return fail("download failed");
+	return 0;
 }

@@ -40,6 +40,7 @@ EXPORTS = ["dvp_ctx_create", "dvp_ctx_destroy", "dvp_ctx_reserve", "dvp_last_err
            "dvp_labels_sizes", "dvp_labels_create", "dvp_labels_destroy", "dvp_labels_run", "dvp_labels_stage", "dvp_labels_timings", "dvp_label_map", "dvp_labels_last_error",
            "dvp_images_create", "dvp_images_destroy", "dvp_images_put", "dvp_images_drop", "dvp_images_size", "dvp_images_bytes", "dvp_images_level", "dvp_images_last_error",
            "dvp_download_image",
+           "dvp_jpeg_decode", "dvp_jpeg_decode_into_store", "dvp_jpeg_decode_timings", "dvp_jpeg_decode_last_error",
            "dvp_plane_prior", "dvp_plane_prior_stage", "dvp_plane_prior_timings"]
 # ... and the one whose name holds a digit (a scan of the header for [a-z_] names does not see it)
 EXPORTS_WITH_DIGITS = ["dvp_upload_images_u8"]
@@ -143,6 +144,11 @@ def lib():
         L.dvp_images_level.argtypes = [vp, ci, ci, ci, ci, ci, vp]
         L.dvp_images_last_error.restype = ctypes.c_char_p
         L.dvp_images_last_error.argtypes = []
+        L.dvp_jpeg_decode.argtypes = [ci, vp, ll, ci, vp, ll, pi, pi]
+        L.dvp_jpeg_decode_into_store.argtypes = [vp, ci, vp, ll, vp, ll]
+        L.dvp_jpeg_decode_timings.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ll)]
+        L.dvp_jpeg_decode_last_error.restype = ctypes.c_char_p
+        L.dvp_jpeg_decode_last_error.argtypes = []
         L.dvp_upload_images_u8.argtypes = [vp, vp, vp, ci, ci]
         L.dvp_download_image.argtypes = [vp, ci, vp, ci]
         L.dvp_plane_prior.argtypes = [vp, vp, ci, ci, vp, vp, ci, vp, pi]
@@ -178,6 +184,39 @@ def jpeg_encode(pixels, quality=95, restart=0, device=0):
     if L.dvp_jpeg_encode(device, _p(a), W, H, C, a.strides[0], int(quality), int(restart), _p(dst), cap, ctypes.byref(n)) != 0:
         raise DvpError(L.dvp_jpeg_last_error().decode())
     return dst[:n.value].tobytes()
+
+
+def _file_bytes(file):
+    return np.frombuffer(bytes(file), np.uint8)
+
+
+def jpeg_size(file, channels=1):
+    """(width, height) of a JPEG file's bytes from its frame header (dvp_jpeg_decode with no output: nothing runs on the device)"""
+    L = lib()
+    f = _file_bytes(file)
+    w, h = ctypes.c_int(0), ctypes.c_int(0)
+    if L.dvp_jpeg_decode(0, _p(f) if f.size else None, f.size, int(channels), None, 0, ctypes.byref(w), ctypes.byref(h)) != 0:
+        raise DvpError(L.dvp_jpeg_decode_last_error().decode())
+    return w.value, h.value
+
+
+def jpeg_decode(file, channels=1, device=0):
+    """a baseline JPEG file's bytes decoded with the inverse DCT and the colour conversion on the GPU (include/dvp_mvs.h
+    dvp_jpeg_decode): the (H, W) uint8 luma plane for channels = 1, the (H, W, 3) B, G, R image for 3"""
+    L = lib()
+    f = _file_bytes(file)
+    W, H = jpeg_size(f, channels)
+    out = np.empty((H, W) if channels == 1 else (H, W, 3), np.uint8)
+    if L.dvp_jpeg_decode(device, _p(f), f.size, int(channels), _p(out), out.strides[0], None, None) != 0:
+        raise DvpError(L.dvp_jpeg_decode_last_error().decode())
+    return out
+
+
+def jpeg_decode_timings():
+    """dict(host_ms, device_ms, record_bytes, blocks) of this thread's last jpeg_decode / ImageStore.put_jpeg"""
+    ms, n = (ctypes.c_double * 2)(), (ctypes.c_longlong * 2)()
+    lib().dvp_jpeg_decode_timings(ms, n)
+    return dict(host_ms=ms[0], device_ms=ms[1], record_bytes=int(n[0]), blocks=int(n[1]))
 
 
 def canny_edge_map(grey, device=0):
@@ -320,6 +359,18 @@ class ImageStore:
     def put(self, image_id, grey):
         a = _grey_rows(grey)
         self._ck(self.L.dvp_images_put(self.h, int(image_id), _p(a), a.shape[1], a.shape[0], a.strides[0]))
+
+    def put_jpeg(self, image_id, file, want_plane=False):
+        """the luma plane of a JPEG file's bytes reconstructed on the device straight into the slot (dvp_jpeg_decode_into_store);
+        want_plane: the (H, W) uint8 plane is copied back and returned"""
+        f = _file_bytes(file)
+        out = None
+        if want_plane:
+            W, H = jpeg_size(f, 1)
+            out = np.empty((H, W), np.uint8)
+        if self.L.dvp_jpeg_decode_into_store(self.h, int(image_id), _p(f) if f.size else None, f.size, _p(out), out.strides[0] if want_plane else 0) != 0:
+            raise DvpError(self.L.dvp_jpeg_decode_last_error().decode())
+        return out
 
     def drop(self, image_id):
         self._ck(self.L.dvp_images_drop(self.h, int(image_id)))

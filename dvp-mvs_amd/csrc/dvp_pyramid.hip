@@ -60,6 +60,22 @@ int store_sources(const dvp_images* store, const int* ids, int n, Sources* out, 
 	return 0;
 }
 
+bool store_has(const dvp_images* store, int id) {
+	std::shared_lock<std::shared_mutex> lock(store->m);
+	return store->entries.count(id) != 0;
+}
+
+int store_adopt(dvp_images* store, int id, dvpmem::DevBlock& bytes, int w, int h) {
+	std::unique_lock<std::shared_mutex> lock(store->m);
+	if (store->entries.count(id)) return 1;
+	dvp_images::Entry& e = store->entries[id];
+	e.bytes = std::move(bytes);
+	e.w = w;
+	e.h = h;
+	store->bytes += (long long)w * h;
+	return 0;
+}
+
 }   // namespace dvppyr
 
 extern "C" const char* dvp_images_last_error(void) { return t_images_error.c_str(); }

@@ -314,6 +314,13 @@ bool stored_size_locked(int image_id, int* w, int* h) {
 	return dvp_images_size(g_image_store, image_id, w, h) == 0;
 }
 }
+static size_t resident_image_budget() {
+	static const size_t budget = [] {
+		const char* e = std::getenv("DVP_RESIDENT_IMAGES_GB");
+		return (size_t)(e ? std::max(0, std::atoi(e)) : 24) << 30;
+	}();
+	return budget;
+}
 static void release_image_store() {
 	std::lock_guard<std::mutex> lock(g_image_store_mutex);
 	if (g_image_store) (void)dvp_images_destroy(g_image_store);
@@ -326,17 +333,38 @@ bool APD::StoreDecoded(int image_id, const path& file, int* width, int* height) 
 	}
 	const Mat gray = DecodedGray(file);   // (a decode takes the time of hundreds of puts: outside the lock)
 	if (gray.empty()) return false;
-	static const size_t budget = [] {
-		const char* e = std::getenv("DVP_RESIDENT_IMAGES_GB");
-		return (size_t)(e ? std::max(0, std::atoi(e)) : 24) << 30;
-	}();
 	std::lock_guard<std::mutex> lock(g_image_store_mutex);
 	if (stored_size_locked(image_id, width, height)) return true;   // another thread put it meanwhile
-	if ((size_t)dvp_images_bytes(g_image_store) + (size_t)gray.cols * gray.rows > budget) return false;
+	if ((size_t)dvp_images_bytes(g_image_store) + (size_t)gray.cols * gray.rows > resident_image_budget()) return false;
 	if (dvp_images_put(g_image_store, image_id, gray.ptr<uint8_t>(0), gray.cols, gray.rows, (long long)gray.step) != 0)
 		DvpFatal(std::string("dvp_images_put failed: ") + dvp_images_last_error());
 	if (width) *width = gray.cols;
 	if (height) *height = gray.rows;
+	return true;
+}
+static size_t g_image_store_pending = 0;   // bytes of the puts under way in PutJpegInStore (g_image_store_mutex)
+bool APD::PutJpegInStore(const path& file, const std::vector<uint8_t>& bytes, Mat* gray) {
+	if (!g_images_on_device || file.parent_path().filename() != "images") return false;
+	const int id = image_id_of(file);
+	int w = 0, h = 0;
+	if (id < 0 || dvp_jpeg_decode(g_device, bytes.data(), (long long)bytes.size(), 1, nullptr, 0, &w, &h) != 0) return false;   // (a bad file: the caller's decode reports it)
+	const size_t size = (size_t)w * h;
+	{
+		std::lock_guard<std::mutex> lock(g_image_store_mutex);
+		if (stored_size_locked(id, nullptr, nullptr)) return false;
+		if ((size_t)dvp_images_bytes(g_image_store) + g_image_store_pending + size > resident_image_budget()) return false;
+		g_image_store_pending += size;
+	}
+	Mat m(h, w, CV_8UC1);
+	const int rc = dvp_jpeg_decode_into_store(g_image_store, id, bytes.data(), (long long)bytes.size(), m.data, (long long)m.step);
+	const std::string message = rc ? dvp_jpeg_decode_last_error() : "";
+	std::lock_guard<std::mutex> lock(g_image_store_mutex);
+	g_image_store_pending -= size;
+	if (rc != 0) {
+		if (stored_size_locked(id, nullptr, nullptr)) return false;   // another thread put the same image meanwhile
+		DvpFatal("dvp_jpeg_decode_into_store failed: " + message);
+	}
+	*gray = m;
 	return true;
 }
 long long APD::StoredImageBytes() {

@@ -55,6 +55,11 @@ Mat LabelSegment(const int scale, const Mat& src_image, LabelStages* stages = nu
 Mat ReadImageGray(const path& image_path_jpg);      // stands in for cv::imread(IMREAD_GRAYSCALE), APD.cpp:1057
 bool ImageFileSize(const path& image_path_jpg, int* width, int* height);   // from the file header, without decoding
 Mat ReadImageColor(const path& image_path_jpg);     // cv::imread(IMREAD_COLOR) (BGR), APD.cpp:1842
+// `apd --decode-on gpu`.  true: ReadImageGray and ReadImageColor hand a .jpg to the engine (include/dvp_mvs.h dvp_jpeg_decode,
+// dvp_jpeg_decode_into_store): the entropy decode stays on the host, the inverse DCT and the colour conversion run on APD::GetDevice().
+// Same bytes; one line "Image decode: on the device (<file>, grey|colour)" per file (grey, into the image store: with --images-on gpu); a failure stops the job.  Default false.
+void SetDecodeOnDevice(bool on);
+bool DecodeOnDevice();
 Mat ResizeLinear(const Mat& src_f32, int new_cols, int new_rows);   // cv::resize(INTER_LINEAR), APD.cpp:1129
 // threads of the host-side pixel loops: min(32, hardware threads), DVP_HOST_THREADS overrides
 int HostThreads();
@@ -165,6 +170,10 @@ public:
 	static bool ImagesOnDevice();
 	static bool StoreDecoded(int image_id, const path& image_file, int* width = nullptr, int* height = nullptr);   // false: unreadable, or no room in the store
 	static long long StoredImageBytes();   // device bytes the store holds
+	// --decode-on gpu with --images-on gpu: the luma plane of images/<id>.jpg (its bytes in `file`) reconstructed straight into the
+	// store's slot, within the same budget, and copied back into *gray.  false: not an image of the job, already stored, or no
+	// room — the caller decodes through dvp_jpeg_decode, and StoreDecoded decides as before.
+	static bool PutJpegInStore(const path& image_file, const std::vector<uint8_t>& file, Mat* gray);
 	static void InsertDecoded(const path& image_file, const Mat& gray);   // a decoded image that came from another rank
 	// true (default): a pass that starts from maps of another size (REFINE_INIT on a finer pyramid level) hands them to the
 	// engine at their own size and RescaleMatToTargetSize runs there (dvp_upload_state_rescaled); false: the five host-side

@@ -3,6 +3,7 @@
 // (APD.cpp:651-692), binary PLY (APD.cpp:842-882), PNM images, bilinear resize, nearest rescale.
 #include "APD.h"
 #include <atomic>
+#include <iterator>
 #include <cstring>
 #include <thread>
 #include <cstdio>
@@ -220,9 +221,37 @@ static bool read_pnm(const path& p, int want_channels, Mat& out) {
 }
 // images/<id>.jpg as the reference's converter writes it (baseline JPEG: host/jpeg.cpp); a .pgm / .ppm of
 // the same stem is used when there is no .jpg (synthetic datasets are written loss-free)
+//
+// `apd --decode-on gpu` (SetDecodeOnDevice): a .jpg is parsed and entropy-decoded here, in DecodeJpeg's own text, and its blocks and
+// pixels are reconstructed by the engine (include/dvp_mvs.h dvp_jpeg_decode; same bytes).  A grey images/<id>.jpg goes straight
+// into the job's image store when there is one (APD::PutJpegInStore: dvp_jpeg_decode_into_store) and comes back as the host plane the
+// edge and label stages still take.  A file the engine refuses stops the job: nothing falls back to the host decoder.
+static std::atomic<bool> g_decode_on_device{false};
+void SetDecodeOnDevice(bool on) { g_decode_on_device = on; }
+bool DecodeOnDevice() { return g_decode_on_device; }
+static Mat decode_jpeg_on_device(const path& jpg, int channels) {
+	std::vector<uint8_t> file;
+	{
+		std::ifstream in(jpg, std::ios::binary);
+		file.assign(std::istreambuf_iterator<char>(in), std::istreambuf_iterator<char>());
+	}
+	const std::string who = "Image decode: " + jpg.string() + ": ";
+	if (file.empty()) DvpFatal(who + "the file is empty or unreadable");
+	Mat m;
+	const bool stored = channels == 1 && APD::PutJpegInStore(jpg, file, &m);
+	if (!stored) {
+		int w = 0, h = 0;
+		if (dvp_jpeg_decode(APD::GetDevice(), file.data(), (long long)file.size(), channels, nullptr, 0, &w, &h) != 0) DvpFatal(who + dvp_jpeg_decode_last_error());
+		m = Mat(h, w, channels == 1 ? CV_8UC1 : CV_8UC3);
+		if (dvp_jpeg_decode(APD::GetDevice(), file.data(), (long long)file.size(), channels, m.data, (long long)m.step, nullptr, nullptr) != 0) DvpFatal(who + dvp_jpeg_decode_last_error());
+	}
+	std::cout << ("Image decode: on the device (" + jpg.filename().string() + (channels == 1 ? (stored ? ", grey, into the image store)\n" : ", grey)\n") : ", colour)\n")) << std::flush;
+	return m;
+}
 static Mat read_image(const path& jpg, int channels) {
 	const std::string ext = jpg.extension().string();
 	if ((ext == ".jpg" || ext == ".jpeg" || ext == ".JPG" || ext == ".JPEG") && std::filesystem::exists(jpg)) {
+		if (g_decode_on_device) return decode_jpeg_on_device(jpg, channels);
 		Mat m = DecodeJpeg(jpg, channels);
 		if (!m.empty()) return m;
 	}

@@ -4,7 +4,7 @@
 //       [--rank R --world N --job ID [--transport rccl|host] [--collective-timeout SEC]] [--jacobi] [--labels]
 //       [--no-fusion | --fusion eth|tat-intermediate|tat-advanced] [--fusion-on device|host]
 //       [--edges-on host|gpu] [--labels-on host|gpu] [--cleanup-on host|gpu] [--images-on host|gpu]
-//       [--prior-on host|gpu]
+//       [--prior-on host|gpu] [--decode-on host|gpu]
 //
 // Schedule.  The image pyramid has round_num levels (the longer side is halved until <= 800).  Level i
 // runs one "A" pass without geometric consistency — FIRST_INIT from scratch / the Depth-Anything prior
@@ -49,6 +49,7 @@ struct Options {
 	bool prior_on_gpu = false;             // --prior-on gpu: the FIRST_INIT plane prior from dep/ + sfm/ is made by the engine into the context's planes (APD::SetPriorOnDevice)
 	bool labels_on_gpu = false;            // --labels-on gpu: GetProblemEdges makes the label maps with a dvp_labels job on the rank's device (APD::SetLabelsOnDevice)
 	bool cleanup_on_gpu = false;           // --cleanup-on gpu: the visibility-mask clean-up runs in the engine on the staged selected-view words (APD::SetCleanupOnDevice)
+	bool decode_on_gpu = false;            // --decode-on gpu: the input JPEGs' inverse DCT and colour conversion run on the device, the entropy decode stays here (SetDecodeOnDevice)
 	bool images_on_gpu = false;            // --images-on gpu: every view's level images are made by the engine from the decoded bytes, uploaded once per job (APD::SetImagesOnDevice)
 	bool previews = false;                 // --previews: the reference's show_medium_result preview images (depth/normal/weak_<it>.jpg, weak.png, rawedge_<s>.jpg)
 	int views_in_flight = 0;               // --views-in-flight N: that many views of a pass at once (default 2) where the order allows it and the level is small; 1 = never
@@ -556,6 +557,11 @@ Options ParseOptions(int argc, char** argv) {
 			if (where != "host" && where != "gpu") { std::cerr << "--cleanup-on takes host or gpu\n"; std::exit(1); }
 			o.cleanup_on_gpu = where == "gpu";
 		}
+		else if (s == "--decode-on" && a + 1 < argc) {
+			const std::string where = argv[++a];
+			if (where != "host" && where != "gpu") { std::cerr << "--decode-on takes host or gpu\n"; std::exit(1); }
+			o.decode_on_gpu = where == "gpu";
+		}
 		else if (s == "--images-on" && a + 1 < argc) {
 			const std::string where = argv[++a];
 			if (where != "host" && where != "gpu") { std::cerr << "--images-on takes host or gpu\n"; std::exit(1); }
@@ -576,7 +582,7 @@ Options ParseOptions(int argc, char** argv) {
 
 int main(int argc, char** argv) {
 	if (argc < 2) {
-		std::cerr << "USAGE: apd dense_folder [gpu_index] [--previews] [--max-src N] [--iters N] [--min-scale S] [--passes P] [--seed X] [--rank R --world N [--job ID]] [--jacobi] [--no-fusion | --fusion KIND] [--fusion-on device|host] [--edges-on host|gpu] [--labels-on host|gpu] [--cleanup-on host|gpu] [--images-on host|gpu] [--prior-on host|gpu] [--views-in-flight N]\n";
+		std::cerr << "USAGE: apd dense_folder [gpu_index] [--previews] [--max-src N] [--iters N] [--min-scale S] [--passes P] [--seed X] [--rank R --world N [--job ID]] [--jacobi] [--no-fusion | --fusion KIND] [--fusion-on device|host] [--edges-on host|gpu] [--labels-on host|gpu] [--cleanup-on host|gpu] [--images-on host|gpu] [--prior-on host|gpu] [--decode-on host|gpu] [--views-in-flight N]\n";
 		return EXIT_FAILURE;
 	}
 	const Options opt = ParseOptions(argc, argv);
@@ -612,6 +618,7 @@ int main(int argc, char** argv) {
 	APD::SetLabelsOnDevice(opt.labels_on_gpu);
 	APD::SetPriorOnDevice(opt.prior_on_gpu);
 	APD::SetImagesOnDevice(opt.images_on_gpu);
+	SetDecodeOnDevice(opt.decode_on_gpu);
 	SetResultCache(!opt.sync_io);
 	APD::SetDeviceRescale(!opt.sync_io && !opt.host_rescale);
 	g_device_maps = !opt.sync_io && !opt.host_rescale;

@@ -399,6 +399,26 @@ int dvp_upload_images_u8(dvp_ctx* ctx, const dvp_images* store, const int* ids, 
 /* The width x height float image `index` the context holds since its last dvp_upload_images*, `pitch_floats` (>= width) per row. */
 int dvp_download_image(dvp_ctx* ctx, int index, float* out, int pitch_floats);
 
+/* ---- the input JPEGs decoded on the device (`apd --decode-on gpu`) -----------------------------------------------------------------
+ * A baseline / extended-sequential 8-bit JPEG file (Huffman-coded, one interleaved scan, one or three components) in host memory.
+ * The marker parse and the entropy decode run on the host, in the text the host mirror's DecodeJpeg runs: a file it rejects
+ * (progressive, a truncated segment, a missing table, a corrupt code, a missing restart marker, sub-sampled luma for one channel)
+ * is rejected here with the same message, before any device work.  Dequantisation, the accurate integer inverse DCT, the clamp,
+ * the replicated chroma sampling and the JFIF colour equations run on the device; the bytes equal DecodeJpeg's.
+ * channels 1: the luma plane (libjpeg's JCS_GRAYSCALE); 3: B, G, R.  `out`: height rows of `pitch_bytes` (>= width * channels).
+ * out == NULL: only *width and *height are set, from the frame header, and nothing touches the device.  NULL size pointers are
+ * skipped.  Host in, host out; returns when `out` is complete.  A refused allocation reports "out of device memory". */
+int dvp_jpeg_decode(int device, const uint8_t* file, long long file_bytes, int channels, uint8_t* out, long long pitch_bytes, int* width, int* height);
+/* The luma plane of the file reconstructed straight into the store's slot `id`: what dvp_images_put of the decoded plane leaves —
+ * 1 byte per pixel, counted in dvp_images_bytes, an id already present is an error — without a host plane in between.  The plane
+ * is copied to the host only when grey_out_or_null is given (height rows of pitch_bytes >= width).  After any error the store is
+ * as it was.  Sizes of 1 ... 32767. */
+int dvp_jpeg_decode_into_store(dvp_images* store, int id, const uint8_t* file, long long file_bytes, uint8_t* grey_out_or_null, long long pitch_bytes);
+/* The calling thread's last successful call of the two above: ms[0] the host part (parse + entropy decode), ms[1] the device part
+ * (upload, launches, read-back, wait); counts[0] the bytes of coefficient records and offsets uploaded, counts[1] the 8 x 8 blocks. */
+int dvp_jpeg_decode_timings(double* ms, long long* counts);
+const char* dvp_jpeg_decode_last_error(void);   /* the calling thread's last error of the three above */
+
 /* ---- the monocular-depth plane prior of a FIRST_INIT pass (APD.cpp:1210-1424) on the device ---------------------------------------
  * From the relative depth map of dep/<id>.dmb (dep_w x dep_h floats as read, dense) and the sparse points of sfm/<id>.txt
  * (xy: 2 floats per point, the image position; xyz: 3 floats, the world point) to the context's planes (DVP_BUF_PLANES), equal

@@ -29,7 +29,7 @@ BUFFERS = dict(planes=(0, np.float32, 4), costs=(1, np.float32, 1), selected_vie
 # every symbol include/dvp_mvs.h declares
 EXPORTS = ["dvp_ctx_create", "dvp_ctx_destroy", "dvp_ctx_reserve", "dvp_last_error", "dvp_upload_images", "dvp_upload_depths",
            "dvp_upload_images_device", "dvp_upload_depths_device", "dvp_upload_cameras", "dvp_upload_state", "dvp_upload_state_rescaled",
-           "dvp_reset_state", "dvp_save_state", "dvp_restore_state", "dvp_set_params", "dvp_set_seed", "dvp_set_sampler", "dvp_set_profiling", "dvp_image_format", "dvp_run_patchmatch",
+           "dvp_reset_state", "dvp_save_state", "dvp_restore_state", "dvp_set_params", "dvp_set_seed", "dvp_set_sampler", "dvp_set_profiling", "dvp_image_format", "dvp_strong_update_form", "dvp_run_patchmatch",
            "dvp_run_stage", "dvp_synchronize", "dvp_download_state", "dvp_download_maps", "dvp_download_maps_begin", "dvp_download_maps_finish", "dvp_buffer_bytes", "dvp_download_buffer",
            "dvp_upload_buffer", "dvp_weak_count", "dvp_get_timings", "dvp_reset_timings", "dvp_eval_cost_vectors",
            "dvp_bench_cost_kernel", "dvp_build_id",
@@ -87,6 +87,7 @@ def lib():
         L.dvp_set_sampler.argtypes = [vp, ci]
         L.dvp_set_profiling.argtypes = [vp, ci]
         L.dvp_image_format.argtypes = [vp]
+        L.dvp_strong_update_form.argtypes = [vp]
         L.dvp_run_patchmatch.argtypes = [vp]
         L.dvp_run_stage.argtypes = [vp, ci, ci, ci]
         L.dvp_synchronize.argtypes = [vp]
@@ -496,6 +497,12 @@ class Context:
         """0: float planes, 1: byte planes (8-bit exact image set), 2: binary16 planes (every texel a binary16 value in
         [0, 255], not all integers: down-sampled levels of 8-bit images) — include/dvp_mvs.h dvp_image_format"""
         return int(self.L.dvp_image_format(self.h))
+
+    def strong_update_form(self):
+        """the split strong update's decision bracket (4, 6, 8, 10, 12, 16; 32: the streaming kernel of DVP_STRONG_WIDE), 0: a
+        monolithic kernel; accounts for the cost buffers once a strong update has tried them — include/dvp_mvs.h
+        dvp_strong_update_form"""
+        return int(self.L.dvp_strong_update_form(self.h))
 
     def save_state(self):
         self._ck(self.L.dvp_save_state(self.h))

@@ -156,7 +156,7 @@ DVP_KERNEL(dvp_random_init, DVP_ST_RANDOM_INIT, DVP_LB_HEAVY)
 DVP_KERNEL(dvp_strong_update, DVP_ST_STRONG_UPDATE, DVP_LB_HEAVY)
 DVP_KERNEL_MV(dvp_strong_update_v8, DVP_ST_STRONG_UPDATE, DVP_LB_HEAVY, kNarrowViews)
 DVP_KERNEL_MV(dvp_strong_update_v16, DVP_ST_STRONG_UPDATE, DVP_LB_HEAVY, 16)
-// split strong update (dvp_strong.hpp): evaluations of the 17 snapshot planes, decisions, refinement (S <= 16)
+// split strong update (dvp_strong.hpp): evaluations of the 17 snapshot planes, decisions, refinement (S <= 16; S <= 31 with DVP_STRONG_WIDE)
 DVP_KERNEL64(dvp_strong_eval, kStageStrongEval, DVP_LB_HEAVY)
 // dvp_strong_eval with the (pixel, slot) items of the wave's 64 pixels compacted over its lanes.  With a pixel per lane a
 // wave makes 17 trips x S views whatever its lanes hold: WEAK and off-image lanes idle, edge pixels have 9 slots instead of
@@ -263,6 +263,12 @@ DVP_DECIDE_KERNEL(8)
 DVP_DECIDE_KERNEL(10)
 DVP_DECIDE_KERNEL(12)
 DVP_DECIDE_KERNEL(16)
+// any S <= 31 (DVP_STRONG_WIDE): the vectors are streamed in 16-byte pieces instead of held (strong_decide_wide_px)
+extern "C" __global__ void __launch_bounds__(256, DVP_LB_DECIDE) dvp_strong_decide_wide(const Dev d, const LaunchArgs a) {
+	int px, py;
+	if (!block_to_pixel(blockIdx.x, threadIdx.x & 63, threadIdx.x >> 6, a.tiles_x, a.tiles, a.rows, a.half, a.colour, d.width, d.height, &px, &py)) return;
+	if (d.weak_info[px + py * d.width] != DVP_WEAK) strong_decide_wide_px(d, px, py, a.iter);
+}
 DVP_KERNEL(dvp_get_depth_normal, DVP_ST_GET_DEPTH_NORMAL, 1)
 DVP_KERNEL(dvp_filter_strong, DVP_ST_FILTER_STRONG, 1)
 DVP_KERNEL(dvp_depth_to_weak, DVP_ST_DEPTH_TO_WEAK, DVP_LB_HEAVY)
@@ -1776,6 +1782,11 @@ int dvp_reset_state(dvp_ctx* c) {
 // pass-internal buffers to their freshly-uploaded content.  Lets a caller run the same pass again
 // from identical inputs (bench steps, A/B checks) without a host round trip.
 int dvp_image_format(const dvp_ctx* c) { return !c ? 0 : (c->images8_ok ? 1 : (c->images16_ok ? 2 : 0)); }
+int dvp_strong_update_form(const dvp_ctx* c) {
+	if (!c) return 0;
+	const StrongForm f = strong_form(c->sw, c->NI - 1, c->split_fits, false, 0);
+	return f.kernel == STRONG_SPLIT ? f.decide : 0;
+}
 int dvp_save_state(dvp_ctx* c) {
 	if (set_device(c)) return 1;
 	const size_t L = c->L;
@@ -2004,7 +2015,7 @@ static int launch_strong_update(dvp_ctx* c, const LaunchGeom& g, const LaunchArg
 		if (f.eval_items) hipLaunchKernelGGL(DVP_PICK(dvp_strong_eval_items, ), wave_grid, wave_block, 0, c->stream, c->d, a);
 		else hipLaunchKernelGGL(DVP_PICK(dvp_strong_eval, ), wave_grid, wave_block, 0, c->stream, c->d, a);
 		hipLaunchKernelGGL(f.decide == 4 ? dvp_strong_decide_v4 : f.decide == 6 ? dvp_strong_decide_v6 : f.decide == 8 ? dvp_strong_decide_v8 : f.decide == 10 ? dvp_strong_decide_v10 :
-		                   f.decide == 12 ? dvp_strong_decide_v12 : dvp_strong_decide_v16, grid, block, 0, c->stream, c->d, a);
+		                   f.decide == 12 ? dvp_strong_decide_v12 : f.decide == 16 ? dvp_strong_decide_v16 : dvp_strong_decide_wide, grid, block, 0, c->stream, c->d, a);
 		// lanes: every lane on its own (hypothesis, view) sequence; the lanes' image planes are 32-bit byte offsets from the set's base
 		if (f.refine_lanes) hipLaunchKernelGGL(DVP_PICK(dvp_strong_refine_lanes, ), wave_grid, wave_block, 0, c->stream, c->d, a);
 		else hipLaunchKernelGGL(DVP_PICK(dvp_strong_refine, ), wave_grid, wave_block, 0, c->stream, c->d, a);

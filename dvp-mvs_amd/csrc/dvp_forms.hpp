@@ -29,6 +29,7 @@ struct FormSwitches {   // unset defaults; =0 / =1 are atoi(e) != 0, "(present)"
 	bool no_images8 = false, no_images16 = false;   // DVP_NO_IMAGES8 / _16 (present): such sets keep the float planes (A/B measurements)
 	bool strong_split = true, strong_reuse = true;  // DVP_STRONG_SPLIT=0: the monolithic kernel; DVP_STRONG_REUSE=0: no plane cache
 	bool refine_lanes = true, eval_items = true;    // DVP_REFINE_LANES=0: dvp_strong_refine; DVP_EVAL_ITEMS=0: dvp_strong_eval (a pixel per lane)
+	int strong_wide = 0;          // DVP_STRONG_WIDE=1: the split form also for 17 <= S <= 31 (dvp_strong_decide_wide); =2: that decision kernel at every S (A/B)
 	bool sweep_split = true, sweep_force = false;   // DVP_SWEEP_SPLIT=0: the fused per-pixel kernel; =2: the passes also without the geometric term
 	double sweep_band_gb = 0.0;   // DVP_SWEEP_BAND_GB=g: sweep_cost holds a band of rows of at most g GB (0: the whole image)
 	bool anchor_tab_off = false;  // DVP_WEAK_ANCHOR_TAB=0: the weak update forms the reference side per item
@@ -46,6 +47,7 @@ inline FormSwitches read_form_switches() {
 	s.strong_reuse = env_flag("DVP_STRONG_REUSE", true);
 	s.refine_lanes = env_flag("DVP_REFINE_LANES", true);
 	s.eval_items = env_flag("DVP_EVAL_ITEMS", true);
+	if (const char* e = getenv("DVP_STRONG_WIDE")) { const int v = atoi(e); s.strong_wide = v == 0 ? 0 : (v == 2 ? 2 : 1); }
 	if (const char* e = getenv("DVP_SWEEP_SPLIT")) { s.sweep_split = atoi(e) != 0; s.sweep_force = atoi(e) == 2; }
 	if (const char* e = getenv("DVP_SWEEP_BAND_GB")) s.sweep_band_gb = atof(e);
 	s.anchor_tab_off = !env_flag("DVP_WEAK_ANCHOR_TAB", true);
@@ -70,19 +72,21 @@ inline int image_format(const FormSwitches& s, unsigned inexact) {
 	return (inexact == 0 && !s.no_images8) ? 1 : ((inexact == 1 && !s.no_images8 && !s.no_images16) ? 2 : 0);
 }
 
-// Strong update: three launches (evaluate / decide / refine) for S <= 16, or one monolithic kernel.
+// Strong update: three launches (evaluate / decide / refine) for S <= 16 — with DVP_STRONG_WIDE for S <= 31 — or one monolithic kernel.
 enum StrongKernel { STRONG_SPLIT, STRONG_MONO_V8, STRONG_MONO_V16, STRONG_MONO };
 struct StrongForm {
 	StrongKernel kernel;
 	bool eval_items;     // split: dvp_strong_eval_items, else dvp_strong_eval
-	int decide;          // split: the view bracket of dvp_strong_decide_v{4,6,8,10,12,16}
+	int decide;          // split: the view bracket of dvp_strong_decide_v{4,6,8,10,12,16}; 32: dvp_strong_decide_wide (any S <= 31, the vectors streamed)
 	bool refine_lanes;   // split: dvp_strong_refine_lanes, else dvp_strong_refine
 	bool plan;           // dvp_strong_plan runs after the sample search (the plane cache exists)
 };
 // image_set_bytes: all row-pair planes — dvp_strong_refine_lanes addresses them with 32-bit byte offsets
 inline StrongForm strong_form(const FormSwitches& s, int S, bool split_fits, bool have_reuse_hdr, unsigned long long image_set_bytes) {
-	if (!(s.strong_split && split_fits && S <= 16)) return { S <= kNarrowViews ? STRONG_MONO_V8 : (S <= 16 ? STRONG_MONO_V16 : STRONG_MONO), false, 0, false, false };
-	return { STRONG_SPLIT, s.eval_items, S <= 4 ? 4 : S <= 6 ? 6 : S <= 8 ? 8 : S <= 10 ? 10 : S <= 12 ? 12 : 16, s.refine_lanes && image_set_bytes < (1ull << 32), have_reuse_hdr };
+	const bool wide = s.strong_wide != 0 && S > 16 && S <= 31;
+	if (!(s.strong_split && split_fits && (S <= 16 || wide))) return { S <= kNarrowViews ? STRONG_MONO_V8 : (S <= 16 ? STRONG_MONO_V16 : STRONG_MONO), false, 0, false, false };
+	const int bracket = (wide || s.strong_wide == 2) ? 32 : (S <= 4 ? 4 : S <= 6 ? 6 : S <= 8 ? 8 : S <= 10 ? 10 : S <= 12 ? 12 : 16);
+	return { STRONG_SPLIT, s.eval_items, bracket, s.refine_lanes && image_set_bytes < (1ull << 32), have_reuse_hdr };
 }
 
 // Weak update: eight launches over the WEAK list (dvp_weak_phased.hpp) or one wave per WEAK pixel, with or without the anchor table.

@@ -816,8 +816,14 @@ DVP_HD void load_slot_costs(const float* sc, size_t view_stride, int S, float* o
 
 // Everything of strong_update_px between the propagation evaluations and the refinement evaluations, statement for
 // statement, with the cost vectors in registers (all loops over directions / views are unrolled; MV >= S).
+DVP_HD void strong_decide_wide_px(const Dev& d, int px, int py, int iter);
 template <int MV>
 DVP_HD void strong_decide_px(const Dev& d, int px, int py, int iter) {
+#if !defined(__HIP_DEVICE_COMPILE__)
+	// host builds only (the emulation dispatches on the bracket and knows none above 16): more views than the bracket holds are the
+	// streaming form's.  No device instantiation carries this call.
+	if (d.params.num_images - 1 > MV) { strong_decide_wide_px(d, px, py, iter); return; }
+#endif
 	const int W = d.width;
 	const int center = py * W + px;
 	const DvpParams& P = d.params;
@@ -1016,6 +1022,242 @@ DVP_HD void strong_decide_px(const Dev& d, int px, int py, int iter) {
 	const f4 n_rand = MV <= 16 ? random_normal_yzl_views<(MV <= 16 ? MV : 16)>(d, px, py, rn, depth_now, selected_views_written ? sel_mask : sel_entry)
 	                           : random_normal_yzl(d, px, py, rn, depth_now);
 #endif
+	const float dmin_p = (1 - 0.02f) * depth_now, dmax_p = (1 + 0.02f) * depth_now;
+	const float depth_pert = rp.uniform() * (dmax_p - dmin_p) + dmin_p;
+	float* rec = d.strong_rec + hi;
+	rec[(SR_PLANE + 0) * Lh] = plane_now.x; rec[(SR_PLANE + 1) * Lh] = plane_now.y; rec[(SR_PLANE + 2) * Lh] = plane_now.z; rec[(SR_PLANE + 3) * Lh] = plane_now.w;
+	rec[SR_DEPTH * Lh] = depth_now; rec[SR_COST * Lh] = cost_now; rec[SR_CENTER * Lh] = costs_center;
+	rec[SR_DRAND * Lh] = depth_rand; rec[SR_DPERT * Lh] = depth_pert;
+	rec[(SR_NRAND + 0) * Lh] = n_rand.x; rec[(SR_NRAND + 1) * Lh] = n_rand.y; rec[(SR_NRAND + 2) * Lh] = n_rand.z;
+}
+
+// ===== the decision step for any S <= 31 (DVP_STRONG_WIDE, StrongForm::decide == 32): the cost vectors streamed, not held ========
+// strong_decide_px keeps the eight directions' vectors in registers (8 x MV floats), which ends at MV = 16.  The decisions do not
+// need them all at once.  Three passes over 16-byte pieces of four views, every piece found through the same place words:
+//   A  per direction k: which of slot k and slot 8 + k gives the direction's vector.  The rule counts costs below good_thr and
+//      above 1.2 over all views — integers, any order — and leaves two bits per direction (`flag`: a sample exists, `pick`: slot
+//      8 + k's vector); the sample position is read again for the one direction that is adopted.  A direction without a sample
+//      keeps the initialiser's vector, (2, 0, 0, ...) for k = 0 and zeros otherwise (wide_chosen_piece).
+//   B  per view, in view order: the prior from the four neighbours' words (0.0f + 0.9f / 0.1f in neighbour order), the
+//      eight-direction loop on element i of the chosen vectors in direction order -> probs[i].  CDF, draws and weights as in
+//      strong_decide_px; the weights live packed as they are stored (view_weight, 8 words).
+//   C  final_costs[k] and the current plane's cost: sums over the views in ascending order where the weight is > 0, multiply and
+//      add rounded separately — the vectors are read a second time (L1 / L2), only the pieces that hold a selected view.
+// Same operations on the same values in the same order per result as strong_decide_px / strong_update_px: the same bits.
+constexpr int kWidePieces = 8;   // 4 views each
+// views 4 q ... 4 q + 3 of the vector at `sc` (beyond S: 0), by value: the pieces stay in registers.  The caller asks for pieces with
+// 4 q < S only: the 16 bytes end at most 12 bytes past the vector, inside the next one or the 64 bytes of slack behind the last record
+DVP_HD f4 load_cost_piece(const float* sc, size_t view_stride, int S, int q) {
+#if defined(__HIP_DEVICE_COMPILE__) && DVP_SLOT_LAYOUT
+	typedef float f4v __attribute__((ext_vector_type(4), aligned(4)));
+	const f4v v = reinterpret_cast<const f4v*>(sc)[q];
+	return mk4(4 * q < S ? v[0] : 0.0f, 4 * q + 1 < S ? v[1] : 0.0f, 4 * q + 2 < S ? v[2] : 0.0f, 4 * q + 3 < S ? v[3] : 0.0f);
+#else
+	const float* p = sc + (size_t)(4 * q) * view_stride;
+	return mk4(4 * q < S ? p[0] : 0.0f, 4 * q + 1 < S ? p[view_stride] : 0.0f, 4 * q + 2 < S ? p[2 * view_stride] : 0.0f, 4 * q + 3 < S ? p[3 * view_stride] : 0.0f);
+#endif
+}
+DVP_HD float piece_view(const f4 p, int j) { return j == 0 ? p.x : (j == 1 ? p.y : (j == 2 ? p.z : p.w)); }   // (j: a constant after unrolling)
+// acc + the piece's costs under the weights of its four views (a byte each in `w`), view by view where the weight is > 0
+DVP_HD float wide_weighted_add(float acc, const f4 p, uint32_t w, int S, int q) {
+#pragma unroll
+	for (int j = 0; j < 4; ++j) {
+		const int wv = (int)((w >> (8 * j)) & 255u);
+		if (4 * q + j < S && wv > 0) acc += wv * piece_view(p, j);
+	}
+	return acc;
+}
+// piece q of direction k's vector after pass A
+DVP_HD f4 wide_chosen_piece(const SlotCostView& cv, uint32_t dw0, uint32_t dw1, uint32_t dw2, uint32_t flag, uint32_t pick, int S, int k, int q) {
+	f4 r = mk4((k == 0 && q == 0) ? 2.0f : 0.0f, 0.0f, 0.0f, 0.0f);   // no sample: the initialiser's vector, `= { 2.0f }` sets one element (APD.cu:2032)
+	if ((flag >> k) & 1u) {
+		const int slot = ((pick >> k) & 1u) ? 8 + k : k;
+		r = load_cost_piece(cv.base + (size_t)strong_slot_place_of(dw0, dw1, dw2, slot) * cv.slot_stride, cv.view_stride, S, q);
+	}
+	return r;
+}
+DVP_HD void strong_decide_wide_px(const Dev& d, int px, int py, int iter) {
+	const int W = d.width;
+	const int center = py * W + px;
+	const DvpParams& P = d.params;
+	const DvpCamera rc = load_camera(d, 0);
+	const int S = P.num_images - 1;
+	const bool reuse = d.reuse_costs != nullptr;
+	SlotCostView cv;
+	if (reuse) { cv.base = d.reuse_costs + (size_t)center * kSlotCount * (size_t)S; cv.slot_stride = (size_t)S; cv.view_stride = 1; }
+	else cv = slot_cost_view(d, px, py);
+	const size_t L = (size_t)W * d.height;
+	const size_t Lh = (size_t)d.half_w * (size_t)d.height, hi = half_index(d, px, py);
+	const float good_thr = 0.8f * dvp_expf((iter) * (iter) / (-90.0f));
+	const uint32_t sel_entry = d.selected_views[center];   // (the pixel's own word: no other pixel of this colour writes it)
+	const uint32_t* dup = reinterpret_cast<const uint32_t*>(d.strong_rec) + hi;
+	const uint32_t dw0 = dup[SR_DUP * Lh], dw1 = dup[(SR_DUP + 1) * Lh], dw2 = dup[(SR_DUP + 2) * Lh];
+	uint32_t have = 0;   // bit s: slot s has a sample
+#pragma unroll
+	for (int slot = 0; slot < 16; ++slot)
+		if (d.search_pos[(size_t)slot * L + center] >= 0) have |= 1u << slot;
+	// ---- pass A: slot k or slot 8 + k (APD.cu:2047-2090, 2104-2137) ----
+	uint32_t flag = 0, pick = 0;
+#pragma unroll 1
+	for (int k = 0; k < 8; ++k) {
+		const bool h0 = (have >> k) & 1u, h1 = (have >> (8 + k)) & 1u;
+		if (h0 || h1) flag |= 1u << k;
+		if (h1 && !h0) pick |= 1u << k;
+		if (h0 && h1) {   // the fixed-stride sample replaces the adaptive one if it is better
+			const float* va = cv.base + (size_t)strong_slot_place_of(dw0, dw1, dw2, k) * cv.slot_stride;
+			const float* vb = cv.base + (size_t)strong_slot_place_of(dw0, dw1, dw2, 8 + k) * cv.slot_stride;
+			int good0 = 0, good1 = 0, bad0 = 0, bad1 = 0;
+#pragma unroll
+			for (int q = 0; q < kWidePieces; ++q) {
+				if (4 * q < S) {
+					const f4 pa = load_cost_piece(va, cv.view_stride, S, q), pb = load_cost_piece(vb, cv.view_stride, S, q);
+#pragma unroll
+					for (int j = 0; j < 4; ++j) {
+						if (4 * q + j < S) {
+							const float a = piece_view(pa, j), b = piece_view(pb, j);
+							if (a < good_thr) good0++;
+							if (a > 1.2f) bad0++;
+							if (b < good_thr) good1++;
+							if (b > 1.2f) bad1++;
+						}
+					}
+				}
+			}
+			if (good1 > good0 || (good1 == good0 && bad1 < bad0)) pick |= 1u << k;
+		}
+	}
+	// ---- pass B: view selection (APD.cu:2462-2530) ----
+	uint32_t nbv[4];
+	{
+		const int nb[4] = { center - W, center + W, center - 1, center + 1 };
+#pragma unroll
+		for (int i = 0; i < 4; ++i) nbv[i] = ((flag >> (2 * i)) & 1u) ? d.selected_views[nb[i]] : 0u;   // guards flag[0],[2],[4],[6] (APD.cu:2471)
+	}
+	float probs[4 * kWidePieces];
+	const float thr = (float)(0.8 * dvp_expf((iter) * (iter) / (-90.0f)));
+#pragma unroll
+	for (int q = 0; q < kWidePieces; ++q) {
+#pragma unroll
+		for (int j = 0; j < 4; ++j) probs[4 * q + j] = 0.0f;
+		if (4 * q < S) {
+			// the eight-direction loop of every view of the piece, direction by direction: a view's sums see the directions in order
+			float count[4], tmpw[4];
+			int count_false[4];
+#pragma unroll
+			for (int j = 0; j < 4; ++j) { count[j] = 0; tmpw[j] = 0; count_false[j] = 0; }
+#pragma unroll
+			for (int k = 0; k < 8; k++) {
+				const f4 p = wide_chosen_piece(cv, dw0, dw1, dw2, flag, pick, S, k, q);
+#pragma unroll
+				for (int j = 0; j < 4; ++j) {
+					const float cst = piece_view(p, j);
+					if (cst < thr) { tmpw[j] += dvp_expf(cst * cst / (-0.18f)); count[j]++; }
+					if (cst > 1.2f) count_false[j]++;
+				}
+			}
+#pragma unroll
+			for (int j = 0; j < 4; ++j) {
+				const int i = 4 * q + j;
+				if (i < S) {
+					float prior = 0.0f;
+#pragma unroll
+					for (int n = 0; n < 4; ++n)
+						if ((flag >> (2 * n)) & 1u) prior += is_set(nbv[n], i) ? 0.9f : 0.1f;
+					float pr = 0.0f;
+					if (count[j] > 2 && count_false[j] < 3) pr = tmpw[j] / count[j];
+					else if (count_false[j] < 3) pr = dvp_expf(thr * thr / (-0.32f));
+					probs[i] = pr * prior;
+				}
+			}
+		}
+	}
+	float psum = 0.0f;
+#pragma unroll
+	for (int i = 0; i < 4 * kWidePieces; ++i)
+		if (i < S) psum += probs[i];
+	const float inv = 1.0f / psum;
+	float cum = 0.0f;
+#pragma unroll
+	for (int i = 0; i < 4 * kWidePieces; ++i)
+		if (i < S) { cum += probs[i] * inv; probs[i] = cum; }
+	uint32_t words[kWidePieces];   // the weights, a byte per view (at most 15 each)
+#pragma unroll
+	for (int q = 0; q < kWidePieces; ++q) words[q] = 0;
+	Rng rv(d.seed, (uint32_t)center, rng_site(PH_STRONG, iter, SUB_VIEW));
+	for (int s = 0; s < 15; ++s) {
+		const float rp = rv.uniform() - FLT_EPSILON;
+		bool done = false;
+#pragma unroll
+		for (int v = 0; v < 4 * kWidePieces; ++v)
+			if (v < S && !done && probs[v] > rp) { words[v >> 2] += 1u << (8 * (v & 3)); done = true; }
+	}
+	uint32_t sel_mask = 0;
+	float weight_norm = 0;
+#pragma unroll
+	for (int i = 0; i < 4 * kWidePieces; ++i) {
+		const int wv = (int)((words[i >> 2] >> (8 * (i & 3))) & 255u);
+		if (i < S && wv > 0) { set_bit(&sel_mask, i); weight_norm += wv; }
+	}
+	{
+		uint32_t* g32 = reinterpret_cast<uint32_t*>(d.view_weight + (size_t)center * 32);   // 32-byte records: aligned
+#pragma unroll
+		for (int q = 0; q < kWidePieces; ++q) g32[q] = words[q];
+	}
+	// ---- pass C: the eight directions' and the current plane's cost under the new weights ----
+	float final_costs[8], cn = 0.0f;
+#pragma unroll
+	for (int k = 0; k < 8; ++k) final_costs[k] = 0.0f;
+	{
+		const float* cur = cv.base + (size_t)strong_slot_place_of(dw0, dw1, dw2, kSlotCur) * cv.slot_stride;
+#pragma unroll
+		for (int q = 0; q < kWidePieces; ++q) {
+			if (4 * q < S && words[q] != 0) {
+#pragma unroll
+				for (int k = 0; k < 8; ++k) final_costs[k] = wide_weighted_add(final_costs[k], wide_chosen_piece(cv, dw0, dw1, dw2, flag, pick, S, k, q), words[q], S, q);
+				cn = wide_weighted_add(cn, load_cost_piece(cur, cv.view_stride, S, q), words[q], S, q);
+			}
+		}
+	}
+#pragma unroll
+	for (int k = 0; k < 8; ++k) final_costs[k] = final_costs[k] / weight_norm;
+	int min_cost_idx = 0;   // FindMinCostIndex (ties -> last, APD.cu:155-166)
+	{
+		float mc = final_costs[0];
+#pragma unroll
+		for (int k = 1; k < 8; ++k)
+			if (final_costs[k] <= mc) { mc = final_costs[k]; min_cost_idx = k; }
+	}
+	// ---- adoption of the best neighbour (APD.cu:2546-2567) ----
+	float cost_now = cn / weight_norm;
+	const float costs_center = cost_now;
+	f4 plane_now = d.planes_snap[center];
+	float depth_now = depth_from_plane(rc, plane_now, px, py);
+	bool selected_views_written = false;
+	{
+		float fmin = final_costs[0];
+#pragma unroll
+		for (int k = 1; k < 8; ++k)
+			if (k == min_cost_idx) fmin = final_costs[k];
+		if ((flag >> min_cost_idx) & 1u) {
+			const int slot = ((pick >> min_cost_idx) & 1u) ? 8 + min_cost_idx : min_cost_idx;
+			const f4 cand = d.planes_snap[d.search_pos[(size_t)slot * L + center]];   // positions[min_cost_idx]
+			const float db = depth_from_plane(rc, cand, px, py);
+			if (db >= P.depth_min && db <= P.depth_max && fmin < cost_now) {
+				depth_now = db;
+				plane_now = cand;
+				cost_now = fmin;
+				selected_views_written = true;
+			}
+		}
+	}
+	// ---- refinement hypotheses from the values at entry (APD.cu:1333-1360) ----
+	Rng rd(d.seed, (uint32_t)center, rng_site(PH_STRONG, iter, SUB_DEPTH_RAND));
+	Rng rn(d.seed, (uint32_t)center, rng_site(PH_STRONG, iter, SUB_NORMAL));
+	Rng rp(d.seed, (uint32_t)center, rng_site(PH_STRONG, iter, SUB_DEPTH_PERT));
+	const float depth_rand = rd.uniform() * (P.depth_max - P.depth_min) + P.depth_min;
+	if (selected_views_written) d.selected_views[center] = sel_mask;
+	// the generic walk: it carries the reference's limit of 19 source directions (`if (index < 20)`), which binds from 20 mask bits on
+	const f4 n_rand = random_normal_yzl_sel(d, px, py, rn, depth_now, selected_views_written ? sel_mask : sel_entry);
 	const float dmin_p = (1 - 0.02f) * depth_now, dmax_p = (1 + 0.02f) * depth_now;
 	const float depth_pert = rp.uniform() * (dmax_p - dmin_p) + dmin_p;
 	float* rec = d.strong_rec + hi;

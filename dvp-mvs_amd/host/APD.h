@@ -204,6 +204,7 @@ public:
 	static void SetResidentDownloader(void (*copy)(float* host, const float* device, size_t count));   // device -> host copy used when a resident map of another size has to be rescaled on the host
 	const DvpTimings& GetTimings() const { return timings; }
 	int GetImageFormat() const { return image_format; }   // dvp_image_format after the view's image upload
+	int GetStrongUpdateForm() const { return ctx ? dvp_strong_update_form(ctx) : 0; }   // after RunPatchMatch*: the form its strong updates took (`apd --strong-wide on`)
 
 private:
 	int num_images = 0;

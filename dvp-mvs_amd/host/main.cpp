@@ -4,7 +4,7 @@
 //       [--rank R --world N --job ID [--transport rccl|host] [--collective-timeout SEC]] [--jacobi] [--labels]
 //       [--no-fusion | --fusion eth|tat-intermediate|tat-advanced] [--fusion-on device|host]
 //       [--edges-on host|gpu] [--labels-on host|gpu] [--cleanup-on host|gpu] [--images-on host|gpu]
-//       [--prior-on host|gpu] [--decode-on host|gpu]
+//       [--prior-on host|gpu] [--decode-on host|gpu] [--strong-wide on|off]
 //
 // Schedule.  The image pyramid has round_num levels (the longer side is halved until <= 800).  Level i
 // runs one "A" pass without geometric consistency — FIRST_INIT from scratch / the Depth-Anything prior
@@ -45,6 +45,7 @@ struct Options {
 	int collective_timeout_s = 600;
 	bool sync_io = false;
 	bool host_rescale = false;
+	bool strong_wide = false;              // --strong-wide on: views with 17 ... 31 sources take the split strong update too (DVP_STRONG_WIDE=1 unless the environment sets it)
 	bool edges_on_gpu = false;             // --edges-on gpu: the Canny edge prior is made by the engine from the resident image (APD::SetEdgesOnDevice)
 	bool prior_on_gpu = false;             // --prior-on gpu: the FIRST_INIT plane prior from dep/ + sfm/ is made by the engine into the context's planes (APD::SetPriorOnDevice)
 	bool labels_on_gpu = false;            // --labels-on gpu: GetProblemEdges makes the label maps with a dvp_labels job on the rank's device (APD::SetLabelsOnDevice)
@@ -160,6 +161,7 @@ struct ViewResult { Mat depth; };
 // `problem.iteration == 15` (main.cpp:378-385): the last pass of its default schedule (4 levels x (1 + 3) passes).  Here: at
 // that literal index too, and at the last pass of whatever plan the driver was given (--min-scale / --geom-passes shorten it).
 int g_final_iteration = 15;
+bool g_strong_wide = false;  // --strong-wide on: a view with more than 16 sources logs the form its strong updates took
 bool g_device_maps = true;   // false (--sync-io / --host-rescale): planes are downloaded and unpacked on the host   // what the exchange step needs from a finished view
 
 // `resident_depth(w, h)`: where on the device the view's new depth map goes for the views that read it as a source (or null)
@@ -209,6 +211,7 @@ ViewResult ProcessProblem(const Problem& problem, const std::function<float*(int
 	// edges_<s>.dmb by the background job, or here when that job may run after the context is gone
 	std::function<void()> fetch_edge = APD.TakeEdgeFetch();
 	if (fetch_edge && !fetch_maps) { fetch_edge(); fetch_edge = nullptr; }
+	if (g_strong_wide && nsrc > 16 && APD.GetStrongUpdateForm() != 0) ViewLog() << "Strong update: split form, " << nsrc << " views" << std::endl;
 	lap(g_device_maps ? "RunPatchMatch" : "RunPatchMatch + download");
 	Mat pixel_states = APD.GetPixelStates();
 	Mat views = APD.GetSelectedViews();
@@ -542,6 +545,11 @@ Options ParseOptions(int argc, char** argv) {
 			if (where != "host" && where != "gpu") { std::cerr << "--edges-on takes host or gpu\n"; std::exit(1); }
 			o.edges_on_gpu = where == "gpu";
 		}
+		else if (s == "--strong-wide" && a + 1 < argc) {
+			const std::string what = argv[++a];
+			if (what != "on" && what != "off") { std::cerr << "--strong-wide takes on or off\n"; std::exit(1); }
+			o.strong_wide = what == "on";
+		}
 		else if (s == "--labels-on" && a + 1 < argc) {
 			const std::string where = argv[++a];
 			if (where != "host" && where != "gpu") { std::cerr << "--labels-on takes host or gpu\n"; std::exit(1); }
@@ -582,7 +590,7 @@ Options ParseOptions(int argc, char** argv) {
 
 int main(int argc, char** argv) {
 	if (argc < 2) {
-		std::cerr << "USAGE: apd dense_folder [gpu_index] [--previews] [--max-src N] [--iters N] [--min-scale S] [--passes P] [--seed X] [--rank R --world N [--job ID]] [--jacobi] [--no-fusion | --fusion KIND] [--fusion-on device|host] [--edges-on host|gpu] [--labels-on host|gpu] [--cleanup-on host|gpu] [--images-on host|gpu] [--prior-on host|gpu] [--decode-on host|gpu] [--views-in-flight N]\n";
+		std::cerr << "USAGE: apd dense_folder [gpu_index] [--previews] [--max-src N] [--iters N] [--min-scale S] [--passes P] [--seed X] [--rank R --world N [--job ID]] [--jacobi] [--no-fusion | --fusion KIND] [--fusion-on device|host] [--edges-on host|gpu] [--labels-on host|gpu] [--cleanup-on host|gpu] [--images-on host|gpu] [--prior-on host|gpu] [--decode-on host|gpu] [--strong-wide on|off] [--views-in-flight N]\n";
 		return EXIT_FAILURE;
 	}
 	const Options opt = ParseOptions(argc, argv);
@@ -604,6 +612,10 @@ int main(int argc, char** argv) {
 	// 7.8 GB cost buffer): 4 contexts in flight are then 317 GB, more than the part has, and the contexts made last would lose
 	// buffers they need more.  Off here unless the environment says otherwise (a driver with fewer views in flight may turn it on).
 	setenv("DVP_STRONG_REUSE", "0", 0);
+	// --strong-wide on: the three-launch strong update also for views with 17 ... 31 sources (a folder of the reference's converter
+	// lists 20 per view), which otherwise take the monolithic kernel.  Same results.  DVP_STRONG_WIDE in the environment wins.
+	if (opt.strong_wide) setenv("DVP_STRONG_WIDE", "1", 0);
+	g_strong_wide = opt.strong_wide;
 	SetHostThreadShare(opt.world);
 	if (opt.world > 1) std::cout << "rank " << opt.rank << " of " << opt.world << ": " << HostThreads() << " host threads (of " << std::thread::hardware_concurrency() << " cores)" << std::endl;
 	APD::SetDevice(opt.gpu);

@@ -193,6 +193,12 @@ int dvp_set_profiling(dvp_ctx* ctx, int count_evals);
  * Same values in every format, so results do not depend on it.  DVP_NO_IMAGES8 in the environment
  * forces 0 for every set; DVP_NO_IMAGES16 turns 2 into 0 and leaves 1 alone. */
 int dvp_image_format(const dvp_ctx* ctx);
+/* The form the context's strong update takes: the view bracket of the split form's decision kernel (4, 6, 8, 10, 12, 16; 32 = the
+ * streaming kernel for up to 31 views, DVP_STRONG_WIDE=1 in the environment at dvp_ctx_create: 17 ... 31 source views, =2: every
+ * count), or 0 for a monolithic kernel.  The split form's cost buffers are allocated by the first strong update (or by
+ * dvp_ctx_reserve, bit 0): from then on a context they did not fit reports 0; before, the answer assumes that they fit.
+ * Same results in every form. */
+int dvp_strong_update_form(const dvp_ctx* ctx);
 
 /* ---- run (APD::RunPatchMatch, APD.cu:4406-4532) ---------------------------------------------- */
 int dvp_run_patchmatch(dvp_ctx* ctx);

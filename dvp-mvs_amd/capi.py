@@ -41,7 +41,8 @@ EXPORTS = ["dvp_ctx_create", "dvp_ctx_destroy", "dvp_ctx_reserve", "dvp_last_err
            "dvp_images_create", "dvp_images_destroy", "dvp_images_put", "dvp_images_drop", "dvp_images_size", "dvp_images_bytes", "dvp_images_level", "dvp_images_last_error",
            "dvp_download_image",
            "dvp_jpeg_decode", "dvp_jpeg_decode_into_store", "dvp_jpeg_decode_timings", "dvp_jpeg_decode_last_error",
-           "dvp_plane_prior", "dvp_plane_prior_stage", "dvp_plane_prior_timings"]
+           "dvp_plane_prior", "dvp_plane_prior_stage", "dvp_plane_prior_timings",
+           "dvp_view_scores", "dvp_convert_image", "dvp_pairs_last_error"]
 # ... and the one whose name holds a digit (a scan of the header for [a-z_] names does not see it)
 EXPORTS_WITH_DIGITS = ["dvp_upload_images_u8"]
 PREVIEW_DEPTH, PREVIEW_NORMAL, PREVIEW_WEAK = 1, 2, 4
@@ -155,6 +156,10 @@ def lib():
         L.dvp_plane_prior.argtypes = [vp, vp, ci, ci, vp, vp, ci, vp, pi]
         L.dvp_plane_prior_stage.argtypes = [vp, ci, vp]
         L.dvp_plane_prior_timings.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ll)]
+        L.dvp_view_scores.argtypes = [ci, ci, vp, vp, vp, ll, vp, vp, vp]
+        L.dvp_convert_image.argtypes = [ci, vp, ci, ci, ll, ci, ci, ci, ci, vp]
+        L.dvp_pairs_last_error.restype = ctypes.c_char_p
+        L.dvp_pairs_last_error.argtypes = []
         _LIB = L
     return _LIB
 
@@ -185,6 +190,37 @@ def jpeg_encode(pixels, quality=95, restart=0, device=0):
     if L.dvp_jpeg_encode(device, _p(a), W, H, C, a.strides[0], int(quality), int(restart), _p(dst), cap, ctypes.byref(n)) != 0:
         raise DvpError(L.dvp_jpeg_last_error().decode())
     return dst[:n.value].tobytes()
+
+
+def view_scores(obs_offsets, obs_point_ids, centres, point_ids, xyz, device=0):
+    """the (N, N) uint32 view-selection scores of a COLMAP model, computed on the GPU (include/dvp_mvs.h dvp_view_scores): image i's
+    point ids are obs_point_ids[obs_offsets[i]:obs_offsets[i + 1]] (-1 = none), centres (N, 3), the points point_ids (P,) at xyz (P, 3)"""
+    L = lib()
+    off = np.ascontiguousarray(obs_offsets, np.int64)
+    ids = np.ascontiguousarray(obs_point_ids, np.int64)
+    c = np.ascontiguousarray(centres, np.float64)
+    pid = np.ascontiguousarray(point_ids, np.int64)
+    x = np.ascontiguousarray(xyz, np.float64)
+    N = off.size - 1
+    if N < 1 or c.size != 3 * N or x.size != 3 * pid.size or (N >= 1 and ids.size != off[-1]):
+        raise ValueError("view_scores: the arrays' sizes do not fit together")
+    out = np.empty((N, N), np.uint32)
+    if L.dvp_view_scores(device, N, _p(off), _p(ids) if ids.size else None, _p(c), pid.size, _p(pid) if pid.size else None, _p(x) if pid.size else None, _p(out)) != 0:
+        raise DvpError(L.dvp_pairs_last_error().decode())
+    return out
+
+
+def convert_image(bgr, pad_w, pad_h, out_w, out_h, device=0):
+    """the (out_h, out_w, 3) picture the COLMAP converter writes from a (H, W, 3) B, G, R uint8 picture: zero padding to pad_w x pad_h,
+    then OpenCV's nearest-neighbour resize (include/dvp_mvs.h dvp_convert_image)"""
+    L = lib()
+    a = np.asarray(bgr)
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or a.strides[2] != 1 or a.strides[1] != 3:
+        raise ValueError("convert_image: a (H, W, 3) uint8 picture with dense rows is required")
+    out = np.empty((max(int(out_h), 0), max(int(out_w), 0), 3), np.uint8)
+    if L.dvp_convert_image(device, _p(a), a.shape[1], a.shape[0], a.strides[0], int(pad_w), int(pad_h), int(out_w), int(out_h), _p(out)) != 0:
+        raise DvpError(L.dvp_pairs_last_error().decode())
+    return out
 
 
 def _file_bytes(file):

@@ -52,6 +52,7 @@ Mat DecodeJpeg(const path& file, int channels);     // 1: luma plane (libjpeg JC
 // intermediate maps of LabelSegment for the stage-by-stage comparison with an independent reading (tests/test_host_oracles.py)
 struct LabelStages { Mat quarter, texture, texture_lines, resized, cleaned; int weak_tex_num = 0; };
 Mat LabelSegment(const int scale, const Mat& src_image, LabelStages* stages = nullptr);   // EdgeSegment mode 1 (APD.cpp:348-401, 437-499), host/labels.cpp
+Mat ReadPnm(const path& file, int channels);         // a binary P5 / P6 file with 255 levels as 1: grey, 3: BGR; empty when unreadable
 Mat ReadImageGray(const path& image_path_jpg);      // stands in for cv::imread(IMREAD_GRAYSCALE), APD.cpp:1057
 bool ImageFileSize(const path& image_path_jpg, int* width, int* height);   // from the file header, without decoding
 Mat ReadImageColor(const path& image_path_jpg);     // cv::imread(IMREAD_COLOR) (BGR), APD.cpp:1842

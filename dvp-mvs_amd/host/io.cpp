@@ -219,6 +219,10 @@ static bool read_pnm(const path& p, int want_channels, Mat& out) {
 	}
 	return true;
 }
+Mat ReadPnm(const path& file, int channels) {
+	Mat m;
+	return read_pnm(file, channels, m) ? m : Mat();
+}
 // images/<id>.jpg as the reference's converter writes it (baseline JPEG: host/jpeg.cpp); a .pgm / .ppm of
 // the same stem is used when there is no .jpg (synthetic datasets are written loss-free)
 //

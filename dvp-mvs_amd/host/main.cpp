@@ -5,6 +5,9 @@
 //       [--no-fusion | --fusion eth|tat-intermediate|tat-advanced] [--fusion-on device|host]
 //       [--edges-on host|gpu] [--labels-on host|gpu] [--cleanup-on host|gpu] [--images-on host|gpu]
 //       [--prior-on host|gpu] [--decode-on host|gpu] [--strong-wide on|off]
+//   apd --convert-from <colmap folder> <save folder> [--model-dir NAME] [--model-ext .txt|.bin] [--scale-factor F] [--max-d N]
+//       [--interval-scale F] [--sfm on|off] [--convert-on gpu|host] [--gpu N]
+//       the reference's colmap2mvsnet.py: a COLMAP model -> the folder the first form reads (host/colmap.cpp)
 //
 // Schedule.  The image pyramid has round_num levels (the longer side is halved until <= 800).  Level i
 // runs one "A" pass without geometric consistency — FIRST_INIT from scratch / the Depth-Anything prior
@@ -26,6 +29,7 @@
 #include "APD.h"
 #include <thread>
 #include "comm.h"
+#include "colmap.h"
 #include <cstdlib>
 #include <map>
 #include <set>
@@ -586,9 +590,50 @@ Options ParseOptions(int argc, char** argv) {
 	return o;
 }
 
+// apd --convert-from <colmap folder> <save folder> [options]: no engine context, no rank, no result store
+int ConvertMain(int argc, char** argv) {
+	const char* usage = "USAGE: apd --convert-from colmap_folder save_folder [--model-dir NAME] [--model-ext .txt|.bin] [--scale-factor F] [--max-d N] [--interval-scale F] [--sfm on|off] [--convert-on gpu|host] [--gpu N]\n";
+	if (argc < 4 || argv[2][0] == '-' || argv[3][0] == '-') { std::cerr << usage; return EXIT_FAILURE; }
+	ConvertOptions o;
+	o.colmap_folder = argv[2];
+	o.save_folder = argv[3];
+	for (int a = 4; a < argc; ++a) {
+		const std::string s = argv[a];
+		if (a + 1 >= argc) { std::cerr << s << " takes a value\n" << usage; return EXIT_FAILURE; }
+		const std::string v = argv[++a];
+		if (s == "--model-dir") o.model_dir = v;
+		else if (s == "--model-ext") {
+			if (v != ".txt" && v != ".bin") { std::cerr << "--model-ext takes .txt or .bin\n"; return EXIT_FAILURE; }
+			o.model_ext = v;
+		}
+		else if (s == "--scale-factor") o.scale_factor = std::atof(v.c_str());
+		else if (s == "--max-d") o.max_d = std::atoi(v.c_str());
+		else if (s == "--interval-scale") o.interval_scale = std::atof(v.c_str());
+		else if (s == "--sfm") {
+			if (v != "on" && v != "off") { std::cerr << "--sfm takes on or off\n"; return EXIT_FAILURE; }
+			o.sfm = v == "on";
+		}
+		else if (s == "--convert-on") {
+			if (v != "gpu" && v != "host") { std::cerr << "--convert-on takes gpu or host\n"; return EXIT_FAILURE; }
+			o.on_gpu = v == "gpu";
+		}
+		else if (s == "--gpu") o.device = std::atoi(v.c_str());
+		else { std::cerr << "unknown option " << s << "\n" << usage; return EXIT_FAILURE; }
+	}
+	std::error_code ec;
+	std::filesystem::create_directories(o.save_folder, ec);
+	std::string error;
+	const auto t0 = std::chrono::steady_clock::now();
+	if (!ConvertColmap(o, &error)) { std::cerr << "apd --convert-from: " << error << std::endl; return EXIT_FAILURE; }
+	std::cout << "Converted " << o.colmap_folder.string() << " -> " << o.save_folder.string() << " (scores and resampling on the " << (o.on_gpu ? "device" : "host") << ", "
+	          << std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - t0).count() << " ms)" << std::endl;
+	return EXIT_SUCCESS;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
+	if (argc >= 2 && std::string(argv[1]) == "--convert-from") return ConvertMain(argc, argv);
 	if (argc < 2) {
 		std::cerr << "USAGE: apd dense_folder [gpu_index] [--previews] [--max-src N] [--iters N] [--min-scale S] [--passes P] [--seed X] [--rank R --world N [--job ID]] [--jacobi] [--no-fusion | --fusion KIND] [--fusion-on device|host] [--edges-on host|gpu] [--labels-on host|gpu] [--cleanup-on host|gpu] [--images-on host|gpu] [--prior-on host|gpu] [--decode-on host|gpu] [--strong-wide on|off] [--views-in-flight N]\n";
 		return EXIT_FAILURE;

@@ -449,6 +449,25 @@ int dvp_plane_prior_stage(dvp_ctx* ctx, int which, void* dst);
  * sweep rows over all of them.  NULL pointers are skipped. */
 int dvp_plane_prior_timings(dvp_ctx* ctx, double* ms, long long* counts);
 
+/* ---- `apd --convert-from`: the numeric steps of the reference's colmap2mvsnet.py on the device --------------------------------------
+ * The view-selection scores of a COLMAP model (calc_score, colmap2mvsnet.py:280-302).  Image i's observations are
+ * obs_point_ids[obs_offsets[i] .. obs_offsets[i + 1]) (obs_offsets: num_images + 1 entries from 0; -1 = no point); centres: 3
+ * doubles per image; the points are point_ids[k] with xyz[3 k ..].  score_out: num_images x num_images, symmetric, zero diagonal.
+ * For i < j: S = the entries of i's list that are not -1 and occur in j's list (a duplicate in i counts each time); the score is
+ * S, or 0 when S > 0 and more than (3 * S) >> 2 of the S angles at the points between the two centres,
+ * (180 / pi) * acos(dot / |u| / |v|) in binary64 with the cosine clamped to [-1, 1], are below 1 degree - the element at
+ * int(S * 0.75) of the sorted angles is then below 1.  Integer counts, so the matrix does not depend on the order of the work.
+ * Errors: num_images outside 1 ... 16384, more than 2^31 - 1 observations or points, a point id that occurs twice, an
+ * observation that names a point absent from point_ids.  Host in, host out. */
+int dvp_view_scores(int device, int num_images, const long long* obs_offsets, const long long* obs_point_ids, const double* centres, long long num_points,
+                    const long long* point_ids, const double* xyz, uint32_t* score_out);
+/* The picture the converter writes (colmap2mvsnet.py:462-469): the w x h 8-bit B, G, R picture (`pitch` bytes per row) padded with
+ * zeros on the right and bottom to pad_w x pad_h, then cv::resize(INTER_NEAREST) to out_w x out_h:
+ * sx = min((int)floor(x * (1.0 / ((double)out_w / pad_w))), pad_w - 1), rows alike.  out: out_h dense rows of 3 * out_w bytes.
+ * Sizes of 1 ... 65535.  Host in, host out. */
+int dvp_convert_image(int device, const uint8_t* bgr, int w, int h, long long pitch, int pad_w, int pad_h, int out_w, int out_h, uint8_t* out);
+const char* dvp_pairs_last_error(void);   /* the calling thread's last error of the two above */
+
 #ifdef __cplusplus
 }
 #endif

@@ -42,7 +42,8 @@ EXPORTS = ["dvp_ctx_create", "dvp_ctx_destroy", "dvp_ctx_reserve", "dvp_last_err
            "dvp_download_image",
            "dvp_jpeg_decode", "dvp_jpeg_decode_into_store", "dvp_jpeg_decode_timings", "dvp_jpeg_decode_last_error",
            "dvp_plane_prior", "dvp_plane_prior_stage", "dvp_plane_prior_timings",
-           "dvp_view_scores", "dvp_convert_image", "dvp_pairs_last_error"]
+           "dvp_view_scores", "dvp_convert_image", "dvp_pairs_last_error",
+           "dvp_undistort_image", "dvp_undistort_last_error"]
 # ... and the one whose name holds a digit (a scan of the header for [a-z_] names does not see it)
 EXPORTS_WITH_DIGITS = ["dvp_upload_images_u8"]
 PREVIEW_DEPTH, PREVIEW_NORMAL, PREVIEW_WEAK = 1, 2, 4
@@ -160,6 +161,9 @@ def lib():
         L.dvp_convert_image.argtypes = [ci, vp, ci, ci, ll, ci, ci, ci, ci, vp]
         L.dvp_pairs_last_error.restype = ctypes.c_char_p
         L.dvp_pairs_last_error.argtypes = []
+        L.dvp_undistort_image.argtypes = [ci, vp, ci, ci, ll, ci, vp, ci, vp]
+        L.dvp_undistort_last_error.restype = ctypes.c_char_p
+        L.dvp_undistort_last_error.argtypes = []
         _LIB = L
     return _LIB
 
@@ -220,6 +224,25 @@ def convert_image(bgr, pad_w, pad_h, out_w, out_h, device=0):
     out = np.empty((max(int(out_h), 0), max(int(out_w), 0), 3), np.uint8)
     if L.dvp_convert_image(device, _p(a), a.shape[1], a.shape[0], a.strides[0], int(pad_w), int(pad_h), int(out_w), int(out_h), _p(out)) != 0:
         raise DvpError(L.dvp_pairs_last_error().decode())
+    return out
+
+
+# COLMAP's camera model ids (csrc/dvp_undistort.hpp)
+CAMERA_MODELS = {"SIMPLE_PINHOLE": 0, "PINHOLE": 1, "SIMPLE_RADIAL": 2, "RADIAL": 3, "OPENCV": 4, "OPENCV_FISHEYE": 5, "FULL_OPENCV": 6, "FOV": 7,
+                 "SIMPLE_RADIAL_FISHEYE": 8, "RADIAL_FISHEYE": 9, "THIN_PRISM_FISHEYE": 10}
+
+
+def undistort_image(bgr, model, params, device=0):
+    """the (H, W, 3) B, G, R uint8 picture resampled into the pinhole camera with its COLMAP camera's fx, fy, cx, cy and size
+    (include/dvp_mvs.h dvp_undistort_image); model: COLMAP's name or id, params: COLMAP's order; rows may be padded"""
+    L = lib()
+    a = np.asarray(bgr)
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or a.strides[2] != 1 or a.strides[1] != 3:
+        raise ValueError("undistort_image: a (H, W, 3) uint8 picture with dense pixels is required")
+    p = np.ascontiguousarray(params, np.float64).reshape(-1)
+    out = np.empty((a.shape[0], a.shape[1], 3), np.uint8)
+    if L.dvp_undistort_image(device, _p(a), a.shape[1], a.shape[0], a.strides[0], CAMERA_MODELS.get(model, model), _p(p), p.size, _p(out)) != 0:
+        raise DvpError(L.dvp_undistort_last_error().decode())
     return out
 
 

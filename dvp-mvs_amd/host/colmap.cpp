@@ -8,6 +8,9 @@
 //                or the same text here), encoded by dvp_jpeg_encode at quality 95
 //   sfm/         the project's own file, which nothing in the reference writes: one line per observation with a point, what
 //                host/prior.cpp reads
+//   --undistort on   the project's own stage too (csrc/dvp_undistort.hpp): every decoded picture is resampled into the pinhole camera
+//                the cams already describe - dvp_undistort_image or the same text here - before it is padded, and sfm/ holds the
+//                points' pinhole projections in place of the observations made in the distorted picture
 // Plain C++: the device is reached through the C ABI only.
 #include "colmap.h"
 
@@ -16,6 +19,7 @@
 #include <map>
 
 #include "../csrc/dvp_pairs.hpp"
+#include "../csrc/dvp_undistort.hpp"
 #include "APD.h"
 
 namespace {
@@ -458,6 +462,15 @@ bool ConvertColmap(const ConvertOptions& opt, std::string* error) {
 	ConvertedCameras cams;
 	if (!ConvertCameras(model, opt, &cams, error)) return false;
 
+	// --undistort on: every picture's camera, by image; FOV has no undistortion here
+	std::vector<const ColmapCamera*> camera_of((size_t)n, nullptr);
+	if (opt.undistort)
+		for (int i = 0; i < n; ++i) {
+			for (const ColmapCamera& c : model.cameras)
+				if (c.id == model.images[(size_t)i].camera_id) camera_of[(size_t)i] = &c;   // (ConvertCameras has met every id)
+			if (camera_of[(size_t)i]->model == "FOV") return fail(error, "camera " + std::to_string(camera_of[(size_t)i]->id) + ": --undistort on cannot undistort the FOV camera model (image " + model.images[(size_t)i].name + ")");
+		}
+
 	// the sizes first, from the headers: nothing is written when an input is unusable
 	const path image_dir = opt.colmap_folder / "images";
 	int max_w = 0, max_h = 0;
@@ -469,6 +482,12 @@ bool ConvertColmap(const ConvertOptions& opt, std::string* error) {
 			if (!std::filesystem::exists(file) || !ImageFileSize(file, &w, &h)) return fail(error, file.string() + ": missing, or its header is unreadable");
 			max_w = std::max(max_w, w);
 			max_h = std::max(max_h, h);
+			if (opt.undistort) {
+				const ColmapCamera& c = *camera_of[(size_t)(&im - model.images.data())];
+				if (c.width != w || c.height != h)
+					return fail(error, file.string() + ": the picture is " + std::to_string(w) + " x " + std::to_string(h) + ", its camera " + std::to_string(c.id) + " " + std::to_string(c.width) + " x " +
+					                       std::to_string(c.height) + " (--undistort on needs the pictures the model was made from)");
+			}
 		}
 
 	// view selection
@@ -508,7 +527,19 @@ bool ConvertColmap(const ConvertOptions& opt, std::string* error) {
 			for (size_t o = 0; o < im.point_ids.size(); ++o) {
 				if (im.point_ids[o] == -1) continue;
 				const ColmapPoint& p = model.points[point_at.at(im.point_ids[o])];   // (ConvertCameras has met every id)
-				text += PyFloatStr(im.xy[2 * o] / opt.scale_factor) + " " + PyFloatStr(im.xy[2 * o + 1] / opt.scale_factor) + " " + PyFloatStr(p.xyz[0]) + " " + PyFloatStr(p.xyz[1]) + " " +
+				double px = im.xy[2 * o], py = im.xy[2 * o + 1];
+				if (opt.undistort) {
+					// where the point lies in the undistorted picture: its pinhole projection, fx Xc / Zc + cx with (Xc, Yc, Zc) = R X + t
+					const double* e = &cams.extrinsic[16 * (size_t)i];
+					const ColmapCamera& cam = *camera_of[(size_t)i];
+					const dvpund::Camera pin = dvpund::make_camera(kind_by_name(cam.model)->id, cam.params.data());
+					const double xc = e[0] * p.xyz[0] + e[1] * p.xyz[1] + e[2] * p.xyz[2] + e[3], yc = e[4] * p.xyz[0] + e[5] * p.xyz[1] + e[6] * p.xyz[2] + e[7],
+					             zc = e[8] * p.xyz[0] + e[9] * p.xyz[1] + e[10] * p.xyz[2] + e[11];
+					if (!(zc > 0)) continue;
+					px = pin.fx * xc / zc + pin.cx;
+					py = pin.fy * yc / zc + pin.cy;
+				}
+				text += PyFloatStr(px / opt.scale_factor) + " " + PyFloatStr(py / opt.scale_factor) + " " + PyFloatStr(p.xyz[0]) + " " + PyFloatStr(p.xyz[1]) + " " +
 				        PyFloatStr(p.xyz[2]) + " " + std::to_string(p.rgb[0]) + " " + std::to_string(p.rgb[1]) + " " + std::to_string(p.rgb[2]) + "\n";
 			}
 			if (!write_text(opt.save_folder / "sfm" / (ToFormatIndex(i) + ".txt"), text, error)) return false;
@@ -523,6 +554,20 @@ bool ConvertColmap(const ConvertOptions& opt, std::string* error) {
 		const path file = image_dir / model.images[(size_t)i].name;
 		Mat bgr;
 		if (!read_input(file, opt, &bgr, error)) return false;
+		if (opt.undistort) {
+			const ColmapCamera& c = *camera_of[(size_t)i];
+			const int kind = kind_by_name(c.model)->id;
+			Mat flat(bgr.rows, bgr.cols, CV_8UC3);
+			if (opt.on_gpu) {
+				if (dvp_undistort_image(opt.device, bgr.data, bgr.cols, bgr.rows, (long long)bgr.step, kind, c.params.data(), kind_by_name(c.model)->num_params, flat.data) != 0)
+					return fail(error, file.string() + ": " + dvp_undistort_last_error());
+			} else {
+				const std::string what = dvpund::check_undistort(bgr.data, bgr.cols, bgr.rows, (long long)bgr.step, kind, c.params.data(), kind_by_name(c.model)->num_params, flat.data);
+				if (!what.empty()) return fail(error, file.string() + ": " + what);
+				dvpund::undistort_image_serial(dvpund::make_camera(kind, c.params.data()), bgr.data, bgr.cols, bgr.rows, (size_t)bgr.step, flat.data);
+			}
+			bgr = flat;
+		}
 		if (opt.on_gpu) {
 			if (dvp_convert_image(opt.device, bgr.data, bgr.cols, bgr.rows, (long long)bgr.step, max_w, max_h, out_w, out_h, picture.data()) != 0) return fail(error, file.string() + ": " + dvp_pairs_last_error());
 		} else {

@@ -39,6 +39,7 @@ struct ConvertOptions {
 	bool sfm = true;        // write sfm/<id>.txt
 	bool on_gpu = true;     // the scores, the JPEG reconstruction and the resampling on `device`; false: the same text on the host
 	bool images = true;     // false: pair.txt, cams/ and sfm/ only (needs no device)
+	bool undistort = false; // true: every picture resampled into the pinhole camera of its COLMAP camera, sfm/ written for that picture (csrc/dvp_undistort.hpp)
 	int device = 0;
 };
 // Replaces files of the same names under save_folder and deletes nothing.  false: *error says what stopped it.

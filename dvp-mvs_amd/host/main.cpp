@@ -6,7 +6,7 @@
 //       [--edges-on host|gpu] [--labels-on host|gpu] [--cleanup-on host|gpu] [--images-on host|gpu]
 //       [--prior-on host|gpu] [--decode-on host|gpu] [--strong-wide on|off]
 //   apd --convert-from <colmap folder> <save folder> [--model-dir NAME] [--model-ext .txt|.bin] [--scale-factor F] [--max-d N]
-//       [--interval-scale F] [--sfm on|off] [--convert-on gpu|host] [--gpu N]
+//       [--interval-scale F] [--sfm on|off] [--convert-on gpu|host] [--undistort on|off] [--gpu N]
 //       the reference's colmap2mvsnet.py: a COLMAP model -> the folder the first form reads (host/colmap.cpp)
 //
 // Schedule.  The image pyramid has round_num levels (the longer side is halved until <= 800).  Level i
@@ -592,7 +592,7 @@ Options ParseOptions(int argc, char** argv) {
 
 // apd --convert-from <colmap folder> <save folder> [options]: no engine context, no rank, no result store
 int ConvertMain(int argc, char** argv) {
-	const char* usage = "USAGE: apd --convert-from colmap_folder save_folder [--model-dir NAME] [--model-ext .txt|.bin] [--scale-factor F] [--max-d N] [--interval-scale F] [--sfm on|off] [--convert-on gpu|host] [--gpu N]\n";
+	const char* usage = "USAGE: apd --convert-from colmap_folder save_folder [--model-dir NAME] [--model-ext .txt|.bin] [--scale-factor F] [--max-d N] [--interval-scale F] [--sfm on|off] [--convert-on gpu|host] [--undistort on|off] [--gpu N]\n";
 	if (argc < 4 || argv[2][0] == '-' || argv[3][0] == '-') { std::cerr << usage; return EXIT_FAILURE; }
 	ConvertOptions o;
 	o.colmap_folder = argv[2];
@@ -617,6 +617,10 @@ int ConvertMain(int argc, char** argv) {
 			if (v != "gpu" && v != "host") { std::cerr << "--convert-on takes gpu or host\n"; return EXIT_FAILURE; }
 			o.on_gpu = v == "gpu";
 		}
+		else if (s == "--undistort") {
+			if (v != "on" && v != "off") { std::cerr << "--undistort takes on or off\n"; return EXIT_FAILURE; }
+			o.undistort = v == "on";
+		}
 		else if (s == "--gpu") o.device = std::atoi(v.c_str());
 		else { std::cerr << "unknown option " << s << "\n" << usage; return EXIT_FAILURE; }
 	}
@@ -625,7 +629,7 @@ int ConvertMain(int argc, char** argv) {
 	std::string error;
 	const auto t0 = std::chrono::steady_clock::now();
 	if (!ConvertColmap(o, &error)) { std::cerr << "apd --convert-from: " << error << std::endl; return EXIT_FAILURE; }
-	std::cout << "Converted " << o.colmap_folder.string() << " -> " << o.save_folder.string() << " (scores and resampling on the " << (o.on_gpu ? "device" : "host") << ", "
+	std::cout << "Converted " << o.colmap_folder.string() << " -> " << o.save_folder.string() << " (scores and resampling on the " << (o.on_gpu ? "device" : "host") << (o.undistort ? ", pictures undistorted" : "") << ", "
 	          << std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - t0).count() << " ms)" << std::endl;
 	return EXIT_SUCCESS;
 }

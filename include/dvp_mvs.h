@@ -468,6 +468,21 @@ int dvp_view_scores(int device, int num_images, const long long* obs_offsets, co
 int dvp_convert_image(int device, const uint8_t* bgr, int w, int h, long long pitch, int pad_w, int pad_h, int out_w, int out_h, uint8_t* out);
 const char* dvp_pairs_last_error(void);   /* the calling thread's last error of the two above */
 
+/* ---- `apd --convert-from ... --undistort on`: the reference has no counterpart (colmap2mvsnet.py expects pictures that COLMAP's
+ * image_undistorter has made, and keeps fx, fy, cx, cy of whatever model it meets); the project's own definition -----------------
+ * The w x h 8-bit B, G, R picture (`pitch` bytes per row) taken with COLMAP camera model `model` (COLMAP's id, 0 ... 10) and
+ * `params` (COLMAP's order: f or fx, fy; cx, cy; the distortion parameters) resampled into the pinhole camera with the same
+ * fx, fy, cx, cy and the same size.  For output pixel (x, y): u = (x + 0.5 - cx) / fx, v alike; (u', v') = the model's forward
+ * distortion of (u, v); sx = fx u' + cx - 0.5, sy alike; both quantised to 1 / 32 pixel, floor(32 s + 0.5), and clamped to
+ * [-64, 32 size + 64]; then cv::remap(INTER_LINEAR, BORDER_CONSTANT)'s fixed-point rule: the four taps weighted with the two
+ * 5-bit fractions, + 512, >> 10, a tap outside the picture counting as 0, a NaN coordinate giving a zero pixel.  Binary64, one
+ * rounding per operator, with the library's own atan for the fisheye models (csrc/dvp_undistort.hpp): the bytes do not depend on
+ * the device or on libm.  out: h dense rows of 3 * w bytes.  No output size is chosen and nothing is cropped.
+ * Errors: a null pointer, an unknown model, FOV (7), a num_params that is not the model's, sizes outside 1 ... 65535, a pitch
+ * below 3 * w.  Host in, host out; safe from several threads. */
+int dvp_undistort_image(int device, const uint8_t* bgr, int w, int h, long long pitch, int model, const double* params, int num_params, uint8_t* out);
+const char* dvp_undistort_last_error(void);   /* the calling thread's last error of the one above */
+
 #ifdef __cplusplus
 }
 #endif

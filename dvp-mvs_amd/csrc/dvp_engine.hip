@@ -380,7 +380,7 @@ extern "C" __global__ void __launch_bounds__(256) dvp_gen_neighbours_list(const 
 }
 DVP_KERNEL_LIST(dvp_neighbour_update_list, DVP_ST_NEIGHBOUR_UPDATE, 1)
 DVP_KERNEL_LIST(dvp_ransac_fit_plane_list, DVP_ST_RANSAC_FIT, 1)
-// ... and the same launch site with one wave per WEAK pixel, lane = draw (dvp_weak_wave.hpp: ransac_fit_plane_wave; DVP_RANSAC_WAVE=1 —
+// ... and the same launch site with one wave per WEAK pixel, lane = draw (dvp_ransac.hpp: ransac_fit_plane_wave; DVP_RANSAC_WAVE=1 —
 // measured no faster than the lane kernel, whose 0.18 lane utilisation turns out not to be what it waits for: kept as the record of that)
 extern "C" __global__ void __launch_bounds__(64) dvp_ransac_fit_plane_wave(const Dev d, const ListArgs a) {
 	__shared__ RansacShared sh[1];
@@ -410,7 +410,7 @@ __device__ __forceinline__ void weak_wave_body(const Dev& d, const ListArgs& a) 
 	if (d.eval_counter && n) atomicAdd(d.eval_counter, n);
 }
 // first half of GenNeighbours (directional anchor search + label extension): one wave per WEAK pixel, the tries of a
-// direction over the lanes (dvp_weak_wave.hpp: gen_neighbours_search_wave)
+// direction over the lanes (dvp_neighbours.hpp: gen_neighbours_search_wave)
 #ifndef DVP_LB_GN
 #define DVP_LB_GN 8   // waves per SIMD (64 VGPRs + 164 B scratch; measured 86 ms per cfg3 pass, 4 waves without scratch: 105 ms)
 #endif

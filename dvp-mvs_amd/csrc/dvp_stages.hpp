@@ -3,6 +3,8 @@
 #ifndef DVP_STAGES_HPP_
 #define DVP_STAGES_HPP_
 
+#include "dvp_edge_inform.hpp"
+#include "dvp_ransac.hpp"
 #include "dvp_weak_wave.hpp"
 #include "dvp_weak_phased.hpp"
 #include <vector>

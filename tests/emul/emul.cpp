@@ -609,7 +609,7 @@ int emu_run_patchmatch(void* c) {
 	return 0;
 }
 
-// the line test of the weak path, both forms (dvp_weak.hpp): which = 0 the closed-form block skipper the kernels call, 1 the
+// the line test of the weak path, both forms (dvp_neighbours.hpp): which = 0 the closed-form block skipper the kernels call, 1 the
 // definition that makes every step; the edge map is the context's (packed here)
 int emu_line_test(void* c, int ax, int ay, int bx, int by, int which) {
 	Emu& e = *(Emu*)c;

@@ -321,7 +321,7 @@ def strong_update_forms_case(_pair, _run_and_compare, form, S, monkeypatch):
 
 
 def test_line_test_closed_form_equals_the_stepping_walk():
-    """bresenham_hits_edge (csrc/dvp_weak.hpp): the kernels' form jumps over blocks of eight steps whose bounding box holds no
+    """bresenham_hits_edge (csrc/dvp_neighbours.hpp): the kernels' form jumps over blocks of eight steps whose bounding box holds no
     edge pixel, from the closed-form state of the reference's walk (BresenhamLine, APD.cu:267-311), instead of making every
     step.  Against the stepping definition on sparse, medium and dense edge maps: every pair of end points with
     |dx|, |dy| <= 40 around several centres (all the small slopes, both majors, the degenerate ones), long walks up to and

@@ -153,6 +153,7 @@ struct Dev {
 	float* sweep_pc;           // [61][L]: the folded cost line of the central window, handed from the first decision pass to the second
 	int sweep_px0;             // sweep passes in bands of rows (a context told to keep sweep_cost small): sweep_cost holds the pixels from this linear index on,
 	int sweep_row0, sweep_row1;   // and the decision passes of a band take the rows [row0, row1) (row1 == 0: the whole image)
+	int sweep_all_slots;       // DVP_SWEEP_ALL_SLOTS: DepthToWeak also evaluates the two end slots no decision reads (dvp_forms.hpp: sweep_slot_read)
 	int half_w;
 	uint32_t* edge_bits;       // the edge map as 32x32-pixel bit tiles (128 B each), see edge_bit()
 	int edge_tiles_x;

@@ -293,7 +293,7 @@ extern "C" __global__ void __launch_bounds__(256) dvp_sweep_decide2(const Dev d,
 // evaluates (71 % of the pixels select a given view at cfg3: 2.8 rounds of 64 instead of 4 rows with 29 % of the lanes idle).
 // a.iter = stage (0: central window + LocalRefine's extra slot, 1: the rest of the line for pixels with a central peak).
 // (a tile is 64 x kSweepRows pixels: dvp_forms.hpp)
-template <int SMP>
+template <int SMP, bool ALL>
 __device__ __forceinline__ void sweep_eval_body(const Dev& d, const LaunchArgs& a) {
 	const int lane = threadIdx.x;
 	const int v = blockIdx.y;
@@ -332,7 +332,7 @@ __device__ __forceinline__ void sweep_eval_body(const Dev& d, const LaunchArgs& 
 	for (int i0 = 0; i0 < n; i0 += 64) {
 		if (i0 + lane < n) {
 			const int e = list[i0 + lane];
-			sweep_eval_px<SMP>(d, tx * 64 + (e & 63), ty * kSweepRows + (e >> 6), v, a.iter, tab, d.eval_counter ? &cnt : nullptr, cams);
+			sweep_eval_px<SMP, ALL>(d, tx * 64 + (e & 63), ty * kSweepRows + (e >> 6), v, a.iter, tab, d.eval_counter ? &cnt : nullptr, cams);
 		}
 	}
 	if (d.eval_counter && cnt) atomicAdd(d.eval_counter, cnt);
@@ -364,8 +364,11 @@ __device__ __forceinline__ void sweep_border_body(const Dev& d, const LaunchArgs
 }
 extern "C" __global__ void __launch_bounds__(64, DVP_LB_HEAVY) dvp_sweep_border(const Dev d, const LaunchArgs a) { sweep_border_body<0>(d, a); }
 extern "C" __global__ void __launch_bounds__(64, DVP_LB_HEAVY) dvp_sweep_border_exact(const Dev d, const LaunchArgs a) { sweep_border_body<1>(d, a); }
-extern "C" __global__ void __launch_bounds__(64, DVP_LB_HEAVY) dvp_sweep_eval(const Dev d, const LaunchArgs a) { sweep_eval_body<0>(d, a); }
-extern "C" __global__ void __launch_bounds__(64, DVP_LB_HEAVY) dvp_sweep_eval_exact(const Dev d, const LaunchArgs a) { sweep_eval_body<1>(d, a); }
+extern "C" __global__ void __launch_bounds__(64, DVP_LB_HEAVY) dvp_sweep_eval(const Dev d, const LaunchArgs a) { sweep_eval_body<0, false>(d, a); }
+extern "C" __global__ void __launch_bounds__(64, DVP_LB_HEAVY) dvp_sweep_eval_exact(const Dev d, const LaunchArgs a) { sweep_eval_body<1, false>(d, a); }
+// DVP_SWEEP_ALL_SLOTS=1 (A/B): the same with the two end slots of the line, which no decision reads (dvp_forms.hpp: sweep_slot_read)
+extern "C" __global__ void __launch_bounds__(64, DVP_LB_HEAVY) dvp_sweep_eval_all(const Dev d, const LaunchArgs a) { sweep_eval_body<0, true>(d, a); }
+extern "C" __global__ void __launch_bounds__(64, DVP_LB_HEAVY) dvp_sweep_eval_exact_all(const Dev d, const LaunchArgs a) { sweep_eval_body<1, true>(d, a); }
 
 // the weak-path launch sites: one lane per entry of the WEAK-pixel list
 DVP_KERNEL_LIST(dvp_find_nearest_strong_list, DVP_ST_FIND_NEAREST_STRONG, 1)
@@ -1310,6 +1313,7 @@ static void sync_dev_struct(dvp_ctx* c) {
 	d.depths = c->depths; d.cameras = c->cameras; d.views = c->views; d.sector_taps = c->sector_taps; d.sector_start = c->sector_start;
 	d.search_pos = c->search_pos;
 	d.sweep_px0 = 0; d.sweep_row0 = 0; d.sweep_row1 = 0;   // (set per band by the sweep passes' launches)
+	d.sweep_all_slots = c->sw.sweep_all_slots ? 1 : 0;
 	d.sweep_rec = c->sweep_rec; d.sweep_cost = c->sweep_cost; d.sweep_pc = c->sweep_pc; d.slot_costs = c->slot_costs; d.strong_rec = c->strong_rec; d.half_w = (c->W + 1) / 2;
 	d.reuse_costs = c->reuse_costs; d.reuse_keys = c->reuse_keys; d.reuse_hdr = c->reuse_hdr; d.reuse_epoch = c->reuse_epoch;
 	d.planes = c->planes; d.planes_snap = c->planes_snap; d.costs = c->costs; d.costs_snap = c->costs_snap;
@@ -2135,9 +2139,10 @@ static int launch_sweeps(dvp_ctx* c, const LaunchGeom& g, const LaunchArgs& a, b
 				b0.tiles = b1.tiles = etx * bty;
 				bgrid = dim3((unsigned)(etx * bty), (unsigned)(c->NI - 1));
 			}
-			hipLaunchKernelGGL(DVP_PICK(dvp_sweep_eval, ), bgrid, dim3(64), 0, c->stream, db, b0);
+			const auto eval = c->sw.sweep_all_slots ? DVP_PICK(dvp_sweep_eval, _all) : DVP_PICK(dvp_sweep_eval, );
+			hipLaunchKernelGGL(eval, bgrid, dim3(64), 0, c->stream, db, b0);
 			hipLaunchKernelGGL(dvp_sweep_decide1, grid, block, 0, c->stream, db, a);
-			if (f.second_eval) hipLaunchKernelGGL(DVP_PICK(dvp_sweep_eval, ), bgrid, dim3(64), 0, c->stream, db, b1);
+			if (f.second_eval) hipLaunchKernelGGL(eval, bgrid, dim3(64), 0, c->stream, db, b1);
 			hipLaunchKernelGGL(dvp_sweep_decide2, grid, block, 0, c->stream, db, a);
 		}
 		if (f.border_kernel) {

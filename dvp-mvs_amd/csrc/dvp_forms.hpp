@@ -22,6 +22,18 @@ constexpr int kSweepRows = DVP_SWEEP_ROWS;   // rows of a dvp_sweep_eval tile (6
 constexpr int kSweepFields = 73;    // [0, 61): slot pd + 30 — ncc for |pd| <= 5, ncc + factor * geom otherwise; [61, 72): geom of slot |pd| <= 5
 constexpr int sweep_window(const DvpParams& P) { int cw = P.weak_peak_radius + 1; if (cw < 5) cw = 5; if (cw > 30) cw = 30; return cw; }
 constexpr size_t sweep_cost_floats(size_t L, int S) { return ((L + 63) / 64) * 64 * (size_t)S * kSweepFields; }
+// Is sweep slot pd (-30 ... 30, line entry pd + 30) evaluated, fetched and folded under a window of half-width cw (sweep_window)?
+// No decision reads the two end slots: the peak searches of DepthToWeak are `for (i = 2; i < 59; ++i)` over the entries i - 1, i,
+// i + 1, i.e. 1 ... 59.  Entry 60 is read nowhere else.  Entry 0 is read once more, as p_costs[min_peak] with min_peak == 0, i.e. when
+// the line has no peak below 2 — and that statement is reached only by pixels with a central peak <= 0.5 (depth_to_weak_px:
+// `if (!central_peak) state = DVP_WEAK` comes first; sweep_decide2_cw returns unless SWF_PEAK is set), whose entries i - 1, i, i + 1
+// lie inside 1 ... 59 and make the same i a peak of the full search, so min_peak != 0 there.  LocalRefine reads the slots -5 ... 5.
+// So both are left out and their line entries are the constant 2, the value of a slot outside the depth range.
+// cw == 30 (weak_peak_radius >= 29, the whole line in the first stage): the argument holds there too (the central-peak test skips
+// i < 2 and i > 58), but the slots stay: in dvp_sweep_eval they would have to be stepped over in the middle of the first stage's
+// walk, and the evaluator's schedule pays for every live value in that loop (profiles/sweep_dead_slots.txt).
+// all_slots: DVP_SWEEP_ALL_SLOTS=1, all 61 everywhere (A/B).
+constexpr bool sweep_slot_read(int cw, int pd, bool all_slots) { return all_slots || cw == 30 || (pd > -30 && pd < 30); }
 
 inline bool env_flag(const char* name, bool unset) { const char* e = getenv(name); return e ? atoi(e) != 0 : unset; }
 
@@ -31,6 +43,7 @@ struct FormSwitches {   // unset defaults; =0 / =1 are atoi(e) != 0, "(present)"
 	bool refine_lanes = true, eval_items = true;    // DVP_REFINE_LANES=0: dvp_strong_refine; DVP_EVAL_ITEMS=0: dvp_strong_eval (a pixel per lane)
 	int strong_wide = 0;          // DVP_STRONG_WIDE=1: the split form also for 17 <= S <= 31 (dvp_strong_decide_wide); =2: that decision kernel at every S (A/B)
 	bool sweep_split = true, sweep_force = false;   // DVP_SWEEP_SPLIT=0: the fused per-pixel kernel; =2: the passes also without the geometric term
+	bool sweep_all_slots = false; // DVP_SWEEP_ALL_SLOTS=1: the sweep site also evaluates the two end slots no decision reads (sweep_slot_read; A/B)
 	double sweep_band_gb = 0.0;   // DVP_SWEEP_BAND_GB=g: sweep_cost holds a band of rows of at most g GB (0: the whole image)
 	bool anchor_tab_off = false;  // DVP_WEAK_ANCHOR_TAB=0: the weak update forms the reference side per item
 	bool gn_wave = false, ransac_wave = false;      // DVP_GN_WAVE=1 / DVP_RANSAC_WAVE=1: a wave per WEAK pixel (measured no faster)
@@ -49,6 +62,7 @@ inline FormSwitches read_form_switches() {
 	s.eval_items = env_flag("DVP_EVAL_ITEMS", true);
 	if (const char* e = getenv("DVP_STRONG_WIDE")) { const int v = atoi(e); s.strong_wide = v == 0 ? 0 : (v == 2 ? 2 : 1); }
 	if (const char* e = getenv("DVP_SWEEP_SPLIT")) { s.sweep_split = atoi(e) != 0; s.sweep_force = atoi(e) == 2; }
+	s.sweep_all_slots = env_flag("DVP_SWEEP_ALL_SLOTS", false);
 	if (const char* e = getenv("DVP_SWEEP_BAND_GB")) s.sweep_band_gb = atof(e);
 	s.anchor_tab_off = !env_flag("DVP_WEAK_ANCHOR_TAB", true);
 	s.gn_wave = env_flag("DVP_GN_WAVE", false);

@@ -1506,6 +1506,7 @@ DVP_HD void depth_to_weak_px(const Dev& d, int px, int py, PatchTab tab, unsigne
 			if (!central_peak) break;
 		}
 		const int pd = k <= 2 * cw ? k - cw : (k - (2 * cw + 1) < 30 - cw ? k - (2 * cw + 1) - 30 : k - 30);
+		if (!sweep_slot_read(cw, pd, d.sweep_all_slots != 0)) { p_costs[pd + 30] = 2.0f; continue; }   // the two end slots: no decision reads them
 		const float p_depth = rc.K[0] * base_line / (disp + pd);
 		if (p_depth < P.depth_min || p_depth > P.depth_max) { p_costs[pd + 30] = 2.0f; continue; }
 		f4 pl = origin;
@@ -1666,7 +1667,8 @@ DVP_HD void local_refine_px(const Dev& d, int px, int py, PatchTab tab, unsigned
 //                      pixels that selected the view with a weight > 0 (compacted tile by tile: dvp_sweep_eval), nothing live
 //                      but the evaluator -> sweep_cost.  Stage 0: the central window (-cw..cw) and LocalRefine's extra slot
 //                      (the current depth); stage 1: the rest of the line, only for pixels whose window holds a cost peak
-//                      (the others are WEAK whatever the rest says: exact, see depth_to_weak_px)
+//                      (the others are WEAK whatever the rest says: exact, see depth_to_weak_px).  Its end slots -30 and +30 are
+//                      not evaluated: no decision reads them (dvp_forms.hpp: sweep_slot_read), 59 slots of the 61
 //   sweep_decide1_px   per pixel: folds the window in the reference's view order, decides `central peak`, does LocalRefine
 //                      (its slots -5..5 and the current depth are all stage 0)
 //   sweep_decide2_px   per pixel with a central peak: folds the rest of the line, peak statistics -> weak_info
@@ -1743,7 +1745,9 @@ DVP_HD bool sweep_go(const Dev& d, int center, int v, int stage) {
 }
 
 // `cams`: the reference camera and the camera of view v + 1 ([0], [1]) where the caller keeps them (LDS), or null
-template <int SMP>
+// ALL: the two end slots are evaluated too (DVP_SWEEP_ALL_SLOTS: dvp_sweep_eval_all).  A template argument, so that the walk's bounds
+// stay constants: with run-time bounds the compiler schedules the loop body worse by more than the two slots save.
+template <int SMP, bool ALL = false>
 DVP_HD void sweep_eval_px(const Dev& d, int px, int py, int v, int stage, PatchTab tab, unsigned long long* nevals, const DvpCamera* cams = nullptr) {
 	const int W = d.width;
 	const int center = px + py * W;
@@ -1769,7 +1773,10 @@ DVP_HD void sweep_eval_px(const Dev& d, int px, int py, int v, int stage, PatchT
 	const int cw = sweep_window(P);
 	float* out = d.sweep_cost + sweep_cost_index(d, v, 0, center);
 	const size_t FS = sweep_field_stride(d);
-	const int k0 = stage == 0 ? 0 : 2 * cw + 1, k1 = stage == 0 ? 2 * cw + 1 + (refine ? 1 : 0) : 61;
+	// The end slots -30 and +30, which no decision reads, are stage 1's first and last k (sweep_slot_read: at cw == 30 they are in
+	// stage 0 and stay): the walk loses them through its bounds, their fields stay unwritten
+	constexpr int kEnds = (sweep_slot_read(5, -30, ALL) || sweep_slot_read(5, 30, ALL)) ? 0 : 1;   // (5: stage 1 exists below the clamp only, any cw < 30)
+	const int k0 = stage == 0 ? 0 : 2 * cw + 1 + kEnds, k1 = stage == 0 ? 2 * cw + 1 + (refine ? 1 : 0) : 61 - kEnds;
 	for (int k = k0; k < k1; ++k) {
 		const bool extra = stage == 0 && k == 2 * cw + 1;   // LocalRefine's current-depth slot
 		const int pd = k <= 2 * cw ? k - cw : (k - (2 * cw + 1) < 30 - cw ? k - (2 * cw + 1) - 30 : k - 30);
@@ -1927,7 +1934,8 @@ DVP_HD void sweep_decide1_px(const Dev& d, int px, int py) {
 	for (int pd = -cw; pd <= cw; ++pd) {
 		const float p_depth = rc.K[0] * base_line / (disp + pd);
 		float pcv = 2.0f;
-		if (!(p_depth < P.depth_min || p_depth > P.depth_max)) {
+		// (cw == 30: the end slots are in this window and stay, see sweep_slot_read)
+		if (sweep_slot_read(cw, pd, d.sweep_all_slots != 0) && !(p_depth < P.depth_min || p_depth > P.depth_max)) {
 			const bool both = refine && pd >= -5 && pd <= 5;
 			float pc, lr;
 			sweep_fold(d, center, pd, sel, vw, both, &pc, &lr);
@@ -1969,7 +1977,8 @@ DVP_HD void sweep_decide1_px(const Dev& d, int px, int py) {
 // view-outside form used below for the rest of the line 13 — 168 registers and a predicate per slot)
 // CW: the window half-width known at compile time (5 at the default weak_peak_radius), 0 = read from the parameters.  With a run-time
 // window every slot's `inside the window?` is a scalar branch around its load, and a wait at every join.
-template <int CW>
+// ALL: the two end slots are fetched and folded too (DVP_SWEEP_ALL_SLOTS); otherwise their entries are the constant 2 (sweep_slot_read)
+template <int CW, bool ALL>
 DVP_HD void sweep_decide2_cw(const Dev& d, int px, int py) {
 	const int W = d.width;
 	const int center = px + py * W;
@@ -1986,7 +1995,7 @@ DVP_HD void sweep_decide2_cw(const Dev& d, int px, int py) {
 	const size_t FS = sweep_field_stride(d);
 	uint64_t live = 0;   // slots outside the window that are inside the depth range
 	for (int pd = -30; pd <= 30; ++pd) {
-		if (pd >= -cw && pd <= cw) continue;
+		if ((pd >= -cw && pd <= cw) || !sweep_slot_read(cw, pd, ALL)) continue;
 		const float p_depth = rc.K[0] * base_line / (disp + pd);
 		if (!(p_depth < P.depth_min || p_depth > P.depth_max)) live |= (uint64_t)1 << (pd + 30);
 	}
@@ -2007,6 +2016,7 @@ DVP_HD void sweep_decide2_cw(const Dev& d, int px, int py) {
 			const int pd = i - 30;
 			cst[i] = 0.0f;
 			if (pd >= -cw && pd <= cw) continue;          // (uniform; cw >= 5: the slots with separate ncc / geom fields are all inside)
+			if (!sweep_slot_read(cw, pd, ALL)) continue;      // (compile time at the default window)
 #if defined(DVP_SWEEP_FOLD_BRANCHY)
 			if ((live >> i) & 1)
 #endif
@@ -2016,7 +2026,7 @@ DVP_HD void sweep_decide2_cw(const Dev& d, int px, int py) {
 #pragma unroll
 		for (int i = 0; i < 61; ++i) {
 			const int pd = i - 30;
-			if (pd >= -cw && pd <= cw) continue;
+			if ((pd >= -cw && pd <= cw) || !sweep_slot_read(cw, pd, ALL)) continue;
 			const float tc = 0.0f + cst[i];
 			const float t = p_costs[i] + tc * w;
 			p_costs[i] = ((live >> i) & 1) ? t : p_costs[i];
@@ -2025,6 +2035,7 @@ DVP_HD void sweep_decide2_cw(const Dev& d, int px, int py) {
 #pragma unroll
 	for (int i = 0; i < 61; ++i) {
 		const int pd = i - 30;
+		if (!sweep_slot_read(cw, pd, ALL)) { p_costs[i] = 2.0f; continue; }
 		if (pd >= -cw && pd <= cw) { p_costs[i] = d.sweep_pc[(size_t)i * L + center]; continue; }
 		float q = p_costs[i] / weight_normal;
 		q = DVP_MIN(2.0f, q);
@@ -2041,7 +2052,8 @@ DVP_HD void sweep_decide2_cw(const Dev& d, int px, int py) {
 			if (p_costs[i] < min_cost) { min_peak = i; min_cost = p_costs[i]; }
 		}
 	}
-	// p_costs[min_peak] == min_cost whenever a peak below 2 exists; otherwise min_peak = 0 and the line's first entry is read
+	// p_costs[min_peak] == min_cost whenever a peak below 2 exists; otherwise min_peak = 0 and the line's first entry is read — which
+	// cannot happen here (SWF_PEAK: the central peak <= 0.5 is a peak of this search too), so that entry may be the constant
 	const float at_min = (min_peak == 0) ? p_costs[0] : min_cost;
 	const int dpk = min_peak - 30;
 	uint8_t state;
@@ -2063,8 +2075,11 @@ DVP_HD void sweep_decide2_cw(const Dev& d, int px, int py) {
 	d.weak_info[center] = state;
 }
 DVP_HD void sweep_decide2_px(const Dev& d, int px, int py) {
-	if (sweep_window(d.params) == 5) sweep_decide2_cw<5>(d, px, py);
-	else sweep_decide2_cw<0>(d, px, py);
+	if (d.sweep_all_slots) {
+		if (sweep_window(d.params) == 5) sweep_decide2_cw<5, true>(d, px, py);
+		else sweep_decide2_cw<0, true>(d, px, py);
+	} else if (sweep_window(d.params) == 5) sweep_decide2_cw<5, false>(d, px, py);
+	else sweep_decide2_cw<0, false>(d, px, py);
 }
 
 }  // namespace dvp

@@ -147,7 +147,7 @@ struct Dev {
 	PlaneKey* reuse_keys;      // [L][17 places]: the plane whose vector a place holds
 	ReuseHdr* reuse_hdr;       // [L]
 	uint32_t reuse_epoch;      // a record written under another epoch is empty (the engine bumps it whenever a vector's inputs can change)
-	// DepthToWeak + LocalRefine as view-compacted passes (dvp_strong.hpp: sweep_*), or null (the fused per-pixel kernel)
+	// DepthToWeak + LocalRefine as view-compacted passes (dvp_sweep.hpp: sweep_*), or null (the fused per-pixel kernel)
 	f4* sweep_rec;             // [2][L]: (camera-frame normal, depth) and (mean baseline, disparity, weight sum, flags) per pixel
 	float* sweep_cost;         // [L/64][S][kSweepFields][64] (sweep_cost_index): per (view, sweep slot, pixel) costs written by dvp_sweep_eval
 	float* sweep_pc;           // [61][L]: the folded cost line of the central window, handed from the first decision pass to the second

@@ -1,1342 +1,25 @@
-// dvp_engine.hip — gfx950 kernels + the C ABI of include/dvp_mvs.h.
+// dvp_engine.hip — the gfx950 PatchMatch engine: the C ABI of include/dvp_mvs.h and the launch functions.
 //
 // Replaces APD::CudaSpaceInitialization / SetDataPassHelperInCuda / RunPatchMatch
 // (/root/reference/APD.cpp:1497-1613, 1670-1704; APD.cu:4406-4532).  One context owns one HIP
 // stream and every device buffer of one reference view; launches are queued back to back on that
 // stream (the reference calls cudaDeviceSynchronize after each of its 16+5*iters launches).
-#include "dvp_stages.hpp"
-#include "dvp_jpeg_enc.h"
-#include "dvp_edges_run.h"
-#include "dvp_viewclean_run.h"
-#include "dvp_prior_run.h"
+//
+// This file is the C ABI and the launch functions.  It includes
+//   dvp_kernels.hpp   LaunchArgs / ListArgs, the launch-bound defaults and every __global__ entry point
+//   dvp_ctx.hpp       struct dvp_ctx, HIP_TRY and the context's arena (dalloc, dfree, alloc_group_or_fall_back)
+//   dvp_probe.inc     the DVP_PROBE micro-benchmark, kernels and host entry (experiment builds only)
+#include "dvp_kernels.hpp"
+#include "dvp_ctx.hpp"
+#ifdef DVP_PROBE
+#include "dvp_probe.inc"
+#endif
 #include "dvp_pyramid_run.h"
-#include <hip/hip_runtime.h>
-#include <cstdlib>
-#include <string>
-#include <vector>
-#include <cstdio>
 #include <cstring>
-#include <mutex>
-#include <condition_variable>
 #include <thread>
 #include <chrono>
 #include <algorithm>
 #include <cmath>
-
-using namespace dvp;
-
-// ------------------------------------------------------------------------------------------------
-// kernels
-// ------------------------------------------------------------------------------------------------
-struct LaunchArgs {
-	int tiles_x, tiles, rows, half, colour, iter;
-};
-
-template <int STAGE, int SMP, int MV = 32>
-__device__ __forceinline__ void stage_body(const Dev& d, const LaunchArgs& a) {
-	const int lane = threadIdx.x & 63;
-	const int wave = threadIdx.x >> 6;
-	int px, py;
-	unsigned long long n = 0;
-	// per-lane (w, w*ref) table of the hoisted patch context: [tap][lane] in LDS (72 KiB / workgroup)
-	__shared__ f2 lds_tab[stage_uses_tab(STAGE) ? kTaps * kTaps * 256 : 1];
-	const PatchTab tab{&lds_tab[stage_uses_tab(STAGE) ? threadIdx.x : 0], 256};
-	if (block_to_pixel(blockIdx.x, lane, wave, a.tiles_x, a.tiles, a.rows, a.half, a.colour, d.width, d.height, &px, &py))
-		run_pixel<STAGE, SMP, MV>(d, px, py, a.iter, d.eval_counter ? &n : nullptr, tab);
-	if (d.eval_counter && n) atomicAdd(d.eval_counter, n);
-}
-
-// Compacted launch for the weak-pixel path: lane t owns the t-th WEAK pixel of the list segment.
-// WEAK pixels are 1-30 % of a view; a lane-per-image-pixel launch leaves 70-99 % of the lanes idle.
-struct ListArgs { int base, count, iter, covered_rows, group, run; };   // group: pixels per wave of the weak update's evaluation launches
-// XCD-aware block -> list-block map.  Workgroup b runs on XCD b % 8 (observed placement, a speed matter
-// only); the list is in super-tile order, so giving every XCD RUNS of kListRun consecutive list blocks
-// (instead of every 8th block) keeps the workgroups that share anchors — and the source-image lines
-// their anchor sub-patches gather — behind one L2.  Bijection on [0, nblocks): whole groups of
-// 8 * kListRun blocks are permuted, the ragged tail keeps its order.
-#ifndef DVP_LIST_RUN
-#define DVP_LIST_RUN 16
-#endif
-constexpr int kListRun = DVP_LIST_RUN;
-// The wave-per-pixel kernels (workgroup = 4 WEAK pixels) use shorter runs: 1 .. 64 blocks measure the same (weak update 400-402 ms
-// per cfg3 pass), 256 blocks 405, the 1 024 of round 2 (the lane kernels' run in pixels) 419 — a run longer than what an XCD has
-// in flight only delays the neighbours.
-#ifndef DVP_WAVE_RUN
-#define DVP_WAVE_RUN 16
-#endif
-constexpr int kWaveRun = DVP_WAVE_RUN;
-__device__ __forceinline__ int list_block(int b, int nblocks, int run) {
-	const int group = 8 * run;
-	if (b >= nblocks / group * group) return b;
-	const int g = b / group, r = b - g * group;
-	const int xcd = r & 7, i = r >> 3;
-	return g * group + xcd * run + i;
-}
-template <int STAGE, int SMP, int MV = 32>
-__device__ __forceinline__ void stage_body_list(const Dev& d, const ListArgs& a) {
-	__shared__ f2 lds_tab[stage_uses_tab(STAGE) ? kTaps * kTaps * 256 : 1];
-	const PatchTab tab{&lds_tab[stage_uses_tab(STAGE) ? threadIdx.x : 0], 256};
-	const int t = list_block(blockIdx.x, gridDim.x, kListRun) * 256 + threadIdx.x;
-	unsigned long long n = 0;
-	if (t < a.count) {
-		const int center = d.weak_list[a.base + t];
-		const int py = center / d.width, px = center - py * d.width;
-		// red/black launches never reach rows beyond the reference's half grid (APD.cu:4421-4424)
-		if (!stage_is_half_c(STAGE) || py < a.covered_rows)
-			run_pixel<STAGE, SMP, MV>(d, px, py, a.iter, d.eval_counter ? &n : nullptr, tab);
-	}
-	if (d.eval_counter && n) atomicAdd(d.eval_counter, n);
-}
-// The same launch sites with ONE wave per workgroup (18 KB of LDS each): tile t = the workgroups b with
-// (b >> 5) * 8 + (b & 7) == t, its row (b >> 3) & 3 — the four rows of a tile stay on the XCD block_to_pixel's map gives the tile.
-// No wave waits for the slowest of its workgroup before the LDS is given back: the strong update's evaluation and refinement
-// kernels gain 11 ms per cfg3 pass (DepthToWeak nothing: stays on 256-lane workgroups).
-template <int STAGE, int SMP, int MV = 32>
-__device__ __forceinline__ void stage_body64(const Dev& d, const LaunchArgs& a) {
-	const int lane = threadIdx.x;
-	const int b = blockIdx.x;
-	const int tile = (b >> 5) * 8 + (b & 7), wave = (b >> 3) & 3;
-	int px, py;
-	unsigned long long n = 0;
-	__shared__ f2 lds_tab[kTaps * kTaps * 64];
-	const PatchTab tab{&lds_tab[lane], 64};
-	if (block_to_pixel(tile, lane, wave, a.tiles_x, a.tiles, a.rows, a.half, a.colour, d.width, d.height, &px, &py))
-		run_pixel<STAGE, SMP, MV>(d, px, py, a.iter, d.eval_counter ? &n : nullptr, tab);
-	if (d.eval_counter && n) atomicAdd(d.eval_counter, n);
-}
-#define DVP_KERNEL64(NAME, STAGE, MINW)                                                                    \
-	extern "C" __global__ void __launch_bounds__(64, MINW) NAME(const Dev d, const LaunchArgs a) {          \
-		stage_body64<STAGE, 0>(d, a);                                                                       \
-	}                                                                                                       \
-	extern "C" __global__ void __launch_bounds__(64, MINW) NAME##_exact(const Dev d, const LaunchArgs a) {  \
-		stage_body64<STAGE, 1>(d, a);                                                                       \
-	}
-#define DVP_KERNEL_LIST_MV(NAME, STAGE, MINW, MV)                                                         \
-	extern "C" __global__ void __launch_bounds__(256, MINW) NAME(const Dev d, const ListArgs a) {         \
-		stage_body_list<STAGE, 0, MV>(d, a);                                                               \
-	}                                                                                                      \
-	extern "C" __global__ void __launch_bounds__(256, MINW) NAME##_exact(const Dev d, const ListArgs a) { \
-		stage_body_list<STAGE, 1, MV>(d, a);                                                               \
-	}
-#define DVP_KERNEL_LIST(NAME, STAGE, MINW)                                                                \
-	extern "C" __global__ void __launch_bounds__(256, MINW) NAME(const Dev d, const ListArgs a) {         \
-		stage_body_list<STAGE, 0>(d, a);                                                                   \
-	}                                                                                                      \
-	extern "C" __global__ void __launch_bounds__(256, MINW) NAME##_exact(const Dev d, const ListArgs a) { \
-		stage_body_list<STAGE, 1>(d, a);                                                                   \
-	}
-
-// One named kernel per launch site so that rocprofv3 --kernel-trace shows the reference's names.
-// NAME: sampler 0 (8-bit interpolation weights, default); NAME_exact: sampler 1.
-#define DVP_KERNEL(NAME, STAGE, MINW)                                                                      \
-	extern "C" __global__ void __launch_bounds__(256, MINW) NAME(const Dev d, const LaunchArgs a) {         \
-		stage_body<STAGE, 0>(d, a);                                                                         \
-	}                                                                                                       \
-	extern "C" __global__ void __launch_bounds__(256, MINW) NAME##_exact(const Dev d, const LaunchArgs a) { \
-		stage_body<STAGE, 1>(d, a);                                                                         \
-	}
-
-// same launch site, private per-view arrays sized for MV views (strong update with S <= 8)
-#define DVP_KERNEL_MV(NAME, STAGE, MINW, MV)                                                               \
-	extern "C" __global__ void __launch_bounds__(256, MINW) NAME(const Dev d, const LaunchArgs a) {         \
-		stage_body<STAGE, 0, MV>(d, a);                                                                     \
-	}                                                                                                       \
-	extern "C" __global__ void __launch_bounds__(256, MINW) NAME##_exact(const Dev d, const LaunchArgs a) { \
-		stage_body<STAGE, 1, MV>(d, a);                                                                     \
-	}
-
-DVP_KERNEL(dvp_gen_edge_inform, DVP_ST_GEN_EDGE_INFORM, 1)
-#ifndef DVP_LB_HEAVY
-// min waves/SIMD the NCC kernels are compiled for: 2 = 256 VGPRs per lane (the pipelined 36-tap
-// evaluation keeps 12 sixteen-byte gathers + the next 12 footprints live) and two 72 KiB patch
-// tables per CU in LDS.
-#define DVP_LB_HEAVY 2
-#endif
-DVP_KERNEL(dvp_random_init, DVP_ST_RANDOM_INIT, DVP_LB_HEAVY)
-DVP_KERNEL(dvp_strong_update, DVP_ST_STRONG_UPDATE, DVP_LB_HEAVY)
-DVP_KERNEL_MV(dvp_strong_update_v8, DVP_ST_STRONG_UPDATE, DVP_LB_HEAVY, kNarrowViews)
-DVP_KERNEL_MV(dvp_strong_update_v16, DVP_ST_STRONG_UPDATE, DVP_LB_HEAVY, 16)
-// split strong update (dvp_strong.hpp): evaluations of the 17 snapshot planes, decisions, refinement (S <= 16; S <= 31 with DVP_STRONG_WIDE)
-DVP_KERNEL64(dvp_strong_eval, kStageStrongEval, DVP_LB_HEAVY)
-// dvp_strong_eval with the (pixel, slot) items of the wave's 64 pixels compacted over its lanes.  With a pixel per lane a
-// wave makes 17 trips x S views whatever its lanes hold: WEAK and off-image lanes idle, edge pixels have 9 slots instead of
-// 17, and 11 % of the remaining planes are bitwise repeats of an earlier slot (strong_slot_sources) — 18 % of the lane-trips
-// at cfg3.  Here every lane first builds its pixel's patch table (LDS, [tap][pixel]) and lists its distinct slots; the
-// items are then numbered across the wave (prefix sum of the counts) and taken 64 per round: lane l evaluates item
-// round * 64 + l = (pixel p, slot s) against the S views with p's table column and p's reference sums (fetched from the
-// owner lane by ds_bpermute).  Same evaluations as strong_eval_px, hence the same bits.  LDS: 18 KB table + 1088 B of item
-// list = 8 workgroups per CU, as before.
-template <int SMP>
-__device__ __forceinline__ void strong_eval_items_body(const Dev& d, const LaunchArgs& a) {
-	const int lane = threadIdx.x;
-	const int b = blockIdx.x;
-	const int tile = (b >> 5) * 8 + (b & 7), wave = (b >> 3) & 3;
-	__shared__ f2 lds_tab[kTaps * kTaps * 64];
-	__shared__ uint8_t items[64 * kSlotCount];
-	int px = 0, py = 0;
-	bool active = block_to_pixel(tile, lane, wave, a.tiles_x, a.tiles, a.rows, a.half, a.colour, d.width, d.height, &px, &py);
-	if (active && d.weak_info[px + py * d.width] == DVP_WEAK) active = false;
-	PatchCtx c;
-	c.tab = PatchTab{&lds_tab[lane], 64};
-	c.sum_ref = c.sum_ref_ref = c.wsum = 0.0f;
-	c.radius = c.inc = c.fast = 0;
-	uint32_t uniq = 0;
-	if (active) {
-		const int center = px + py * d.width;
-		int radius, inc;
-		patch_geometry(d, center, &radius, &inc);
-		build_patch_ctx(d, px, py, radius, inc, 0, c.tab, &c);
-		if (d.reuse_hdr) uniq = d.reuse_hdr[center].eval;   // dvp_strong_plan has listed the slots and written their places
-		else {
-			uint32_t src[3], w[3];
-			uniq = strong_slot_sources(d, center, src);
-			strong_source_places(src, w);
-			const size_t Lh = (size_t)d.half_w * (size_t)d.height;
-			uint32_t* dup = reinterpret_cast<uint32_t*>(d.strong_rec) + half_index(d, px, py);
-			dup[SR_DUP * Lh] = w[0]; dup[(SR_DUP + 1) * Lh] = w[1]; dup[(SR_DUP + 2) * Lh] = w[2];
-		}
-	}
-	// Item order: pixel-major — all distinct slots of pixel 0, then pixel 1, ...; exclusive prefix sum of the lanes' item
-	// counts.  (Rank-major — the first distinct slot of every pixel, then the second, ... — keeps neighbouring pixels with the
-	// same direction's sample side by side like the pixel-per-lane kernel: L2 hit rate of the launch site 0.58 -> 0.84 and 65
-	// -> 48 B of fabric traffic per evaluation, but the same time at cfg3 (467 vs 466 ms) and 3.8 % more at cfg2 (148 vs 143
-	// ms): the kernel issues VALU instructions, it does not wait for lines, and the lanes of one pixel share its table column.)
-	const int n = __popc(uniq);
-	int incl = n;
-#pragma unroll
-	for (int o = 1; o < 64; o <<= 1) {
-		const int t = __shfl_up(incl, o, 64);
-		if (lane >= o) incl += t;
-	}
-	const int off = incl - n;
-	const int total = __shfl(incl, 63, 64);
-	{
-		int k = 0;
-		for (uint32_t m = uniq; m; m &= m - 1, ++k) items[off + k] = (uint8_t)lane;
-	}
-	__syncthreads();
-	unsigned long long cnt = 0;
-	for (int i0 = 0; i0 < total; i0 += 64) {
-		const bool valid = i0 + lane < total;
-		const int i = valid ? i0 + lane : total - 1;   // the tail of the last round repeats its last item without storing
-		const int pl = items[i];
-		const int k = i - __shfl(off, pl, 64);
-		uint32_t m = (uint32_t)__shfl((int)uniq, pl, 64);
-		for (int j = 0; j < k; ++j) m &= m - 1;
-		const int slot = dvp_ctz(m);
-		PatchCtx ci;
-		ci.tab = PatchTab{&lds_tab[pl], 64};
-		ci.sum_ref = __shfl(c.sum_ref, pl, 64);
-		ci.sum_ref_ref = __shfl(c.sum_ref_ref, pl, 64);
-		ci.wsum = __shfl(c.wsum, pl, 64);
-		ci.radius = __shfl(c.radius, pl, 64);
-		ci.inc = __shfl(c.inc, pl, 64);
-		ci.fast = __shfl(c.fast, pl, 64);
-		const int ipx = __shfl(px, pl, 64), ipy = __shfl(py, pl, 64);
-		strong_eval_item<SMP>(d, ci, ipx, ipy, slot, valid, d.eval_counter ? &cnt : nullptr);
-	}
-	if (d.eval_counter && cnt) atomicAdd(d.eval_counter, cnt);
-}
-extern "C" __global__ void __launch_bounds__(64, DVP_LB_HEAVY) dvp_strong_eval_items(const Dev d, const LaunchArgs a) { strong_eval_items_body<0>(d, a); }
-extern "C" __global__ void __launch_bounds__(64, DVP_LB_HEAVY) dvp_strong_eval_items_exact(const Dev d, const LaunchArgs a) { strong_eval_items_body<1>(d, a); }
-DVP_KERNEL64(dvp_strong_refine, kStageStrongRefine, DVP_LB_HEAVY)
-DVP_KERNEL64(dvp_strong_refine_lanes, kStageStrongRefineLanes, DVP_LB_HEAVY)
-template <int MV>
-__device__ __forceinline__ void strong_decide_body(const Dev& d, const LaunchArgs& a) {
-	int px, py;
-	if (!block_to_pixel(blockIdx.x, threadIdx.x & 63, threadIdx.x >> 6, a.tiles_x, a.tiles, a.rows, a.half, a.colour, d.width, d.height, &px, &py)) return;
-	if (d.weak_info[px + py * d.width] != DVP_WEAK) strong_decide_px<MV>(d, px, py, a.iter);
-}
-// the cost vectors of the 8 directions live in registers: one instantiation per view-count bracket
-// (4 waves per SIMD: the kernel waits for its cost loads 70 % of the time; 128 VGPRs cost the v10 instantiation 20 spilled registers and
-// win 1.7 ms of 10 per cfg3 launch; 5 waves the same, 6 less)
-#ifndef DVP_LB_DECIDE
-#define DVP_LB_DECIDE 4
-#endif
-#define DVP_DECIDE_KERNEL(MV) extern "C" __global__ void __launch_bounds__(256, DVP_LB_DECIDE) dvp_strong_decide_v##MV(const Dev d, const LaunchArgs a) { strong_decide_body<MV>(d, a); }
-// (Round 6 built the same decisions with the wave's 64 cost records staged in LDS by coalesced loads — 39 KB per wave at S = 9, i.e.
-// four waves per CU: 17.8 ms per cfg3 launch against 8.0 for the plain loads below on the pixel-major records; removed,
-// profiles/r06_ab_notes.txt.)
-DVP_DECIDE_KERNEL(4)
-DVP_DECIDE_KERNEL(6)
-DVP_DECIDE_KERNEL(8)
-DVP_DECIDE_KERNEL(10)
-DVP_DECIDE_KERNEL(12)
-DVP_DECIDE_KERNEL(16)
-// any S <= 31 (DVP_STRONG_WIDE): the vectors are streamed in 16-byte pieces instead of held (strong_decide_wide_px)
-extern "C" __global__ void __launch_bounds__(256, DVP_LB_DECIDE) dvp_strong_decide_wide(const Dev d, const LaunchArgs a) {
-	int px, py;
-	if (!block_to_pixel(blockIdx.x, threadIdx.x & 63, threadIdx.x >> 6, a.tiles_x, a.tiles, a.rows, a.half, a.colour, d.width, d.height, &px, &py)) return;
-	if (d.weak_info[px + py * d.width] != DVP_WEAK) strong_decide_wide_px(d, px, py, a.iter);
-}
-DVP_KERNEL(dvp_get_depth_normal, DVP_ST_GET_DEPTH_NORMAL, 1)
-DVP_KERNEL(dvp_filter_strong, DVP_ST_FILTER_STRONG, 1)
-DVP_KERNEL(dvp_depth_to_weak, DVP_ST_DEPTH_TO_WEAK, DVP_LB_HEAVY)
-DVP_KERNEL(dvp_local_refine, DVP_ST_LOCAL_REFINE, DVP_LB_HEAVY)
-DVP_KERNEL(dvp_depth_to_weak_refine, kStageSweeps, DVP_LB_HEAVY)   // the two sweeps in one launch (dvp_run_patchmatch)
-// ... and the same launch site as view-compacted passes (dvp_strong.hpp: sweep_*)
-template <int WHAT>
-__device__ __forceinline__ void sweep_light_body(const Dev& d, const LaunchArgs& a) {
-	int px, py;
-	if (!block_to_pixel(blockIdx.x, threadIdx.x & 63, threadIdx.x >> 6, a.tiles_x, a.tiles, a.rows, 0, 0, d.width, d.height, &px, &py)) return;
-	if (WHAT != 0 && d.sweep_row1 > 0 && (py < d.sweep_row0 || py >= d.sweep_row1)) return;   // a band's decision pass
-	if (WHAT == 0) sweep_prepare_px(d, px, py);
-	else if (WHAT == 1) sweep_decide1_px(d, px, py);
-	else sweep_decide2_px(d, px, py);
-}
-extern "C" __global__ void __launch_bounds__(256) dvp_sweep_prepare(const Dev d, const LaunchArgs a) { sweep_light_body<0>(d, a); }
-extern "C" __global__ void __launch_bounds__(256) dvp_sweep_decide1(const Dev d, const LaunchArgs a) { sweep_light_body<1>(d, a); }
-extern "C" __global__ void __launch_bounds__(256) dvp_sweep_decide2(const Dev d, const LaunchArgs a) { sweep_light_body<2>(d, a); }
-// Evaluation pass: workgroup = one wave = one 64 x 4 tile of the launch map, grid.y = source view (dispatched view after view:
-// the workgroups in flight gather from ONE image).  The tile's pixels that take part — they selected the view with a weight
-// > 0 — are compacted into a list in LDS (ballot ranks, row after row) and taken 64 per round, so that every lane of a round
-// evaluates (71 % of the pixels select a given view at cfg3: 2.8 rounds of 64 instead of 4 rows with 29 % of the lanes idle).
-// a.iter = stage (0: central window + LocalRefine's extra slot, 1: the rest of the line for pixels with a central peak).
-// (a tile is 64 x kSweepRows pixels: dvp_forms.hpp)
-template <int SMP, bool ALL>
-__device__ __forceinline__ void sweep_eval_body(const Dev& d, const LaunchArgs& a) {
-	const int lane = threadIdx.x;
-	const int v = blockIdx.y;
-	__shared__ f2 lds_tab[kTaps * kTaps * 64];
-	__shared__ uint16_t list[64 * kSweepRows];   // tile-local pixel index (row * 64 + x): 18 KB + 2 KB = 8 workgroups per CU
-	__shared__ DvpCamera cams[2];                // reference camera, camera of the launch's view
-	const PatchTab tab{&lds_tab[lane], 64};
-	static_assert(sizeof(DvpCamera) == 112, "28 dwords");
-	if (lane < 56) {
-		const int which = lane >= 28 ? 1 : 0;
-		reinterpret_cast<uint32_t*>(&cams[which])[lane - 28 * which] = reinterpret_cast<const uint32_t*>(d.cameras + (which ? v + 1 : 0))[lane - 28 * which];
-	}
-	// tile of this workgroup: the strip map of block_to_pixel (XCD b % 8 owns a column of a strip of 8 tile columns) over
-	// tiles of kSweepRows rows; a.tiles_x / a.tiles = that grid
-	const int tiles_y = a.tiles / a.tiles_x;
-	int tx, ty;
-	{
-		const int per_strip = 8 * tiles_y;
-		const int st = (int)blockIdx.x / per_strip, rem = (int)blockIdx.x - st * per_strip;
-		const int w_last = a.tiles_x - st * 8;
-		if (w_last >= 8) { ty = rem >> 3; tx = st * 8 + (rem & 7); }
-		else { ty = rem / w_last; tx = st * 8 + (rem - ty * w_last); }
-	}
-	ty += a.rows;   // first tile row of the launch (a band of the image; 0: all of it)
-	const int x = tx * 64 + lane;
-	int n = 0;
-	for (int r = 0; r < kSweepRows; ++r) {
-		const int y = ty * kSweepRows + r;
-		const bool go = x < d.width && y < d.height && sweep_go(d, x + y * d.width, v, a.iter);
-		const unsigned long long m = __ballot(go);
-		if (go) list[n + __popcll(m & ((1ull << lane) - 1ull))] = (uint16_t)(r * 64 + lane);
-		n += __popcll(m);
-	}
-	__syncthreads();
-	unsigned long long cnt = 0;
-	for (int i0 = 0; i0 < n; i0 += 64) {
-		if (i0 + lane < n) {
-			const int e = list[i0 + lane];
-			sweep_eval_px<SMP, ALL>(d, tx * 64 + (e & 63), ty * kSweepRows + (e >> 6), v, a.iter, tab, d.eval_counter ? &cnt : nullptr, cams);
-		}
-	}
-	if (d.eval_counter && cnt) atomicAdd(d.eval_counter, cnt);
-}
-// The 6-pixel frame of the view-compacted form (UNKNOWN for DepthToWeak, a full LocalRefine: the fused kernel's per-pixel
-// code) over the frame's pixels only: lane t of the launch = the t-th frame pixel (6 rows on top, 6 at the bottom, 2 x 6
-// columns between them).  The full-grid launch kept 8 800 waves resident for 6 active lanes each at 6208 x 4128 (6.6 ms).
-template <int SMP>
-__device__ __forceinline__ void sweep_border_body(const Dev& d, const LaunchArgs& a) {
-	__shared__ f2 lds_tab[kTaps * kTaps * 64];
-	const PatchTab tab{&lds_tab[threadIdx.x], 64};
-	const int W = d.width, H = d.height;
-	const long long t = (long long)blockIdx.x * 64 + threadIdx.x;
-	int px, py;
-	if (t < 12ll * W) {
-		const int r = (int)(t / W);
-		px = (int)(t - (long long)r * W);
-		py = r < 6 ? r : H - 12 + r;
-	} else {
-		const long long u = t - 12ll * W;
-		const int r = (int)(u / 12), cidx = (int)(u - 12ll * r);
-		if (r >= H - 12) return;
-		py = 6 + r;
-		px = cidx < 6 ? cidx : W - 12 + cidx;
-	}
-	unsigned long long n = 0;
-	run_pixel<kStageSweeps, SMP>(d, px, py, kSweepBorderOnly, d.eval_counter ? &n : nullptr, tab);
-	if (d.eval_counter && n) atomicAdd(d.eval_counter, n);
-}
-extern "C" __global__ void __launch_bounds__(64, DVP_LB_HEAVY) dvp_sweep_border(const Dev d, const LaunchArgs a) { sweep_border_body<0>(d, a); }
-extern "C" __global__ void __launch_bounds__(64, DVP_LB_HEAVY) dvp_sweep_border_exact(const Dev d, const LaunchArgs a) { sweep_border_body<1>(d, a); }
-extern "C" __global__ void __launch_bounds__(64, DVP_LB_HEAVY) dvp_sweep_eval(const Dev d, const LaunchArgs a) { sweep_eval_body<0, false>(d, a); }
-extern "C" __global__ void __launch_bounds__(64, DVP_LB_HEAVY) dvp_sweep_eval_exact(const Dev d, const LaunchArgs a) { sweep_eval_body<1, false>(d, a); }
-// DVP_SWEEP_ALL_SLOTS=1 (A/B): the same with the two end slots of the line, which no decision reads (dvp_forms.hpp: sweep_slot_read)
-extern "C" __global__ void __launch_bounds__(64, DVP_LB_HEAVY) dvp_sweep_eval_all(const Dev d, const LaunchArgs a) { sweep_eval_body<0, true>(d, a); }
-extern "C" __global__ void __launch_bounds__(64, DVP_LB_HEAVY) dvp_sweep_eval_exact_all(const Dev d, const LaunchArgs a) { sweep_eval_body<1, true>(d, a); }
-
-// the weak-path launch sites: one lane per entry of the WEAK-pixel list
-DVP_KERNEL_LIST(dvp_find_nearest_strong_list, DVP_ST_FIND_NEAREST_STRONG, 1)
-// GenNeighbours' directional search: one lane per WEAK pixel, the list of found points in LDS (one column per lane)
-extern "C" __global__ void __launch_bounds__(256) dvp_gen_neighbours_list(const Dev d, const ListArgs a) {
-	__shared__ s2 pts[kGnDirSlots * 256];
-	const int t = list_block(blockIdx.x, gridDim.x, kListRun) * 256 + threadIdx.x;
-	if (t >= a.count) return;
-	const int center = d.weak_list[a.base + t];
-	const int py = center / d.width, px = center - py * d.width;
-	gen_neighbours_px(d, px, py, pts + threadIdx.x, 256);
-}
-DVP_KERNEL_LIST(dvp_neighbour_update_list, DVP_ST_NEIGHBOUR_UPDATE, 1)
-DVP_KERNEL_LIST(dvp_ransac_fit_plane_list, DVP_ST_RANSAC_FIT, 1)
-// ... and the same launch site with one wave per WEAK pixel, lane = draw (dvp_ransac.hpp: ransac_fit_plane_wave; DVP_RANSAC_WAVE=1 —
-// measured no faster than the lane kernel, whose 0.18 lane utilisation turns out not to be what it waits for: kept as the record of that)
-extern "C" __global__ void __launch_bounds__(64) dvp_ransac_fit_plane_wave(const Dev d, const ListArgs a) {
-	__shared__ RansacShared sh[1];
-	const int t = list_block(blockIdx.x, gridDim.x, kWaveRun * 4);
-	if (t >= a.count) return;
-	const int center = d.weak_list[a.base + t];
-	const int py = center / d.width, px = center - py * d.width;
-	ransac_fit_plane_wave(d, px, py, a.iter, sh[0]);
-}
-
-// Black/RedPixelUpdateWeak (APD.cu:4487-4489): one WAVE per WEAK pixel of the list segment, per-pixel state in LDS
-// (dvp_weak_wave.hpp)
-template <int SMP, int FMT, int TAB>
-__device__ __forceinline__ void weak_wave_body(const Dev& d, const ListArgs& a) {
-	// one wave = one WEAK pixel = one workgroup (10 KB of LDS): with four pixels per workgroup the LDS of a finished pixel waited
-	// for the slowest of the four (weak update 400 -> 376 ms per cfg3 pass); the XCD runs keep their length in pixels
-	__shared__ WeakSharedT<TAB> sh[1];
-	const int wave = 0;
-	const int t = list_block(blockIdx.x, gridDim.x, kWaveRun * 4);
-	if (t >= a.count) return;
-	const int center = d.weak_list[a.base + t];
-	const int py = center / d.width, px = center - py * d.width;
-	if (py >= a.covered_rows) return;   // rows beyond the reference's half grid (APD.cu:4421-4424)
-	if (d.weak_info[center] != DVP_WEAK) return;   // NeigbourUpdate turned it UNKNOWN since the list was built (APD.cu:3119-3123)
-	unsigned long long n = 0;
-	weak_update_wave<SMP, FMT, TAB>(d, px, py, a.iter, d.eval_counter ? &n : nullptr, sh[wave]);
-	if (d.eval_counter && n) atomicAdd(d.eval_counter, n);
-}
-// first half of GenNeighbours (directional anchor search + label extension): one wave per WEAK pixel, the tries of a
-// direction over the lanes (dvp_neighbours.hpp: gen_neighbours_search_wave)
-#ifndef DVP_LB_GN
-#define DVP_LB_GN 8   // waves per SIMD (64 VGPRs + 164 B scratch; measured 86 ms per cfg3 pass, 4 waves without scratch: 105 ms)
-#endif
-extern "C" __global__ void __launch_bounds__(256, DVP_LB_GN) dvp_gen_neighbours_search(const Dev d, const ListArgs a) {
-	__shared__ GnShared sh[4];
-	const int wave = threadIdx.x >> 6;
-	const int t = list_block(blockIdx.x, gridDim.x, kWaveRun) * 4 + wave;
-	if (t >= a.count) return;
-	const int center = d.weak_list[a.base + t];
-	if (d.weak_info[center] != DVP_WEAK) return;
-	const int py = center / d.width, px = center - py * d.width;
-	gen_neighbours_search_wave(d, px, py, sh[wave]);
-}
-// second half of GenNeighbours (RANSAC plane + ranking): one wave per WEAK pixel, point tables in LDS
-// (3 workgroups per CU is what the 12.6 KB of LDS per wave allow; stated, the compiler fits the kernel in 108 VGPRs, left alone it takes 179: 2 waves per SIMD)
-extern "C" __global__ void __launch_bounds__(64, 3) dvp_gen_neighbours_fit(const Dev d, const ListArgs a) {
-	__shared__ FitShared sh[1];   // (one wave per workgroup, as the weak update: 65 -> 59 ms per cfg3 launch)
-	const int wave = 0;
-	const int t = list_block(blockIdx.x, gridDim.x, kWaveRun * 4);
-	if (t >= a.count) return;
-	const int center = d.weak_list[a.base + t];
-	if (d.weak_info[center] != DVP_WEAK) return;
-	const int py = center / d.width, px = center - py * d.width;
-	gen_neighbours_fit_wave(d, px, py, sh[wave]);
-}
-
-#ifndef DVP_LB_WEAK
-#define DVP_LB_WEAK 4   // waves per SIMD the wave kernel is compiled for (LDS: 34 KB per workgroup -> 4 workgroups per CU; 128 VGPRs)
-#endif
-// (no suffix: the anchor sub-patches' reference side comes from the pass' table, Dev::anchor_tab; _notab: formed per item —
-// the definition, used when the table does not fit or DVP_WEAK_ANCHOR_TAB=0)
-extern "C" __global__ void __launch_bounds__(64, DVP_LB_WEAK) dvp_weak_update_wave(const Dev d, const ListArgs a) { weak_wave_body<0, 0, 1>(d, a); }
-extern "C" __global__ void __launch_bounds__(64, DVP_LB_WEAK) dvp_weak_update_wave_exact(const Dev d, const ListArgs a) { weak_wave_body<1, 0, 1>(d, a); }
-extern "C" __global__ void __launch_bounds__(64, DVP_LB_WEAK) dvp_weak_update_wave_notab(const Dev d, const ListArgs a) { weak_wave_body<0, 0, 0>(d, a); }
-extern "C" __global__ void __launch_bounds__(64, DVP_LB_WEAK) dvp_weak_update_wave_exact_notab(const Dev d, const ListArgs a) { weak_wave_body<1, 0, 0>(d, a); }
-// the same launch site reading the byte planes (Dev::images8: all images 8-bit exact)
-extern "C" __global__ void __launch_bounds__(64, DVP_LB_WEAK) dvp_weak_update_wave_u8(const Dev d, const ListArgs a) { weak_wave_body<0, 1, 1>(d, a); }
-extern "C" __global__ void __launch_bounds__(64, DVP_LB_WEAK) dvp_weak_update_wave_exact_u8(const Dev d, const ListArgs a) { weak_wave_body<1, 1, 1>(d, a); }
-extern "C" __global__ void __launch_bounds__(64, DVP_LB_WEAK) dvp_weak_update_wave_u8_notab(const Dev d, const ListArgs a) { weak_wave_body<0, 1, 0>(d, a); }
-extern "C" __global__ void __launch_bounds__(64, DVP_LB_WEAK) dvp_weak_update_wave_exact_u8_notab(const Dev d, const ListArgs a) { weak_wave_body<1, 1, 0>(d, a); }
-// ... and the binary16 planes (Dev::images16: down-sampled levels of 8-bit images)
-extern "C" __global__ void __launch_bounds__(64, DVP_LB_WEAK) dvp_weak_update_wave_f16(const Dev d, const ListArgs a) { weak_wave_body<0, 2, 1>(d, a); }
-extern "C" __global__ void __launch_bounds__(64, DVP_LB_WEAK) dvp_weak_update_wave_exact_f16(const Dev d, const ListArgs a) { weak_wave_body<1, 2, 1>(d, a); }
-extern "C" __global__ void __launch_bounds__(64, DVP_LB_WEAK) dvp_weak_update_wave_f16_notab(const Dev d, const ListArgs a) { weak_wave_body<0, 2, 0>(d, a); }
-extern "C" __global__ void __launch_bounds__(64, DVP_LB_WEAK) dvp_weak_update_wave_exact_f16_notab(const Dev d, const ListArgs a) { weak_wave_body<1, 2, 0>(d, a); }
-// The same launch site as EIGHT launches (dvp_weak_phased.hpp): the evaluation launches E0 / E1 / E2a / E2b take one wave per
-// GROUP of a.group consecutive WEAK pixels of the list, the per-pixel decisions D1 / D2 / D3 and the final plain-NCC cost E3
-// run one LANE per WEAK pixel.
-template <int SMP, int FMT, int MODE>
-__device__ __forceinline__ void weak_group_body(const Dev& d, const ListArgs& a) {
-	constexpr int GRP = MODE == 0 ? kGrpWide : kGrp;
-	__shared__ WeakGroupSharedT<GRP> sh;
-	const int G = a.group < GRP ? a.group : GRP;
-	const int run = a.run / G;          // XCD runs of a.run pixels (the one-wave kernel's: kWaveRun * 4)
-	const int blk = list_block(blockIdx.x, gridDim.x, run < 1 ? 1 : run);
-	if (blk * G >= a.count) return;
-	if (threadIdx.x < (unsigned)GRP) {
-		const int t = blk * G + (int)threadIdx.x;
-		int center = -1;
-		if ((int)threadIdx.x < G && t < a.count) {
-			center = d.weak_list[a.base + t];
-			// rows beyond the reference's half grid (APD.cu:4421-4424); NeigbourUpdate turned it UNKNOWN since the list was built (APD.cu:3119-3123)
-			if (center / d.width >= a.covered_rows || d.weak_info[center] != DVP_WEAK) center = -1;
-		}
-		sh.center[threadIdx.x] = center;
-	}
-	wave_sync();
-	unsigned long long n = 0;
-	weak_group_eval<SMP, FMT, MODE, GRP>(d, G, d.eval_counter ? &n : nullptr, sh);
-	if (d.eval_counter && n) atomicAdd(d.eval_counter, n);
-}
-#define DVP_WEAK_PHASE_KERNELS(NAME, MODE)                                                                                                              \
-	extern "C" __global__ void __launch_bounds__(64, DVP_LB_WEAK) NAME(const Dev d, const ListArgs a) { weak_group_body<0, 0, MODE>(d, a); }           \
-	extern "C" __global__ void __launch_bounds__(64, DVP_LB_WEAK) NAME##_exact(const Dev d, const ListArgs a) { weak_group_body<1, 0, MODE>(d, a); }   \
-	extern "C" __global__ void __launch_bounds__(64, DVP_LB_WEAK) NAME##_u8(const Dev d, const ListArgs a) { weak_group_body<0, 1, MODE>(d, a); }      \
-	extern "C" __global__ void __launch_bounds__(64, DVP_LB_WEAK) NAME##_exact_u8(const Dev d, const ListArgs a) { weak_group_body<1, 1, MODE>(d, a); }    \
-	extern "C" __global__ void __launch_bounds__(64, DVP_LB_WEAK) NAME##_f16(const Dev d, const ListArgs a) { weak_group_body<0, 2, MODE>(d, a); }     \
-	extern "C" __global__ void __launch_bounds__(64, DVP_LB_WEAK) NAME##_exact_f16(const Dev d, const ListArgs a) { weak_group_body<1, 2, MODE>(d, a); }
-DVP_WEAK_PHASE_KERNELS(dvp_weak_eval_candidates, 0)
-DVP_WEAK_PHASE_KERNELS(dvp_weak_eval_planes, 1)
-DVP_WEAK_PHASE_KERNELS(dvp_weak_eval_first_view, 2)
-DVP_WEAK_PHASE_KERNELS(dvp_weak_eval_survivors, 3)
-template <int PART>
-__device__ __forceinline__ void weak_phase_lane_body(const Dev& d, const ListArgs& a) {
-	const int t = list_block(blockIdx.x, gridDim.x, kListRun) * 256 + threadIdx.x;
-	if (t >= a.count) return;
-	const int center = d.weak_list[a.base + t];
-	const int py = center / d.width, px = center - py * d.width;
-	if (py >= a.covered_rows) return;
-	if (d.weak_info[center] != DVP_WEAK) return;
-	if (PART == 0) weak_d1_px(d, px, py, a.iter);
-	else if (PART == 1) weak_d2_px(d, px, py, a.iter);
-	else weak_d3_px(d, px, py);
-}
-#ifndef DVP_LB_WEAK_DECIDE
-#define DVP_LB_WEAK_DECIDE 2   // 256-lane workgroups per SIMD... (waves per SIMD = this; the kernels wait for scattered loads)
-#endif
-extern "C" __global__ void __launch_bounds__(256, DVP_LB_WEAK_DECIDE) dvp_weak_select_views(const Dev d, const ListArgs a) { weak_phase_lane_body<0>(d, a); }
-extern "C" __global__ void __launch_bounds__(256, DVP_LB_WEAK_DECIDE) dvp_weak_make_hypotheses(const Dev d, const ListArgs a) { weak_phase_lane_body<1>(d, a); }
-extern "C" __global__ void __launch_bounds__(256, DVP_LB_WEAK_DECIDE) dvp_weak_adopt(const Dev d, const ListArgs a) { weak_phase_lane_body<2>(d, a); }
-// E3: the per-lane evaluator of the strong path over the WEAK list (one-wave workgroups, 18 KB of patch table each)
-template <int SMP>
-__device__ __forceinline__ void weak_final_cost_body(const Dev& d, const ListArgs& a) {
-	__shared__ f2 lds_tab[kTaps * kTaps * 64];
-	const PatchTab tab{&lds_tab[threadIdx.x], 64};
-	const int t = list_block(blockIdx.x, gridDim.x, kListRun * 4) * 64 + threadIdx.x;
-	if (t >= a.count) return;
-	const int center = d.weak_list[a.base + t];
-	const int py = center / d.width, px = center - py * d.width;
-	if (py >= a.covered_rows) return;
-	if (d.weak_info[center] != DVP_WEAK) return;
-	unsigned long long n = 0;
-	weak_final_cost_px<SMP>(d, px, py, tab, d.eval_counter ? &n : nullptr);
-	if (d.eval_counter && n) atomicAdd(d.eval_counter, n);
-}
-extern "C" __global__ void __launch_bounds__(64, 2) dvp_weak_final_cost(const Dev d, const ListArgs a) { weak_final_cost_body<0>(d, a); }
-extern "C" __global__ void __launch_bounds__(64, 2) dvp_weak_final_cost_exact(const Dev d, const ListArgs a) { weak_final_cost_body<1>(d, a); }
-
-// the pass' table of anchor reference sides: thread = (WEAK list entry, view, anchor), anchor fastest (neighbouring lanes write
-// neighbouring 128-byte records)
-extern "C" __global__ void __launch_bounds__(256) dvp_weak_anchor_table(const Dev d, const ListArgs a) {
-	const int S = d.params.num_images - 1;
-	const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-	if (i >= (long long)a.count * S * kAnchors) return;
-	const int k = (int)(i % kAnchors);
-	const long long r = i / kAnchors;
-	const int v0 = (int)(r % S);
-	const int t = (int)(r / S);
-	// (the records written through an LDS transpose — eight whole records per store instruction instead of 16 bytes into each of
-	// 64 lines — measure the same 19 ms per cfg3 pass: the launch does not wait for its stores)
-	if (d.images8) build_anchor_record<1>(d, d.weak_list[a.base + t], v0, k);
-	else if (d.images16) build_anchor_record<2>(d, d.weak_list[a.base + t], v0, k);
-	else build_anchor_record<0>(d, d.weak_list[a.base + t], v0, k);
-}
-
-// replicate the image border into the kImgPad-wide frame of a padded plane set
-extern "C" __global__ void dvp_pad_replicate(float* planes, int W, int H, int pitch, size_t plane_stride, int n_planes) {
-	const int PW = W + 2 * kImgPad, PH = H + 2 * kImgPad;
-	const int frame = 2 * kImgPad * PW + 2 * kImgPad * H;   // border cells per plane
-	const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-	if (t >= (long long)frame * n_planes) return;
-	const int pl = (int)(t / frame);
-	int k = (int)(t - (long long)pl * frame);
-	int x, y;
-	if (k < 2 * kImgPad * PW) {           // top and bottom bands
-		y = k / PW;
-		x = k - y * PW;
-		if (y >= kImgPad) y += H;
-	} else {                              // left and right bands of the interior rows
-		k -= 2 * kImgPad * PW;
-		y = kImgPad + k / (2 * kImgPad);
-		x = k % (2 * kImgPad);
-		if (x >= kImgPad) x += W;
-	}
-	float* p = planes + (size_t)pl * plane_stride;
-	const int sx = clampi(x - kImgPad, 0, W - 1) + kImgPad, sy = clampi(y - kImgPad, 0, H - 1) + kImgPad;
-	p[(size_t)y * pitch + x] = p[(size_t)sy * pitch + sx];
-}
-
-// plain padded planes -> row-pair planes: out[(y*pitch + x)*2 + {0,1}] = {in[y][x], in[y+1][x]}
-// (the last padded row pairs with itself; the sampler never reads its second component)
-extern "C" __global__ void dvp_interleave_rows(const float* __restrict__ in, float* __restrict__ out, int PH, int pitch, size_t plane_stride, int n_planes) {
-	const int x = blockIdx.x * blockDim.x + threadIdx.x;
-	const int y = blockIdx.y;
-	const int pl = blockIdx.z;
-	if (x >= pitch) return;
-	const float* p = in + (size_t)pl * plane_stride;
-	const int y1 = y + 1 < PH ? y + 1 : y;
-	const float2 v = make_float2(p[(size_t)y * pitch + x], p[(size_t)y1 * pitch + x]);
-	reinterpret_cast<float2*>(out + (size_t)pl * plane_stride * 2)[(size_t)y * pitch + x] = v;
-}
-
-// row-pair float planes -> tiled byte planes (Dev::images8), and the format probe of the upload: *inexact collects the bits of
-// tile_pair_rule (dvp_dev.hpp) over every element — bit 0: some texel is not an integer in [0, 255] (no byte planes), bit 1: some
-// texel is not a binary16 value in [0, 255] (no binary16 planes either).
-// One thread per tile element: tile (tx, ty), element (ex, ey) = padded pixel (tx*7 + ex, ty*8 + ey), clamped to the
-// padded plane (the right-most column of a tile repeats the first pixel of the next tile).
-extern "C" __global__ void dvp_pairs_to_tiles(const float* __restrict__ pairs, uint8_t* __restrict__ out, int PW, int PH, int pitch, size_t plane_stride,
-                                              int tiles_x, int tiles_y, int n_planes, int* inexact) {
-	const size_t per_plane = (size_t)tiles_x * tiles_y * 64;
-	const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-	if (i >= per_plane * n_planes) return;
-	const int pl = (int)(i / per_plane);
-	const size_t r = i - (size_t)pl * per_plane;
-	const int tile = (int)(r >> 6), e = (int)(r & 63);
-	const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
-	const int sx = min(tx * kT8W + (e % kT8E), PW - 1), sy = min(ty * kT8H + (e / kT8E), PH - 1);
-	if (e >= kT8E * kT8H) return;
-	const float* plane = pairs + (size_t)pl * plane_stride * 2;
-	const float2 v = reinterpret_cast<const float2*>(plane)[(size_t)sy * pitch + sx];
-	const float2 u = reinterpret_cast<const float2*>(plane)[(size_t)sy * pitch + min(sx + 1, PW - 1)];
-	uint32_t h;
-	const unsigned bad = tile_pair_rule(v.x, v.y, &h);
-	if (bad) {
-		if ((*inexact & bad) != bad) atomicOr(inexact, (int)bad);
-		if (bad & 1u) return;
-	}
-	uint8_t* dst = out + ((size_t)pl * tiles_x * tiles_y + tile) * 128 + (size_t)e * kT8B;
-	dst[0] = (uint8_t)v.x;
-	dst[1] = (uint8_t)v.y;
-	if (kT8Quad) { dst[2] = (uint8_t)u.x; dst[3] = (uint8_t)u.y; }
-}
-
-// row-pair float planes -> tiled binary16 planes (Dev::images16), after dvp_pairs_to_tiles found every texel binary16-exact.
-// One thread per tile element: tile (tx, ty), element (ex, ey) = padded pixel (tx*7 + ex, ty*4 + ey), clamped to the padded plane.
-extern "C" __global__ void dvp_pairs_to_tiles16(const float* __restrict__ pairs, uint32_t* __restrict__ out, int PW, int PH, int pitch, size_t plane_stride,
-                                                int tiles_x, int tiles_y, int n_planes) {
-	constexpr int kPer = kT16E * kT16H;   // 32 elements per tile
-	const size_t per_plane = (size_t)tiles_x * tiles_y * kPer;
-	const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-	if (i >= per_plane * n_planes) return;
-	const int pl = (int)(i / per_plane);
-	const size_t r = i - (size_t)pl * per_plane;
-	const int tile = (int)(r / kPer), e = (int)(r % kPer);
-	const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
-	const int sx = min(tx * kT16W + (e % kT16E), PW - 1), sy = min(ty * kT16H + (e / kT16E), PH - 1);
-	const float2 v = reinterpret_cast<const float2*>(pairs + (size_t)pl * plane_stride * 2)[(size_t)sy * pitch + sx];
-	uint32_t h;
-	(void)tile_pair_rule(v.x, v.y, &h);
-	out[((size_t)pl * tiles_x * tiles_y + tile) * (128 / 4) + e] = h;
-}
-
-// byte edge map -> 32x32 bit tiles (one thread per 32-bit word)
-extern "C" __global__ void dvp_pack_edge_bits(const uint8_t* __restrict__ edge, uint32_t* __restrict__ bits, int W, int H, int tiles_x, size_t words, int equals) {
-	const size_t w = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-	if (w < words) bits[w] = pack_edge_word(edge, W, H, tiles_x, w, equals);
-}
-
-// visibility-prior candidates of GenEdgeInform: pixels x source views (blockIdx.y = view, wave-uniform)
-extern "C" __global__ void __launch_bounds__(256) dvp_gen_candidates(const Dev d, const LaunchArgs a) {
-	int px, py;
-	if (block_to_pixel(blockIdx.x, threadIdx.x & 63, threadIdx.x >> 6, a.tiles_x, a.tiles, a.rows, 0, 0, d.width, d.height, &px, &py))
-		gen_candidates_px(d, px, py, (int)blockIdx.y);
-}
-
-// all views of a pixel by one lane (gen_candidates_views_px: the tap weights once instead of once per view)
-extern "C" __global__ void __launch_bounds__(256) dvp_gen_candidates_views(const Dev d, const LaunchArgs a) {
-	int px, py;
-	if (block_to_pixel(blockIdx.x, threadIdx.x & 63, threadIdx.x >> 6, a.tiles_x, a.tiles, a.rows, 0, 0, d.width, d.height, &px, &py))
-		gen_candidates_views_px<kCandGroup>(d, px, py, (int)blockIdx.y * kCandGroup);
-}
-extern "C" __global__ void __launch_bounds__(256) dvp_gen_candidates_views_list(const Dev d, const unsigned* list, const unsigned* n_list) {
-	const unsigned t = blockIdx.x * 256 + threadIdx.x;
-	if (t >= *n_list) return;
-	const int center = (int)list[t];
-	const int py = center / d.width, px = center - py * d.width;
-	gen_candidates_views_px<kCandGroup>(d, px, py, (int)blockIdx.y * kCandGroup);
-}
-
-// ... and the same for the ANCHOR pixels only (dvp_run_patchmatch).  The weak update is the records' one reader, and it reads
-// them at the anchors of WEAK pixels (make_anchor_record, wave_ncc_new: the anchor's eight offsets per view, APD.cu:938-952) —
-// after GenNeighbours that is a few percent of the image where the reference's GenEdgeInform fills every pixel x view (52 ms
-// of side-stream work at 6208x4128, S = 9).  Three launches: mark the anchors of the WEAK list, compact the marks into a
-// list (any order), one lane per (listed pixel, view).  They read the selected-view map as GenEdgeInform saw it (a snapshot
-// taken before RandomInitialization rewrites it), so the records are those of the full launch.
-extern "C" __global__ void __launch_bounds__(256) dvp_anchor_mask(const Dev d, const ListArgs a, uint8_t* mask) {
-	const int t = blockIdx.x * 256 + threadIdx.x;
-	if (t >= a.count) return;
-	const int center = d.weak_list[a.base + t];
-	const s2* nb = d.neighbours + (size_t)d.neighbours_map[center] * DVP_NEIGHBOUR_NUM;
-	for (int k = 1; k < DVP_NEIGHBOUR_NUM; ++k) {
-		const s2 q = nb[k];
-		if (q.x >= 0 && q.y >= 0 && q.x < d.width && q.y < d.height) mask[(size_t)q.y * d.width + q.x] = 1;
-	}
-}
-extern "C" __global__ void __launch_bounds__(256) dvp_mask_compact(const uint8_t* mask, size_t L, unsigned* list, unsigned* n_list) {
-	const size_t p = (size_t)blockIdx.x * 256 + threadIdx.x;
-	const bool go = p < L && mask[p] != 0;
-	const unsigned long long m = __ballot(go);
-	if (!m) return;
-	const int lane = threadIdx.x & 63;
-	unsigned base = 0;
-	if (lane == __builtin_ctzll(m)) base = atomicAdd(n_list, (unsigned)__popcll(m));
-	base = __shfl(base, __builtin_ctzll(m), 64);
-	if (go) list[base + __popcll(m & ((1ull << lane) - 1ull))] = (unsigned)p;
-}
-extern "C" __global__ void __launch_bounds__(256) dvp_gen_candidates_list(const Dev d, const unsigned* list, const unsigned* n_list) {
-	const unsigned t = blockIdx.x * 256 + threadIdx.x;
-	if (t >= *n_list) return;
-	const int center = (int)list[t];
-	const int py = center / d.width, px = center - py * d.width;
-	gen_candidates_px(d, px, py, (int)blockIdx.y);
-}
-
-extern "C" __global__ void dvp_pack_bits_transposed(const uint8_t* __restrict__ map, uint32_t* __restrict__ bits, int W, int H, int tiles_x, size_t words, int equals) {
-	const size_t w = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-	if (w < words) bits[w] = pack_edge_word_t(map, W, H, tiles_x, w, equals);
-}
-
-// cell table of the edge map (edge_count_upper): counts per 8x8 cell from the bit tiles, then the two prefix passes
-extern "C" __global__ void dvp_edge_cell_counts(const Dev d) {
-	const int c = blockIdx.x * blockDim.x + threadIdx.x;
-	if (c >= d.sat_cells_x * d.sat_cells_y) return;
-	const int cy = c / d.sat_cells_x, cx = c - cy * d.sat_cells_x;
-	int n = 0;
-	for (int r = 0; r < 8; ++r) {
-		const int y = cy * 8 + r;
-		if (y >= d.height) break;
-		const unsigned w = d.edge_bits[(size_t)(((y >> 5) * d.edge_tiles_x + (cx >> 2)) * 32 + (y & 31))];
-		n += __popc((w >> ((cx & 3) * 8)) & 255u);
-	}
-	d.edge_sat[(cy + 1) * (d.sat_cells_x + 1) + cx + 1] = n;
-}
-extern "C" __global__ void dvp_edge_sat_rows(const Dev d) {   // one thread per table row: running sum along x
-	const int r = blockIdx.x * blockDim.x + threadIdx.x;
-	if (r > d.sat_cells_y) return;
-	int* row = d.edge_sat + (size_t)r * (d.sat_cells_x + 1);
-	int acc = 0;
-	for (int x = 0; x <= d.sat_cells_x; ++x) { acc += (r == 0 || x == 0) ? 0 : row[x]; row[x] = acc; }
-}
-extern "C" __global__ void dvp_edge_sat_cols(const Dev d) {   // one thread per table column: running sum along y
-	const int x = blockIdx.x * blockDim.x + threadIdx.x;
-	if (x > d.sat_cells_x) return;
-	const int P = d.sat_cells_x + 1;
-	int acc = 0;
-	for (int r = 0; r <= d.sat_cells_y; ++r) { acc += d.edge_sat[(size_t)r * P + x]; d.edge_sat[(size_t)r * P + x] = acc; }
-}
-
-// sample search of the strong update (same red/black launch geometry, no LDS, small register footprint)
-extern "C" __global__ void __launch_bounds__(256) dvp_strong_search(const Dev d, const LaunchArgs a) {
-	int px, py;
-	if (block_to_pixel(blockIdx.x, threadIdx.x & 63, threadIdx.x >> 6, a.tiles_x, a.tiles, a.rows, a.half, a.colour, d.width, d.height, &px, &py))
-		strong_search_px(d, px, py);
-}
-
-// plane-cache plan of the split strong update (strong_reuse_plan): which of the pixel's planes still have their vector from its
-// previous visit, and where every slot's vector lies.  Light like the search, so that the 256-VGPR evaluation kernel only reads the result.
-extern "C" __global__ void __launch_bounds__(256) dvp_strong_plan(const Dev d, const LaunchArgs a) {
-	int px, py;
-	if (block_to_pixel(blockIdx.x, threadIdx.x & 63, threadIdx.x >> 6, a.tiles_x, a.tiles, a.rows, a.half, a.colour, d.width, d.height, &px, &py) &&
-	    d.weak_info[px + py * d.width] != DVP_WEAK)
-		strong_plan_px(d, px, py);
-}
-
-// line-scan pre-pass of GenEdgeInform: nearest edge pixel in 8 directions (blockIdx.y = direction)
-extern "C" __global__ void __launch_bounds__(256) dvp_edge_rays(const Dev d, int what) {
-	edge_ray_line(d, blockIdx.y, blockIdx.x * blockDim.x + threadIdx.x, what);
-}
-
-// ---- WEAK-pixel bookkeeping on the device (dvp_upload_state) -------------------------------------------------
-// neighbours_map (running index of WEAK pixels in raster order, APD.cpp:1182-1193) and the compacted WEAK list of the
-// list kernels used to be built by serial host loops over all L pixels per pass (25.6 M at full resolution: 0.2 s, plus a
-// 26 MB download when the weak map was already on the device).  Three small launches instead: ballot counts per unit,
-// one exclusive scan, ballot-rank scatter.
-// List order: 64 x 64 super-tiles row-major over the image, 16 x 16 tiles row-major inside them, rows inside those; black
-// ((x + y) even) pixels first, then red.  "Slot" = (super-tile, tile position 0..15); a slot outside the image counts zero.
-constexpr int kWeakTile = 16, kWeakSuper = 64, kWeakChunk = 1024;   // raster chunk of the neighbours_map scan
-DVP_HD void weak_slot_origin(int slot, int supers_x, int* tx, int* ty) {
-	const int super = slot >> 4, t = slot & 15;
-	*tx = (super % supers_x) * kWeakSuper + (t & 3) * kWeakTile;
-	*ty = (super / supers_x) * kWeakSuper + (t >> 2) * kWeakTile;
-}
-// one wave per slot: counts[slot] = black WEAK pixels, counts[n_slots + slot] = red ones;
-// one wave per raster chunk: counts[2 * n_slots + chunk] = WEAK pixels of the chunk
-extern "C" __global__ void __launch_bounds__(256) dvp_weak_counts(const uint8_t* __restrict__ weak, int W, int H, int supers_x, int n_slots, int n_chunks, int* __restrict__ counts) {
-	const int lane = threadIdx.x & 63;
-	const int unit = blockIdx.x * 4 + (threadIdx.x >> 6);
-	if (unit < n_slots) {
-		int tx, ty;
-		weak_slot_origin(unit, supers_x, &tx, &ty);
-		int nb = 0, nr = 0;
-		for (int step = 0; step < 4; ++step) {
-			const int x = tx + (lane & 15), y = ty + step * 4 + (lane >> 4);
-			const bool wk = x < W && y < H && weak[(size_t)y * W + x] == DVP_WEAK;
-			nb += __popcll(__ballot(wk && !((x + y) & 1)));
-			nr += __popcll(__ballot(wk && ((x + y) & 1)));
-		}
-		if (lane == 0) { counts[unit] = nb; counts[n_slots + unit] = nr; }
-	} else if (unit < n_slots + n_chunks) {
-		const int chunk = unit - n_slots;
-		const size_t L = (size_t)W * H;
-		int n = 0;
-		for (int step = 0; step < kWeakChunk / 64; ++step) {
-			const size_t i = (size_t)chunk * kWeakChunk + step * 64 + lane;
-			n += __popcll(__ballot(i < L && weak[i] == DVP_WEAK));
-		}
-		if (lane == 0) counts[2 * n_slots + chunk] = n;
-	}
-}
-// exclusive scan of three int arrays in place (one workgroup each): blockIdx.x selects [start[b], start[b + 1]); totals[b] = sum
-extern "C" __global__ void __launch_bounds__(1024) dvp_scan3(int* __restrict__ data, int s0, int s1, int s2, int s3, int* __restrict__ totals) {
-	__shared__ int part[1024];
-	__shared__ int carry;
-	const int starts[4] = { s0, s1, s2, s3 };
-	const int lo = starts[blockIdx.x], hi = starts[blockIdx.x + 1];
-	if (threadIdx.x == 0) carry = 0;
-	__syncthreads();
-	for (int base = lo; base < hi; base += 1024) {
-		const int i = base + (int)threadIdx.x;
-		const int v = i < hi ? data[i] : 0;
-		part[threadIdx.x] = v;
-		__syncthreads();
-		for (int off = 1; off < 1024; off <<= 1) {
-			const int add = threadIdx.x >= (unsigned)off ? part[threadIdx.x - off] : 0;
-			__syncthreads();
-			part[threadIdx.x] += add;
-			__syncthreads();
-		}
-		if (i < hi) data[i] = carry + part[threadIdx.x] - v;
-		__syncthreads();
-		if (threadIdx.x == 1023) carry += part[1023];
-		__syncthreads();
-	}
-	if (threadIdx.x == 0) totals[blockIdx.x] = carry;
-}
-// scatter: the list entries of a slot / the running indices of a chunk, in pixel order, by ballot rank
-extern "C" __global__ void __launch_bounds__(256) dvp_weak_fill(const uint8_t* __restrict__ weak, int W, int H, int supers_x, int n_slots, int n_chunks,
-                                                               const int* __restrict__ offs, const int* __restrict__ totals, int* __restrict__ list, int* __restrict__ map) {
-	const int lane = threadIdx.x & 63;
-	const int unit = blockIdx.x * 4 + (threadIdx.x >> 6);
-	const unsigned long long below = (1ull << lane) - 1ull;
-	if (unit < n_slots) {
-		int tx, ty;
-		weak_slot_origin(unit, supers_x, &tx, &ty);
-		int ob = offs[unit], orr = totals[0] + offs[n_slots + unit];   // red entries follow all black ones
-		for (int step = 0; step < 4; ++step) {
-			const int x = tx + (lane & 15), y = ty + step * 4 + (lane >> 4);
-			const bool wk = x < W && y < H && weak[(size_t)y * W + x] == DVP_WEAK;
-			const bool red = (x + y) & 1;
-			const unsigned long long mb = __ballot(wk && !red), mr = __ballot(wk && red);
-			if (wk) list[red ? orr + __popcll(mr & below) : ob + __popcll(mb & below)] = y * W + x;
-			ob += __popcll(mb);
-			orr += __popcll(mr);
-		}
-	} else if (unit < n_slots + n_chunks) {
-		const int chunk = unit - n_slots;
-		const size_t L = (size_t)W * H;
-		int o = offs[2 * n_slots + chunk];
-		for (int step = 0; step < kWeakChunk / 64; ++step) {
-			const size_t i = (size_t)chunk * kWeakChunk + step * 64 + lane;
-			const bool wk = i < L && weak[i] == DVP_WEAK;
-			const unsigned long long m = __ballot(wk);
-			if (i < L) map[i] = wk ? o + __popcll(m & below) : 0;
-			o += __popcll(m);
-		}
-	}
-}
-
-// RescaleMatToTargetSize (APD.cpp:1773-1795) for the five maps a REFINE_INIT pass inherits from the coarser pyramid level
-// (APD.cpp:1428-1456 depth + normal -> planes, selected views, :1169-1181 pixel states, :1648-1667 radius map): nearest
-// neighbour with the source's index rule — the ROW index is divided by the WIDTH ratio and the column index by the height
-// ratio (`o_r = r / scale_x`, `o_c = c / scale_y`, :1787-1788; the same unless the aspect ratios differ) — one IEEE float
-// division and a truncation each; a pixel whose source index falls outside the coarse map stays zero.  Then the radius
-// rule of APD.cpp:1660-1666: a pixel whose state is UNKNOWN restarts with the default patch radius.
-struct RescaleArgs {
-	int W, H, sw, sh;
-	float scale_x, scale_y;
-	const float* depth; const float* normal; const uint32_t* views; const uint8_t* weak; const int* radius;   // coarse maps; weak / radius may be null
-	f4* planes; uint32_t* out_views; uint8_t* out_weak; int* out_radius;
-	int radius_fallback;
-};
-extern "C" __global__ void __launch_bounds__(256) dvp_rescale_state(const RescaleArgs a) {
-	const int c = blockIdx.x * blockDim.x + threadIdx.x, r = blockIdx.y;
-	if (c >= a.W) return;
-	const int o_r = static_cast<int>(r / a.scale_x);
-	const int o_c = static_cast<int>(c / a.scale_y);
-	const bool in = o_r >= 0 && o_c >= 0 && o_r < a.sh && o_c < a.sw;
-	const size_t o = (size_t)r * a.W + c, i = in ? (size_t)o_r * a.sw + o_c : 0;
-	a.planes[o] = in ? mk4(a.normal[3 * i], a.normal[3 * i + 1], a.normal[3 * i + 2], a.depth[i]) : mk4(0.0f, 0.0f, 0.0f, 0.0f);
-	a.out_views[o] = in ? a.views[i] : 0u;
-	const uint8_t st = a.weak ? (in ? a.weak[i] : (uint8_t)0) : (uint8_t)DVP_STRONG;
-	a.out_weak[o] = st;
-	if (a.radius) a.out_radius[o] = st == DVP_UNKNOWN ? a.radius_fallback : (in ? a.radius[i] : 0);
-}
-
-// What the driver makes of the downloaded planes (main.cpp:300-309): depth map = plane.w where it lies inside
-// [depth_min, depth_max], else 0 and the pixel's state becomes UNKNOWN; normal map = plane.xyz.  (`!(w < min || w > max)`
-// as the source writes it: a NaN depth is kept.)
-extern "C" __global__ void __launch_bounds__(256) dvp_unpack_maps(const f4* __restrict__ planes, const uint8_t* __restrict__ weak, size_t L, float dmin, float dmax,
-                                                                 float* __restrict__ depth, float* __restrict__ normal, uint8_t* __restrict__ state) {
-	const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-	if (i >= L) return;
-	const f4 ph = planes[i];
-	const bool usable = !(ph.w < dmin || ph.w > dmax);
-	depth[i] = usable ? ph.w : 0.0f;
-	normal[3 * i] = ph.x; normal[3 * i + 1] = ph.y; normal[3 * i + 2] = ph.z;
-	state[i] = usable ? weak[i] : (uint8_t)DVP_UNKNOWN;
-}
-
-extern "C" __global__ void dvp_prepare_views(const DvpCamera* cams, ViewConst* views, int n) {
-	const int v = blockIdx.x * blockDim.x + threadIdx.x;
-	if (v >= 1 && v < n) compute_view_const(cams[0], cams[v], &views[v]);
-}
-
-// ComputeMultiViewCostVectorOld over a list of (pixel, plane) pairs — KATs and the roofline
-// micro-benchmark.  One lane per pair.
-extern "C" __global__ void __launch_bounds__(256) dvp_cost_vectors(const Dev d, const int* px, const f4* planes, int n, float* out) {
-	const int i = blockIdx.x * blockDim.x + threadIdx.x;
-	if (i >= n) return;
-	const int x = px[2 * i], y = px[2 * i + 1];
-	const int S = d.num_images - 1;
-	PatchCtx c;
-	__shared__ f2 lds_tab[kTaps * kTaps * 256];
-	int radius, inc;
-	patch_geometry(d, x + y * d.width, &radius, &inc);
-	build_patch_ctx(d, x, y, radius, inc, 0, PatchTab{&lds_tab[threadIdx.x], 256}, &c);
-	const f4 pl = planes[i];
-	for (int v = 0; v < S; ++v) out[(size_t)i * S + v] = d.sampler ? ncc_old<1>(d, c, x, y, v + 1, pl) : ncc_old<0>(d, c, x, y, v + 1, pl);
-}
-
-// same computation on every pixel with its current plane (camera frame); writes the view-mean
-extern "C" __global__ void __launch_bounds__(256) dvp_cost_all_pixels(const Dev d, const LaunchArgs a, float* out) {
-	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-	int px, py;
-	if (!block_to_pixel(blockIdx.x, lane, wave, a.tiles_x, a.tiles, a.rows, 0, 0, d.width, d.height, &px, &py)) return;
-	const int center = px + py * d.width;
-	const int S = d.num_images - 1;
-	PatchCtx c;
-	__shared__ f2 lds_tab[kTaps * kTaps * 256];
-	int radius, inc;
-	patch_geometry(d, center, &radius, &inc);
-	build_patch_ctx(d, px, py, radius, inc, 0, PatchTab{&lds_tab[threadIdx.x], 256}, &c);
-	const f4 pl = d.planes[center];
-	float acc = 0.0f;
-	for (int v = 0; v < S; ++v) acc += ncc_old<0>(d, c, px, py, v + 1, pl);
-	out[center] = acc / S;
-}
-
-
-#ifdef DVP_PROBE
-// ---- mapping probe (experiment, not part of the product): K evaluations x S views per pixel with the planes of pixels
-// `stride` apart, (A) lane = pixel like the NCC kernels, (B) lane = (pixel, view): 64 / S x-adjacent pixels per wave, the
-// patch table of a pixel shared by its S lanes in LDS.
-#ifndef DVP_PROBE_LB
-#define DVP_PROBE_LB 2
-#endif
-extern "C" __global__ void __launch_bounds__(256, 2) dvp_probe_a(const Dev d, const LaunchArgs a, float* out, int K, int stride) {
-	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-	int px, py;
-	if (!block_to_pixel(blockIdx.x, lane, wave, a.tiles_x, a.tiles, a.rows, 0, 0, d.width, d.height, &px, &py)) return;
-	const int center = px + py * d.width;
-	const int S = d.num_images - 1, L = d.width * d.height;
-	PatchCtx c;
-	__shared__ f2 lds_tab[kTaps * kTaps * 256];
-	int radius, inc;
-	patch_geometry(d, center, &radius, &inc);
-	build_patch_ctx(d, px, py, radius, inc, 0, PatchTab{&lds_tab[threadIdx.x], 256}, &c);
-	float acc = 0.0f;
-	for (int k = 0; k < K; ++k) {
-		int q = center + (k - K / 2) * stride;
-		q = q < 0 ? 0 : (q >= L ? L - 1 : q);
-		const f4 pl = d.planes[q];
-		for (int v = 0; v < S; ++v) acc += ncc_old<0>(d, c, px, py, v + 1, pl);
-	}
-	out[center] = acc;
-}
-extern "C" __global__ void __launch_bounds__(256, DVP_PROBE_LB) dvp_probe_b(const Dev d, float* out, int K, int stride) {
-	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-	const int S = d.num_images - 1, L = d.width * d.height;
-	const int P = 64 / S;                                // pixels per wave
-	const int waves_x = (d.width + P - 1) / P;
-	const int gw = blockIdx.x * 4 + wave;
-	const int py = gw / waves_x, x0 = (gw - py * waves_x) * P;
-	if (py >= d.height) return;
-	__shared__ f2 tab[4][9 * 36];                         // [wave][pixel][tap] (P <= 9... here P * 36 <= 324 for S >= 7)
-	__shared__ float caa[4][9 * 36];
-	__shared__ float sums[4][9][3];
-	const int v = lane / P, pi = lane - v * P;           // lanes of one view are contiguous
-	const int px = x0 + pi;
-	const bool active = v < S && px < d.width;
-	const int radius = d.params.strong_radius, inc = d.params.strong_increment;
-	// table: entry e = pixel * 36 + tap, built by whichever lane
-	for (int e = lane; e < P * 36; e += 64) {
-		const int pe = e / 36, t = e - pe * 36, ty = t / 6, tx = t - ty * 6;
-		const int qx = x0 + pe < d.width ? x0 + pe : d.width - 1;
-		const float cpix = img_texel(d.images, d.org, d.pitch, d.width, d.height, qx, py);
-		const float av = img_texel(d.images, d.org, d.pitch, d.width, d.height, qx - radius + tx * inc, py - radius + ty * inc);
-		const float w = bilateral_weight((float)(-radius + tx * inc), (float)(-radius + ty * inc), av, cpix, d.params.sigma_spatial, d.params.sigma_color, 0);
-		tab[wave][e] = mk2(w, w * av);
-		caa[wave][e] = w * av * av;
-	}
-	__builtin_amdgcn_wave_barrier();
-	if (lane < P) {
-		float sr = 0.0f, srr = 0.0f, ws = 0.0f;
-		for (int ty = 0; ty < 6; ++ty) {
-			float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f;
-			for (int tx = 0; tx < 6; ++tx) { const f2 t = tab[wave][lane * 36 + ty * 6 + tx]; a0 += t.y; a1 += caa[wave][lane * 36 + ty * 6 + tx]; a2 += t.x; }
-			sr += a0; srr += a1; ws += a2;
-		}
-		sums[wave][lane][0] = sr; sums[wave][lane][1] = srr; sums[wave][lane][2] = ws;
-	}
-	__builtin_amdgcn_wave_barrier();
-	if (!active) return;
-	PatchCtx c;
-	c.tab = PatchTab{&tab[wave][pi * 36], 1};
-	c.sum_ref = sums[wave][pi][0]; c.sum_ref_ref = sums[wave][pi][1]; c.wsum = sums[wave][pi][2];
-	c.radius = radius; c.inc = inc; c.fast = 1;
-	const ViewConst vc = d.views[v + 1];                  // per-lane record (vector loads)
-	const unsigned plane_off = (unsigned)((size_t)(v + 1) * d.plane_stride * 2 * sizeof(float));
-	const int center = px + py * d.width;
-	float acc = 0.0f;
-	for (int k = 0; k < K; ++k) {
-		int q = center + (k - K / 2) * stride;
-		q = q < 0 ? 0 : (q >= L ? L - 1 : q);
-		const f4 pl = d.planes[q];
-		float H[9];
-		homography(vc, pl, H);
-		const f2 pt = apply_homography(H, px, py);
-		if (pt.x >= vc.fw || pt.x < 0.0f || pt.y >= vc.fh || pt.y < 0.0f) { acc += 2.0f; continue; }
-		acc += ncc_patch_fast<0>(d, c, H, d.images, px, py, plane_off);
-	}
-	atomicAdd(&out[center], acc);
-}
-// ---- round 6: the SWEEP-shaped probe.  Work per pixel = DepthToWeak's: the 61 disparity slots around the
-// pixel's own plane + the current depth, against the views of `vmask`.  (C) lane = pixel, slots in a loop — the mapping of
-// dvp_sweep_eval; (D) wave = ONE pixel, lane = slot: the patch table is wave-uniform (288 B, read by LDS broadcast), a tap's 62
-// gathers walk one epipolar segment.  Both sum a pixel's costs views-inside-slots in the same order: identical bits.
-__device__ __forceinline__ float probe_slot_plane(const DvpCamera& rc, const f4 origin, float base_line, float disp, int k, int px, int py, const DvpParams& P, bool* in_range) {
-	float p_depth = origin.w;
-	*in_range = true;
-	if (k < 61) {
-		p_depth = rc.K[0] * base_line / (disp + (k - 30));
-		if (p_depth < P.depth_min || p_depth > P.depth_max) *in_range = false;
-	}
-	return distance_to_origin(rc, px, py, p_depth, origin);
-}
-extern "C" __global__ void __launch_bounds__(256, 2) dvp_probe_c(const Dev d, const LaunchArgs a, float* out, unsigned vmask) {
-	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-	int px, py;
-	if (!block_to_pixel(blockIdx.x, lane, wave, a.tiles_x, a.tiles, a.rows, 0, 0, d.width, d.height, &px, &py)) return;
-	const int center = px + py * d.width;
-	const int S = d.num_images - 1;
-	PatchCtx c;
-	__shared__ f2 lds_tab[kTaps * kTaps * 256];
-	int radius, inc;
-	patch_geometry(d, center, &radius, &inc);
-	build_patch_ctx(d, px, py, radius, inc, 0, PatchTab{&lds_tab[threadIdx.x], 256}, &c);
-	const DvpCamera rc = load_camera(d, 0);
-	const f4 origin = normal_world_to_cam(rc, d.planes[center]);
-	const float base_line = 0.4f, disp = rc.K[0] * base_line / origin.w;
-	float acc = 0.0f;
-	for (int k = 0; k < 62; ++k) {
-		bool ok;
-		f4 pl = origin;
-		pl.w = probe_slot_plane(rc, origin, base_line, disp, k, px, py, d.params, &ok);
-		float t = 0.0f;
-		if (ok) for (int v = 0; v < S; ++v) if ((vmask >> v) & 1) t += ncc_old<0>(d, c, px, py, v + 1, pl);
-		acc += t;
-	}
-	out[center] = acc;
-}
-#ifndef DVP_PROBE_NPX
-#define DVP_PROBE_NPX 16
-#endif
-extern "C" __global__ void __launch_bounds__(64, DVP_PROBE_LB) dvp_probe_d(const Dev d, float* out, unsigned vmask) {
-	const int lane = threadIdx.x;
-	const int S = d.num_images - 1;
-	__shared__ f2 ctab[kTaps * kTaps];
-	__shared__ float caa[kTaps * kTaps];
-	__shared__ float tot[64];
-	// block -> run of DVP_PROBE_NPX pixels of one row: XCD b % 8 owns a 64-pixel column of a strip of 8, four runs per row, rows top to bottom
-	const int runs = 64 / DVP_PROBE_NPX;
-	const int tiles_x = (d.width + 63) / 64;
-	const int per_strip = 8 * d.height * runs;
-	const int st = (int)blockIdx.x / per_strip, rem = (int)blockIdx.x - st * per_strip;
-	const int w_last = tiles_x - st * 8 >= 8 ? 8 : tiles_x - st * 8;
-	const int col = rem % w_last, k2 = rem / w_last;
-	const int py = k2 / runs, x0 = (st * 8 + col) * 64 + (k2 - py * runs) * DVP_PROBE_NPX;
-	if (py >= d.height) return;
-	const DvpCamera rc = load_camera(d, 0);
-	for (int i = 0; i < DVP_PROBE_NPX; ++i) {
-		const int px = x0 + i;
-		if (px >= d.width) break;
-		const int center = px + py * d.width;
-		int radius, inc;
-		patch_geometry(d, center, &radius, &inc);
-		PatchCtx c;
-		c.radius = radius; c.inc = inc; c.fast = 1;
-		c.tab = PatchTab{ctab, 1};
-		if (lane < kTaps * kTaps) {
-			const int ty = lane / kTaps, tx = lane - ty * kTaps;
-			const float cpix = img_texel(d.images, d.org, d.pitch, d.width, d.height, px, py);
-			const float av = img_texel(d.images, d.org, d.pitch, d.width, d.height, px - radius + tx * inc, py - radius + ty * inc);
-			const float w = bilateral_weight((float)(-radius + tx * inc), (float)(-radius + ty * inc), av, cpix, d.params.sigma_spatial, d.params.sigma_color, 0);
-			const float wa = w * av;
-			ctab[lane] = mk2(w, wa);
-			caa[lane] = wa * av;
-		}
-		__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-		{
-			float sr = 0.0f, srr = 0.0f, ws = 0.0f;
-			for (int ty = 0; ty < kTaps; ++ty) {
-				float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f;
-				for (int tx = 0; tx < kTaps; ++tx) { const f2 t = ctab[ty * kTaps + tx]; a0 += t.y; a1 += caa[ty * kTaps + tx]; a2 += t.x; }
-				sr += a0; srr += a1; ws += a2;
-			}
-			c.sum_ref = sr; c.sum_ref_ref = srr; c.wsum = ws;
-		}
-		f4 origin = normal_world_to_cam(rc, d.planes[center]);
-		origin.x = uniform_f(origin.x); origin.y = uniform_f(origin.y); origin.z = uniform_f(origin.z); origin.w = uniform_f(origin.w);
-		const float base_line = 0.4f, disp = rc.K[0] * base_line / origin.w;
-		bool ok;
-		f4 pl = origin;
-		pl.w = probe_slot_plane(rc, origin, base_line, disp, lane, px, py, d.params, &ok);
-		float t = 0.0f;
-		if (lane < 62 && ok) for (int v = 0; v < S; ++v) if ((vmask >> v) & 1) t += ncc_old<0>(d, c, px, py, v + 1, pl);
-		tot[lane] = t;
-		__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-		if (lane == 0) {
-			float acc = 0.0f;
-			for (int k = 0; k < 62; ++k) acc += tot[k];
-			out[center] = acc;
-		}
-		__builtin_amdgcn_wave_barrier();
-	}
-}
-extern "C" int dvp_probe(dvp_ctx* c, int mode, int K, int stride, int repeat, float* mean_ms, float* checksum);
-#endif
-
-// ------------------------------------------------------------------------------------------------
-// context
-// ------------------------------------------------------------------------------------------------
-struct EventPair { int stage; hipEvent_t a, b; };   // stage: launch site, or one of the two whole-run timers below
-enum { EV_TOTAL = -1, EV_ITER_LOOP = -2 };
-
-struct dvp_ctx {
-	int device = 0;
-	// The DVP_* switches as read when the context was created, and — the `*_fits` members below — whether the optional buffers
-	// of a form could be had.  Which form a launch site takes is decided from the two by dvp_forms.hpp.
-	FormSwitches sw;
-	int W = 0, H = 0, NI = 0, pitch = 0;
-	size_t L = 0;
-	hipStream_t stream = nullptr;
-	// second stream of dvp_run_patchmatch: the visibility-prior candidates (VALU-bound, read by the weak updates only)
-	// run beside the latency-bound list kernels of the weak path's preparation
-	// visibility-prior candidates at anchor pixels only (dvp_run_patchmatch; DVP_CAND_MASK=0: every pixel, as dvp_run_stage)
-	// Which form pays depends on the WEAK share: the full launch runs on the side stream beside the latency-bound anchor search and
-	// is hidden when that takes long enough (>= ~4.5 % WEAK at 6208x4128: bench cfg3, 6.9 % — masked there it would run beside
-	// RandomInit and the strong update instead and cost them 28 ms); at the 1-3 % WEAK of the real schedule's full-size passes the
-	// anchor search is over after 12-38 ms and the full launch was 50-60 ms exposed per view (profiles/r06_e2e_apd.txt).
-	// DVP_CAND_MASK=1 / 0 forces a form; default: masked below 4 % WEAK.
-	bool cand_mask_fits = true;    // false: the mark bytes did not fit
-	uint8_t* cand_mask = nullptr;
-	unsigned *cand_list = nullptr, *cand_n = nullptr;
-	uint32_t* sel_snap = nullptr;
-	hipStream_t side = nullptr;
-	hipEvent_t side_fork = nullptr, side_join = nullptr;
-	Dev d{};
-	std::vector<void*> allocs;
-	// named device buffers
-	float* images = nullptr;        // row-pair planes (dvp_dev.hpp: img_texel / load_quad)
-	uint8_t* images8 = nullptr;     // the same as bytes; images8_ok says whether the last upload was 8-bit exact
-	int* images8_flag = nullptr;
-	bool images8_ok = false;
-	uint32_t* images16 = nullptr;   // the same as binary16 pairs (Dev::images16), allocated at the first upload (or dvp_ctx_reserve) that wants them
-	bool images16_ok = false;       // the last upload is binary16-exact and not 8-bit exact: the weak update reads images16
-	float* image_stage = nullptr;   // plain padded planes the uploads land in before dvp_interleave_rows
-	float* depths = nullptr;
-	uint32_t* edge_bits = nullptr;  // bit-tiled copy of `edge`, rebuilt before the launches that walk lines
-	uint32_t* strong_bits = nullptr; // bit-tiled (weak_info == STRONG), rebuilt before FindNearestStrongPoint and GenNeighbours
-	uint32_t* strong_bits_t = nullptr;   // ... with transposed tiles (FindNearestStrongPoint's column segments)
-	int* edge_sat = nullptr;         // cell table of the edge map (Dev::edge_sat), rebuilt with edge_bits
-	DvpCamera* cameras = nullptr; ViewConst* views = nullptr; int* sector_taps = nullptr; int* sector_start = nullptr;
-	f4* planes = nullptr; f4* planes_snap = nullptr; f4* fit_planes = nullptr;
-	int* search_pos = nullptr;   // [16][L]
-	float* slot_costs = nullptr; // [17][S][half_w * H]: split strong update (allocated at its first launch)
-	float* strong_rec = nullptr; // [SR_FIELDS][half_w * H]
-	// plane cache of the split strong update (Dev::reuse_*), allocated with slot_costs' stand-in at the first launch
-	float* reuse_costs = nullptr; PlaneKey* reuse_keys = nullptr; ReuseHdr* reuse_hdr = nullptr;
-	bool reuse_fits = true;      // false: the records did not fit — the per-launch half-size cost buffer
-	uint32_t reuse_epoch = 0;    // bump_reuse_epoch
-	bool split_fits = true;      // false: slot_costs did not fit — the monolithic kernel
-	f4* sweep_rec = nullptr; float* sweep_cost = nullptr; float* sweep_pc = nullptr;   // DepthToWeak + LocalRefine as view-compacted passes (allocated at the first fused launch)
-	bool sweep_fits = true;      // false: the buffers did not fit — the fused per-pixel kernel
-	int sweep_band_rows = 0;     // rows of a band of sweep_cost (DVP_SWEEP_BAND_GB; 67 GB for the whole image at 6208x4128 with 9 sources); 0 = not banded
-	float* costs = nullptr; float* costs_snap = nullptr; float* complex_ = nullptr;
-	uint32_t* selected_views = nullptr;
-	uint8_t* view_weight = nullptr; uint8_t* weak_info = nullptr; uint8_t* weak_reliable = nullptr; uint8_t* edge = nullptr;
-	s2* label_stop = nullptr; s2* weak_nearest_strong = nullptr; s2* neighbours = nullptr; s2* gn_points = nullptr; int* gn_count = nullptr; s2* candidate = nullptr; s2* edge_neigh = nullptr; s2* label_boundary = nullptr;
-	int* neighbours_map = nullptr; int* label = nullptr; int* radius = nullptr;
-	unsigned long long* eval_counter = nullptr;
-	float* scratch_out = nullptr;
-	size_t weak_alloc = 0;       // capacity (in WEAK pixels) of the per-WEAK buffers
-	AnchorRec* anchor_tab = nullptr;   // [WEAK][S][11] reference sides of the anchor sub-patches (dvp_weak_wave.hpp), allocated at the first weak update
-	size_t anchor_tab_alloc = 0;       // capacity in records
-	bool anchor_tab_valid = false;     // built for the current anchors / offsets / images (any launch or upload that can change them clears it)
-	bool anchor_tab_fits = true;       // false: the table did not fit — the weak update forms the reference side per item
-	// the weak update as seven launches (dvp_weak_phased.hpp): per-WEAK-pixel hand-over, allocated at the first weak update
-	WeakRec* weak_rec = nullptr; f2* weak_ctab = nullptr; float* weak_ev = nullptr;
-	size_t weak_phase_alloc = 0;       // capacity in WEAK pixels
-	bool weak_phase_fits = true;       // false: the buffers did not fit — the one-wave form
-	int* weak_list = nullptr;    // compacted WEAK pixel indices (black first, then red)
-	size_t weak_list_alloc = 0;
-	int* weak_counts = nullptr;  // scratch of the device-side compaction: per-slot black / red counts, per-chunk counts, then 3 totals
-	int* weak_totals_host = nullptr;   // pinned: (black, red, all)
-	uint8_t* coarse = nullptr;   // staging of the coarser level's maps (dvp_upload_state_rescaled)
-	uint8_t* maps_out = nullptr; // staging of dvp_download_maps: depth [L] f32, normal [L][3] f32, selected views [L] u32, radius [L] i32, states [L] u8 (words first: all aligned)
-	// dvp_download_maps_begin / _finish: the copies to the host run on their own stream, from any thread, while this context is
-	// already on its next view; `dl_busy` = maps_out holds maps that have not been fetched yet
-	hipStream_t copy = nullptr;
-	uint8_t* maps_host = nullptr;   // pinned mirror of maps_out (one DMA, no staging through the runtime's pageable-copy path)
-	std::mutex dl_m;
-	std::condition_variable dl_cv;
-	bool dl_busy = false;
-	bool dl_fetching = false;   // a dvp_download_maps_finish call is running right now (it ends in bounded time)
-	size_t coarse_alloc = 0;
-	// dvp_preview_begin / _finish: the rendered previews (BGR) and their encodes, one slot per kind; like maps_out they are
-	// overwritten by the next dvp_preview_begin only
-	uint8_t* pv_bgr[3] = { nullptr, nullptr, nullptr };
-	dvpjpeg::Encoder pv_enc[3];
-	unsigned long long* pv_total = nullptr;   // pinned: the encodes' data sizes
-	hipEvent_t pv_done = nullptr;             // the last dvp_preview_begin's work on `stream`
-	hipStream_t pv_copy = nullptr;            // the fetches of dvp_preview_finish / _pixels (any thread)
-	int pv_kinds = 0;
-	// dvp_edge_map_begin / _finish: the Canny edge prior from image 0 (dvp_edges.hip).  Scratch and output maps exist from the
-	// first dvp_edge_map_begin (or dvp_ctx_reserve bit 3) on.  Two output slots: a driver fetches a view's map in the view's
-	// background job, when the context may have begun the next view's map already; _finish serves begun maps oldest first, and
-	// a third _begin overwrites the oldest map nobody fetched.
-	dvpedge::Scratch eg;
-	struct EdgeSlot { dvpmem::DevBlock map; hipEvent_t done = nullptr; unsigned long long seq = 0; bool pending = false, fetching = false; };
-	EdgeSlot eg_slot[2];
-	unsigned long long eg_seq = 0;
-	hipStream_t eg_copy = nullptr;            // the fetches of dvp_edge_map_finish (any thread)
-	std::mutex eg_m;
-	std::condition_variable eg_cv;
-	bool have_images = false;                 // dvp_upload_images* has run
-	// dvp_set_view_cleanup: the visibility-mask clean-up of the staged selected-view words (dvp_viewclean.hip).  The scratch exists
-	// from the first dvp_download_maps_begin with the clean-up on (or dvp_ctx_reserve bit 4) on.
-	dvpvc::Scratch vc;
-	bool vc_on = false;
-	int vc_num_src = 0, vc_min_region = 0;
-	// dvp_plane_prior: the monocular-depth plane prior of a FIRST_INIT pass (dvp_prior.hip).  The scratch exists from the first call on.
-	dvpprior::Scratch pr;
-	bool have_cameras = false;                // dvp_upload_cameras has run
-	// dvp_save_state / dvp_restore_state: device-side copy of the per-pixel input state
-	f4* saved_planes = nullptr; uint32_t* saved_views = nullptr; uint8_t* saved_weak = nullptr; int* saved_radius = nullptr;
-	bool have_saved = false;
-	int lut_radius = -1;
-	bool have_depths = false;
-	bool profiling = false;
-	std::vector<EventPair> events;
-	DvpTimings timings{};
-	std::string error;
-};
-
-static std::string g_create_error;
-
-#define HIP_TRY(ctx, expr)                                                                          \
-	do {                                                                                            \
-		hipError_t e_ = (expr);                                                                     \
-		if (e_ != hipSuccess) {                                                                     \
-			char buf_[512];                                                                         \
-			snprintf(buf_, sizeof(buf_), "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-			(ctx)->error = buf_;                                                                    \
-			return 1;                                                                               \
-		}                                                                                           \
-	} while (0)
-
-template <class T>
-static int dalloc(dvp_ctx* c, T** p, size_t count, bool zero = true) {
-	void* q = nullptr;
-	const size_t bytes = (count ? count : 1) * sizeof(T);
-	HIP_TRY(c, hipMalloc(&q, bytes));
-	c->allocs.push_back(q);
-	if (zero) HIP_TRY(c, hipMemsetAsync(q, 0, bytes, c->stream));
-	*p = (T*)q;
-	return 0;
-}
-
-// give a superseded block back (the caller has made sure no queued work still uses it)
-template <class T>
-static void dfree(dvp_ctx* c, T** p) {
-	if (!*p) return;
-	for (size_t i = 0; i < c->allocs.size(); ++i)
-		if (c->allocs[i] == (void*)*p) { c->allocs[i] = c->allocs.back(); c->allocs.pop_back(); break; }
-	(void)hipFree((void*)*p);
-	*p = nullptr;
-}
-
-// one block of a group of optional buffers (alloc_group_or_fall_back)
-struct AllocReq { void** p; size_t bytes; bool zero; };   // p == nullptr: nothing to allocate
-template <class T>
-static AllocReq areq(T** p, size_t bytes, bool zero = false) { return { reinterpret_cast<void**>(p), bytes, zero }; }
-
-// The plane cache's records (Dev::reuse_*) hold cost vectors from one strong update of a pass to the next.  A vector depends on
-// the images, the cameras, the parameters, the sampler and the radius map (the header checks the pixel's own radius): every call
-// that can change one of them, and the start of every dvp_run_patchmatch, makes all records empty by moving on to a new epoch.
-static void bump_reuse_epoch(dvp_ctx* c) {
-	if (++c->reuse_epoch == 0) {   // wrapped: headers of 2^32 epochs ago must not match
-		if (c->reuse_hdr) (void)hipMemsetAsync(c->reuse_hdr, 0, c->L * sizeof(ReuseHdr), c->stream);
-		c->reuse_epoch = 1;
-	}
-	c->d.reuse_epoch = c->reuse_epoch;
-}
-
-static size_t img16_plane_bytes(int W, int H) { return (size_t)img16_tiles_x(W) * img16_tiles_y(H) * 128; }
-
-static bool anchor_table_off(const dvp_ctx* c) { return c->sw.anchor_tab_off || !c->anchor_tab_fits; }
-
-static void sync_dev_struct(dvp_ctx* c) {
-	Dev& d = c->d;
-	d.width = c->W; d.height = c->H; d.num_images = c->NI; d.pitch = c->pitch;
-	d.org = kImgPad * c->pitch + kImgPad;
-	d.plane_stride = (size_t)c->pitch * (c->H + 2 * kImgPad);
-	d.images = c->images; d.images8 = c->images8_ok ? c->images8 : nullptr; d.img8_tiles_x = img8_tiles_x(c->W); d.img8_plane_bytes = (size_t)img8_tiles_x(c->W) * img8_tiles_y(c->H) * 128;
-	d.images16 = c->images16_ok ? c->images16 : nullptr; d.img16_tiles_x = img16_tiles_x(c->W); d.img16_plane_bytes = img16_plane_bytes(c->W, c->H);
-	d.depths = c->depths; d.cameras = c->cameras; d.views = c->views; d.sector_taps = c->sector_taps; d.sector_start = c->sector_start;
-	d.search_pos = c->search_pos;
-	d.sweep_px0 = 0; d.sweep_row0 = 0; d.sweep_row1 = 0;   // (set per band by the sweep passes' launches)
-	d.sweep_all_slots = c->sw.sweep_all_slots ? 1 : 0;
-	d.sweep_rec = c->sweep_rec; d.sweep_cost = c->sweep_cost; d.sweep_pc = c->sweep_pc; d.slot_costs = c->slot_costs; d.strong_rec = c->strong_rec; d.half_w = (c->W + 1) / 2;
-	d.reuse_costs = c->reuse_costs; d.reuse_keys = c->reuse_keys; d.reuse_hdr = c->reuse_hdr; d.reuse_epoch = c->reuse_epoch;
-	d.planes = c->planes; d.planes_snap = c->planes_snap; d.costs = c->costs; d.costs_snap = c->costs_snap;
-	d.selected_views = c->selected_views; d.view_weight = c->view_weight; d.weak_info = c->weak_info;
-	d.weak_reliable = c->weak_reliable; d.weak_nearest_strong = c->weak_nearest_strong;
-	d.anchor_tab = (anchor_table_off(c) || !c->anchor_tab_valid) ? nullptr : c->anchor_tab; d.neighbours_map = c->neighbours_map; d.neighbours = c->neighbours; d.gn_points = c->gn_points; d.gn_count = c->gn_count; d.fit_planes = c->fit_planes;
-	d.candidate = c->candidate; d.edge = c->edge; d.edge_bits = c->edge_bits; d.strong_bits = c->strong_bits; d.strong_bits_t = c->strong_bits_t; d.edge_sat = c->edge_sat; d.sat_cells_x = sat_cells(c->W); d.sat_cells_y = sat_cells(c->H); d.edge_tiles_x = edge_tiles_x(c->W); d.edge_neigh = c->edge_neigh; d.label = c->label;
-	d.label_boundary = c->label_boundary; d.label_stop = c->label_stop; d.complex_ = c->complex_; d.radius = c->radius;
-	d.weak_list = c->weak_list;
-	d.weak_rec = c->weak_rec; d.weak_ctab = c->weak_ctab; d.weak_ev = c->weak_ev;
-	d.eval_counter = c->profiling ? c->eval_counter : nullptr;
-}
-
-// the binary16 planes, allocated once per context and only by the contexts that see such image sets (or are told to expect them)
-static int ensure_images16(dvp_ctx* c) {
-	if (c->images16) return 0;
-	return dalloc(c, &c->images16, img16_plane_bytes(c->W, c->H) / 4 * c->NI, false);
-}
-
-static int set_device(dvp_ctx* c) {
-	HIP_TRY(c, hipSetDevice(c->device));
-	return 0;
-}
 
 extern "C" {
 
@@ -1853,34 +536,6 @@ int dvp_set_profiling(dvp_ctx* c, int on) { c->profiling = on != 0; sync_dev_str
 // dvp_ctx_reserve, off the critical path (a multi-GB hipMalloc inside a launch site took 0.5-1 s of a view on some boxes:
 // profiles/r06_ab_notes.txt).  A group that does not fit is not an error: the site takes the form that does without — the same bits.
 
-// All of `reqs` (four at most), in order, or none of them.  On success the pointers are set, owned by the context and in c->d.
-// Otherwise *fits goes false and `msg`, a format with one %f for `gb`, says so.  `hook`: the tests' environment variable that
-// takes the fall-back without trying.  `retry_bytes`: a smaller size to try for the first block when the asked one is refused.
-// Returns the bytes of the first block, 0 for the fall-back.
-static size_t alloc_group_or_fall_back(dvp_ctx* c, std::initializer_list<AllocReq> reqs, const char* hook, bool* fits, const char* msg, double gb, size_t retry_bytes = 0) {
-	void* got[4] = { nullptr, nullptr, nullptr, nullptr };
-	const AllocReq* r = reqs.begin();
-	const size_t n = reqs.size();
-	size_t first = r[0].bytes;
-	bool ok = n <= 4 && !(hook && getenv(hook));
-	for (size_t i = 0; i < n && ok; ++i) {
-		if (!r[i].p) continue;
-		ok = hipMalloc(&got[i], r[i].bytes) == hipSuccess;
-		if (!ok && i == 0 && retry_bytes) { (void)hipGetLastError(); first = retry_bytes; ok = hipMalloc(&got[0], first) == hipSuccess; }
-		if (!ok) got[i] = nullptr;
-		else if (r[i].zero) ok = hipMemsetAsync(got[i], 0, r[i].bytes, c->stream) == hipSuccess;   // (never the block with a retry size)
-	}
-	if (!ok) {
-		(void)hipGetLastError();   // clear the sticky out-of-memory status
-		for (void* q : got) if (q) (void)hipFree(q);
-		*fits = false;
-		if (msg) fprintf(stderr, msg, gb);
-	}
-	else for (size_t i = 0; i < n; ++i) if (r[i].p) { *r[i].p = got[i]; c->allocs.push_back(got[i]); }
-	sync_dev_struct(c);   // (also after a refusal: the callers have freed the blocks they were replacing)
-	return ok ? first : 0;
-}
-
 // The pass' table of anchor reference sides (dvp_weak_wave.hpp: build_anchor_record) — built at the first weak update after
 // anything that can change the anchors (GenNeighbours, NeigbourUpdate), the offsets (GenEdgeInform), the images or the WEAK
 // list; the iterations of a pass then share it.
@@ -2344,7 +999,7 @@ int dvp_run_patchmatch(dvp_ctx* c) {
 	if (launch_stage(c, DVP_ST_FILTER_STRONG, 0, 0)) return 1;
 	if (launch_stage(c, DVP_ST_FILTER_STRONG, 0, 1)) return 1;
 	// DepthToWeak and LocalRefine (APD.cu:4502-4505) in ONE launch: LocalRefine's sweep repeats eleven planes of
-	// DepthToWeak's (dvp_strong.hpp, depth_to_weak_px).  Timed in the DVP_ST_DEPTH_TO_WEAK bucket.
+	// DepthToWeak's (dvp_sweep.hpp, depth_to_weak_px).  Timed in the DVP_ST_DEPTH_TO_WEAK bucket.
 	if (launch_stage(c, DVP_ST_DEPTH_TO_WEAK, 0, 0, true)) return 1;
 	HIP_TRY(c, hipEventRecord(tot.b, c->stream));
 	c->events.push_back(tot);
@@ -2673,13 +1328,6 @@ int dvp_reset_timings(dvp_ctx* c) {
 }
 
 // ---- KAT / micro-benchmark ---------------------------------------------------------------------
-namespace {
-struct EventPairGuard {
-	hipEvent_t a = nullptr, b = nullptr;
-	~EventPairGuard() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-};
-}  // namespace
-
 int dvp_eval_cost_vectors(dvp_ctx* c, const int32_t* px, const float* planes, int n, float* out, float* kernel_ms) {
 	if (set_device(c)) return 1;
 	if (!c->sector_taps) { c->error = "dvp_set_params must be called first"; return 1; }
@@ -2725,39 +1373,5 @@ int dvp_bench_cost_kernel(dvp_ctx* c, int repeat, float* mean_kernel_ms, uint64_
 	if (evals_per_launch) *evals_per_launch = (uint64_t)c->L * (uint64_t)(c->NI - 1);
 	return 0;
 }
-
-#ifdef DVP_PROBE
-int dvp_probe(dvp_ctx* c, int mode, int K, int stride, int repeat, float* mean_ms, float* checksum) {
-	if (set_device(c)) return 1;
-	const LaunchGeom g = make_geom(c->W, c->H, false);
-	LaunchArgs a;
-	a.tiles_x = g.tiles_x; a.tiles = g.tiles; a.rows = g.rows; a.half = 0; a.colour = 0; a.iter = 0;
-	const int S = c->NI - 1, P = 64 / S;
-	const int waves = ((c->W + P - 1) / P) * c->H;
-	EventPairGuard ev;
-	HIP_TRY(c, hipEventCreate(&ev.a));
-	HIP_TRY(c, hipEventCreate(&ev.b));
-	for (int i = 0; i <= repeat; ++i) {
-		if (i == 1) HIP_TRY(c, hipEventRecord(ev.a, c->stream));
-		HIP_TRY(c, hipMemsetAsync(c->scratch_out, 0, c->L * 4, c->stream));
-		if (mode == 0) hipLaunchKernelGGL(dvp_probe_a, dim3(g.grid()), dim3(256), 0, c->stream, c->d, a, c->scratch_out, K, stride);
-		else if (mode == 1) hipLaunchKernelGGL(dvp_probe_b, dim3((waves + 3) / 4), dim3(256), 0, c->stream, c->d, c->scratch_out, K, stride);
-		else if (mode == 2) hipLaunchKernelGGL(dvp_probe_c, dim3(g.grid()), dim3(256), 0, c->stream, c->d, a, c->scratch_out, (unsigned)K);   // K = view mask
-		else hipLaunchKernelGGL(dvp_probe_d, dim3((unsigned)(g.tiles_x * c->H * (64 / DVP_PROBE_NPX))), dim3(64), 0, c->stream, c->d, c->scratch_out, (unsigned)K);
-	}
-	HIP_TRY(c, hipEventRecord(ev.b, c->stream));
-	HIP_TRY(c, hipGetLastError());
-	HIP_TRY(c, hipStreamSynchronize(c->stream));
-	float ms = 0.0f;
-	HIP_TRY(c, hipEventElapsedTime(&ms, ev.a, ev.b));
-	*mean_ms = ms / repeat;
-	std::vector<float> h(c->L);
-	HIP_TRY(c, hipMemcpy(h.data(), c->scratch_out, c->L * 4, hipMemcpyDeviceToHost));
-	double sum = 0;
-	for (float v : h) sum += v;
-	*checksum = (float)(sum / (double)c->L);
-	return 0;
-}
-#endif
 
 }  // extern "C"

@@ -7,6 +7,7 @@
 #include "dvp_ransac.hpp"
 #include "dvp_weak_wave.hpp"
 #include "dvp_weak_phased.hpp"
+#include "dvp_sweep.hpp"
 #include <vector>
 #include <cmath>
 
@@ -138,7 +139,7 @@ DVP_HD void run_pixel(const Dev& d, int px, int py, int iter, unsigned long long
 	else if (STAGE == DVP_ST_FILTER_STRONG) { if (d.weak_info[center] != DVP_WEAK) filter_strong_px(d, px, py); }
 	else if (STAGE == DVP_ST_DEPTH_TO_WEAK) depth_to_weak_px<SMP, false>(d, px, py, tab, nevals);
 	else if (STAGE == kStageSweeps) {
-		// iter == kSweepBorderOnly: the border launch of the view-compacted form (sweep_* in dvp_strong.hpp), which leaves the
+		// iter == kSweepBorderOnly: the border launch of the view-compacted form (sweep_* in dvp_sweep.hpp), which leaves the
 		// 6-pixel frame — UNKNOWN for DepthToWeak, a full LocalRefine — to this kernel
 		if (iter == kSweepBorderOnly && !sweep_is_border(d, px, py)) return;
 		depth_to_weak_px<SMP, true>(d, px, py, tab, nevals);

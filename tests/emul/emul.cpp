@@ -30,7 +30,7 @@ struct Emu {
 	std::vector<f4> planes, planes_snap, fit_planes;
 	std::vector<int> search_pos;
 	std::vector<float> slot_costs, strong_rec;   // the split strong update's hand-over buffers (dvp_strong.hpp)
-	std::vector<f4> sweep_rec;                   // DepthToWeak + LocalRefine as view-compacted passes (dvp_strong.hpp: sweep_*)
+	std::vector<f4> sweep_rec;                   // DepthToWeak + LocalRefine as view-compacted passes (dvp_sweep.hpp: sweep_*)
 	std::vector<float> sweep_cost, sweep_pc;
 	std::vector<float> costs, costs_snap, complex_;
 	std::vector<uint32_t> selected_views;

@@ -5,7 +5,7 @@
 
 extern "C" {
 
-// the switch as the engine reads it when a context is created (dvp_engine.hip: sync_dev_struct); the emulation's own launches
+// the switch as the engine reads it when a context is created (dvp_ctx.hpp: sync_dev_struct); the emulation's own launches
 // (emu_run_stage: the fused kernel, the separate kernels) then see it in Dev
 void swh_read_switches(void* c) { ((Emu*)c)->d.sweep_all_slots = read_form_switches().sweep_all_slots ? 1 : 0; }
 

@@ -140,7 +140,7 @@ def test_two_pass_weak_path_with_geom(images, anchors, monkeypatch):
 @pytest.mark.parametrize("geom", [0, 1])
 def test_fused_sweeps_equal_the_two_launches(geom, form, wpr, monkeypatch):
     """`form`: the fused launch site as view-compacted passes (prepare / evaluate per view over the pixels that selected it /
-    decide, dvp_strong.hpp: sweep_*) or as the one per-pixel kernel (DVP_SWEEP_SPLIT=0); `wpr`: weak_peak_radius — the
+    decide, dvp_sweep.hpp: sweep_*) or as the one per-pixel kernel (DVP_SWEEP_SPLIT=0); `wpr`: weak_peak_radius — the
     central window that is evaluated first grows with it (9 -> 21 slots, 40 -> the whole line, no second stage).
     dvp_run_patchmatch issues DepthToWeak + LocalRefine (APD.cu:4502-4505) as ONE launch; dvp_run_stage keeps
     them separate.  Both must leave the same bits (and both equal the oracle's two functions, checked by the

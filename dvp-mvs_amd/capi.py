@@ -43,7 +43,8 @@ EXPORTS = ["dvp_ctx_create", "dvp_ctx_destroy", "dvp_ctx_reserve", "dvp_last_err
            "dvp_jpeg_decode", "dvp_jpeg_decode_into_store", "dvp_jpeg_decode_timings", "dvp_jpeg_decode_last_error",
            "dvp_plane_prior", "dvp_plane_prior_stage", "dvp_plane_prior_timings",
            "dvp_view_scores", "dvp_convert_image", "dvp_pairs_last_error",
-           "dvp_undistort_image", "dvp_undistort_last_error"]
+           "dvp_undistort_image", "dvp_undistort_last_error",
+           "dvp_cloud_distances", "dvp_cloud_evaluate", "dvp_cloud_last_error"]
 # ... and the one whose name holds a digit (a scan of the header for [a-z_] names does not see it)
 EXPORTS_WITH_DIGITS = ["dvp_upload_images_u8"]
 PREVIEW_DEPTH, PREVIEW_NORMAL, PREVIEW_WEAK = 1, 2, 4
@@ -164,6 +165,10 @@ def lib():
         L.dvp_undistort_image.argtypes = [ci, vp, ci, ci, ll, ci, vp, ci, vp]
         L.dvp_undistort_last_error.restype = ctypes.c_char_p
         L.dvp_undistort_last_error.argtypes = []
+        L.dvp_cloud_distances.argtypes = [ci, vp, ll, vp, ll, ctypes.c_float, vp]
+        L.dvp_cloud_evaluate.argtypes = [ci, vp, ll, vp, ll, vp, ci, vp, vp, vp, vp, vp]
+        L.dvp_cloud_last_error.restype = ctypes.c_char_p
+        L.dvp_cloud_last_error.argtypes = []
         _LIB = L
     return _LIB
 
@@ -224,6 +229,46 @@ def convert_image(bgr, pad_w, pad_h, out_w, out_h, device=0):
     out = np.empty((max(int(out_h), 0), max(int(out_w), 0), 3), np.uint8)
     if L.dvp_convert_image(device, _p(a), a.shape[1], a.shape[0], a.strides[0], int(pad_w), int(pad_h), int(out_w), int(out_h), _p(out)) != 0:
         raise DvpError(L.dvp_pairs_last_error().decode())
+    return out
+
+
+def _cloud(points, what):
+    a = np.ascontiguousarray(points, np.float32)
+    if a.ndim != 2 or a.shape[1] != 3:
+        raise ValueError("%s: a (N, 3) array of points is required" % what)
+    return a
+
+
+def cloud_distances(query, target, max_distance, device=0):
+    """(N,) float32 squared distances from every query point to its nearest target, +inf beyond max_distance, NaN for a query with a
+    non-finite coordinate, computed on the GPU (include/dvp_mvs.h dvp_cloud_distances)"""
+    L = lib()
+    q, t = _cloud(query, "cloud_distances"), _cloud(target, "cloud_distances")
+    out = np.empty(len(q), np.float32)
+    if L.dvp_cloud_distances(device, _p(q), len(q), _p(t), len(t), float(max_distance), _p(out)) != 0:
+        raise DvpError(L.dvp_cloud_last_error().decode())
+    return out
+
+
+def cloud_evaluate(recon, truth, tolerances, device=0, distances=False):
+    """dict(within_recon, within_truth: (K,) int64; used: (2,) int64; accuracy, completeness, f1: (K,) float64 fractions) of a
+    reconstructed cloud against a ground-truth cloud (include/dvp_mvs.h dvp_cloud_evaluate); distances=True adds d2_recon, d2_truth"""
+    L = lib()
+    r, t = _cloud(recon, "cloud_evaluate"), _cloud(truth, "cloud_evaluate")
+    tol = np.ascontiguousarray(tolerances, np.float32).reshape(-1)
+    wr, wt, used = np.zeros(max(tol.size, 1), np.int64), np.zeros(max(tol.size, 1), np.int64), np.zeros(2, np.int64)
+    dr = np.empty(len(r), np.float32) if distances else None
+    dt = np.empty(len(t), np.float32) if distances else None
+    if L.dvp_cloud_evaluate(device, _p(r), len(r), _p(t), len(t), _p(tol), tol.size, _p(wr), _p(wt), _p(used), _p(dr), _p(dt)) != 0:
+        raise DvpError(L.dvp_cloud_last_error().decode())
+    wr, wt = wr[:tol.size], wt[:tol.size]
+    a = wr / used[0] if used[0] else np.zeros(tol.size)
+    c = wt / used[1] if used[1] else np.zeros(tol.size)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        f1 = np.where(a + c > 0, 2 * a * c / (a + c), 0.0)
+    out = dict(within_recon=wr, within_truth=wt, used=used, accuracy=a, completeness=c, f1=f1)
+    if distances:
+        out.update(d2_recon=dr, d2_truth=dt)
     return out
 
 

@@ -8,6 +8,8 @@
 //   apd --convert-from <colmap folder> <save folder> [--model-dir NAME] [--model-ext .txt|.bin] [--scale-factor F] [--max-d N]
 //       [--interval-scale F] [--sfm on|off] [--convert-on gpu|host] [--undistort on|off] [--gpu N]
 //       the reference's colmap2mvsnet.py: a COLMAP model -> the folder the first form reads (host/colmap.cpp)
+//   apd --evaluate <recon.ply> --against <truth.ply> [--tolerances T0,T1,...] [--evaluate-on gpu|host] [--gpu N] [--out FILE]
+//       accuracy, completeness and F1 of a fused cloud against a ground-truth cloud (host/evaluate.cpp)
 //
 // Schedule.  The image pyramid has round_num levels (the longer side is halved until <= 800).  Level i
 // runs one "A" pass without geometric consistency — FIRST_INIT from scratch / the Depth-Anything prior
@@ -30,6 +32,7 @@
 #include <thread>
 #include "comm.h"
 #include "colmap.h"
+#include "evaluate.h"
 #include <cstdlib>
 #include <map>
 #include <set>
@@ -634,10 +637,49 @@ int ConvertMain(int argc, char** argv) {
 	return EXIT_SUCCESS;
 }
 
+// apd --evaluate <recon.ply> --against <truth.ply> [options]: no engine context, no rank, no result store
+int EvaluateMain(int argc, char** argv) {
+	const char* usage = "USAGE: apd --evaluate recon.ply --against truth.ply [--tolerances 0.01,0.02,0.05,0.1,0.2,0.5] [--evaluate-on gpu|host] [--gpu N] [--out FILE]\n";
+	if (argc < 3 || argv[2][0] == '-') { std::cerr << usage; return EXIT_FAILURE; }
+	EvaluateOptions o;
+	o.recon = argv[2];
+	for (int a = 3; a < argc; ++a) {
+		const std::string s = argv[a];
+		if (a + 1 >= argc) { std::cerr << s << " takes a value\n" << usage; return EXIT_FAILURE; }
+		const std::string v = argv[++a];
+		if (s == "--against") o.truth = v;
+		else if (s == "--tolerances") {
+			o.tolerances.clear();
+			std::stringstream list(v);
+			std::string item;
+			while (std::getline(list, item, ',')) {
+				char* end = nullptr;
+				const float t = std::strtof(item.c_str(), &end);
+				if (item.empty() || *end) { std::cerr << "--tolerances takes numbers separated by commas, got `" << item << "`\n"; return EXIT_FAILURE; }
+				o.tolerances.push_back(t);
+			}
+			if (o.tolerances.empty() || o.tolerances.size() > 8) { std::cerr << "--tolerances takes 1 to 8 numbers\n"; return EXIT_FAILURE; }
+		}
+		else if (s == "--evaluate-on") {
+			if (v != "gpu" && v != "host") { std::cerr << "--evaluate-on takes gpu or host\n"; return EXIT_FAILURE; }
+			o.on_gpu = v == "gpu";
+		}
+		else if (s == "--gpu") o.device = std::atoi(v.c_str());
+		else if (s == "--out") o.out = v;
+		else { std::cerr << "unknown option " << s << "\n" << usage; return EXIT_FAILURE; }
+	}
+	if (o.truth.empty()) { std::cerr << "--against is required\n" << usage; return EXIT_FAILURE; }
+	std::string report, error;
+	if (!EvaluateClouds(o, &report, &error)) { std::cerr << "apd --evaluate: " << error << std::endl; return EXIT_FAILURE; }
+	std::cout << report << std::flush;
+	return EXIT_SUCCESS;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
 	if (argc >= 2 && std::string(argv[1]) == "--convert-from") return ConvertMain(argc, argv);
+	if (argc >= 2 && std::string(argv[1]) == "--evaluate") return EvaluateMain(argc, argv);
 	if (argc < 2) {
 		std::cerr << "USAGE: apd dense_folder [gpu_index] [--previews] [--max-src N] [--iters N] [--min-scale S] [--passes P] [--seed X] [--rank R --world N [--job ID]] [--jacobi] [--no-fusion | --fusion KIND] [--fusion-on device|host] [--edges-on host|gpu] [--labels-on host|gpu] [--cleanup-on host|gpu] [--images-on host|gpu] [--prior-on host|gpu] [--decode-on host|gpu] [--strong-wide on|off] [--views-in-flight N]\n";
 		return EXIT_FAILURE;

@@ -483,6 +483,27 @@ const char* dvp_pairs_last_error(void);   /* the calling thread's last error of 
 int dvp_undistort_image(int device, const uint8_t* bgr, int w, int h, long long pitch, int model, const double* params, int num_params, uint8_t* out);
 const char* dvp_undistort_last_error(void);   /* the calling thread's last error of the one above */
 
+/* ---- `apd --evaluate`: a fused cloud scored against a ground-truth cloud; the reference has no counterpart, the definition is the
+ * project's own (csrc/dvp_cloudeval.hpp, DESIGN.md "Cloud evaluation") ---------------------------------------------------------------
+ * For a query p: m(p) = the minimum over the targets q with three finite coordinates of (dx*dx + dy*dy) + dz*dz, d = p - q, in
+ * binary32 with one rounding per operator; d2(p) = m(p) if m(p) <= T*T (binary32 product, T = max_distance or the largest
+ * tolerance), else +inf; NaN for a query with a non-finite coordinate; +inf everywhere when no target is finite.  Equal to the
+ * brute-force double loop bit for bit, whatever order the device works in.
+ * d2_out[i] as defined above for query i against the target cloud; xyz arrays are packed float triples (host pointers) */
+int dvp_cloud_distances(int device, const float* query_xyz, long long num_query, const float* target_xyz, long long num_target, float max_distance, float* d2_out);
+/* both directions and the counts; within_* hold num_tol entries, used[0] / used[1] the finite-coordinate points of recon / truth;
+ * d2_recon / d2_truth may be NULL.  within_recon[k] = the finite-coordinate points of recon with d2 <= t_k * t_k (binary32 product)
+ * against truth, within_truth[k] the same with the roles swapped: accuracy(k) = within_recon[k] / used[0], completeness(k) =
+ * within_truth[k] / used[1].
+ * Errors: a null pointer, a count outside 0 ... 2^31 - 1, more than 2^30 points with finite coordinates in the two clouds together
+ * (both functions), num_tol outside 1 ... 8, a tolerance that is not finite and positive or
+ * whose square is not a normal binary32 number, tolerances that do not strictly ascend, clouds that extend over more than
+ * 2^21 - 2 cells of the largest tolerance along an axis, no device memory.  Host in, host out; safe from several threads. */
+int dvp_cloud_evaluate(int device, const float* recon_xyz, long long num_recon, const float* truth_xyz, long long num_truth,
+                       const float* tolerances, int num_tol, long long* within_recon, long long* within_truth,
+                       long long* used, float* d2_recon, float* d2_truth);
+const char* dvp_cloud_last_error(void);   /* the calling thread's last error of the two above */
+
 #ifdef __cplusplus
 }
 #endif

@@ -73,6 +73,10 @@ struct dvp_ctx {
 	f4* sweep_rec = nullptr; float* sweep_cost = nullptr; float* sweep_pc = nullptr;   // DepthToWeak + LocalRefine as view-compacted passes (allocated at the first fused launch)
 	bool sweep_fits = true;      // false: the buffers did not fit — the fused per-pixel kernel
 	int sweep_band_rows = 0;     // rows of a band of sweep_cost (DVP_SWEEP_BAND_GB; 67 GB for the whole image at 6208x4128 with 9 sources); 0 = not banded
+	// the passes' evaluation launches from per-view lists (dvp_sweep_list.hpp): a group of its own, allocated behind the cost records
+	uint32_t* sweep_list = nullptr; int* sweep_list_counts = nullptr;   // [S][cap] entries; [S][tiles] counts / offsets, then the lengths [S, padded to threes]
+	int sweep_list_cap = 0, sweep_list_tiles = 0;   // room per view: the pixels of the image or of a band; tiles of an evaluation launch at most
+	bool sweep_list_fits = true; // false: the lists did not fit — the tile form (dvp_sweep_eval)
 	float* costs = nullptr; float* costs_snap = nullptr; float* complex_ = nullptr;
 	uint32_t* selected_views = nullptr;
 	uint8_t* view_weight = nullptr; uint8_t* weak_info = nullptr; uint8_t* weak_reliable = nullptr; uint8_t* edge = nullptr;
@@ -209,6 +213,8 @@ static void sync_dev_struct(dvp_ctx* c) {
 	d.sweep_px0 = 0; d.sweep_row0 = 0; d.sweep_row1 = 0;   // (set per band by the sweep passes' launches)
 	d.sweep_all_slots = c->sw.sweep_all_slots ? 1 : 0;
 	d.sweep_rec = c->sweep_rec; d.sweep_cost = c->sweep_cost; d.sweep_pc = c->sweep_pc; d.slot_costs = c->slot_costs; d.strong_rec = c->strong_rec; d.half_w = (c->W + 1) / 2;
+	d.sweep_list = c->sweep_list; d.sweep_list_counts = c->sweep_list_counts; d.sweep_list_cap = c->sweep_list_cap;
+	d.sweep_list_n = c->sweep_list_counts ? c->sweep_list_counts + (size_t)(c->NI - 1) * c->sweep_list_tiles : nullptr;
 	d.reuse_costs = c->reuse_costs; d.reuse_keys = c->reuse_keys; d.reuse_hdr = c->reuse_hdr; d.reuse_epoch = c->reuse_epoch;
 	d.planes = c->planes; d.planes_snap = c->planes_snap; d.costs = c->costs; d.costs_snap = c->costs_snap;
 	d.selected_views = c->selected_views; d.view_weight = c->view_weight; d.weak_info = c->weak_info;

@@ -154,6 +154,11 @@ struct Dev {
 	int sweep_px0;             // sweep passes in bands of rows (a context told to keep sweep_cost small): sweep_cost holds the pixels from this linear index on,
 	int sweep_row0, sweep_row1;   // and the decision passes of a band take the rows [row0, row1) (row1 == 0: the whole image)
 	int sweep_all_slots;       // DVP_SWEEP_ALL_SLOTS: DepthToWeak also evaluates the two end slots no decision reads (dvp_forms.hpp: sweep_slot_read)
+	// the evaluation passes' per-view (pixel, view) lists (dvp_sweep_list.hpp), or null (the evaluation walks tiles)
+	uint32_t* sweep_list;      // [S][sweep_list_cap]: (y << 16) | x of the pixels that take part in the stage being evaluated, in tile order
+	int* sweep_list_n;         // [S]: entries of each view's list (the scan's totals; read on the device only)
+	int* sweep_list_counts;    // [S][tiles]: entries per (view, tile), then their exclusive scan
+	int sweep_list_cap;        // entries a view's list has room for: the pixels of the image, or of a band of rows
 	int half_w;
 	uint32_t* edge_bits;       // the edge map as 32x32-pixel bit tiles (128 B each), see edge_bit()
 	int edge_tiles_x;

@@ -617,6 +617,18 @@ static void ensure_sweep_buffers(dvp_ctx* c) {
 	alloc_group_or_fall_back(c, { areq(&c->sweep_rec, 2 * L * sizeof(f4)), areq(&c->sweep_pc, 61 * L * sizeof(float)), areq(&c->sweep_cost, sweep_cost_floats(band_px, c->NI - 1) * sizeof(float)) },
 		"DVP_TEST_SWEEP_ALLOC_FAIL", &c->sweep_fits, "dvp: no room for the view-compacted DepthToWeak's cost buffer (%.1f GB); using the fused kernel\n", (double)(c->NI - 1) * kSweepFields * L * 4 / 1e9);
 }
+// The evaluation launches' per-view lists: 4 bytes per (pixel, view) of the image or of a band (0.9 GB at 6208x4128, S = 9; one
+// buffer: a stage's lists are consumed before the next stage's are built, in stream order), the counts per (view, tile) and the
+// lengths.  A context that cannot have them evaluates tile by tile.
+static void ensure_sweep_list_buffers(dvp_ctx* c) {
+	if (c->sweep_list || !c->sweep_cost || !c->sw.sweep_list || !c->sweep_list_fits) return;
+	const size_t S = (size_t)c->NI - 1;
+	const int band_rows = c->sweep_band_rows > 0 ? c->sweep_band_rows : c->H;
+	c->sweep_list_cap = band_rows * c->W;
+	c->sweep_list_tiles = ((c->W + 63) / 64) * ((band_rows + kSweepRows - 1) / kSweepRows);
+	alloc_group_or_fall_back(c, { areq(&c->sweep_list, S * (size_t)c->sweep_list_cap * sizeof(uint32_t)), areq(&c->sweep_list_counts, (S * c->sweep_list_tiles + (S + 2) / 3 * 3) * sizeof(int)) },
+		"DVP_TEST_SWEEP_LIST_ALLOC_FAIL", &c->sweep_list_fits, "dvp: no room for the sweep passes' (pixel, view) lists (%.2f GB); evaluating tile by tile\n", (double)S * c->sweep_list_cap * 4 / 1e9);
+}
 
 // ---- launches ---------------------------------------------------------------------------------
 // Which kernels a launch site runs is decided by dvp_forms.hpp; the functions below issue them.
@@ -771,7 +783,10 @@ static int launch_sweeps(dvp_ctx* c, const LaunchGeom& g, const LaunchArgs& a, b
 	const dim3 grid(g.grid()), block(256);
 	if (sweep_form(c->sw, fused, c->d.params, c->sweep_fits, c->W, c->H).kernel == SWEEP_PASSES) ensure_sweep_buffers(c);
 	const SweepForm f = sweep_form(c->sw, fused, c->d.params, c->sweep_fits, c->W, c->H);
+	if (sweep_eval_form(c->sw, f, c->sweep_list_fits) == SWEEP_EVAL_LISTS) ensure_sweep_list_buffers(c);
 	if (f.kernel == SWEEP_PASSES) {
+		const bool lists = sweep_eval_form(c->sw, f, c->sweep_list_fits) == SWEEP_EVAL_LISTS;
+		const auto list_eval = c->sw.sweep_all_slots ? DVP_PICK(dvp_sweep_eval_list, _all) : DVP_PICK(dvp_sweep_eval_list, );
 		LaunchArgs s0 = a, s1 = a, sb = a;
 		s0.iter = 0; s1.iter = 1; sb.iter = kSweepBorderOnly;
 		const int etx = (c->W + 63) / 64, ety = (c->H + kSweepRows - 1) / kSweepRows;
@@ -793,6 +808,23 @@ static int launch_sweeps(dvp_ctx* c, const LaunchGeom& g, const LaunchArgs& a, b
 				b0.rows = b1.rows = row0 / kSweepRows;
 				b0.tiles = b1.tiles = etx * bty;
 				bgrid = dim3((unsigned)(etx * bty), (unsigned)(c->NI - 1));
+			}
+			if (lists) {
+				// per stage: the band's lists (counts per (view, tile), a scan per view — dvp_scan3 takes three — and the scatter), then
+				// the evaluation over the upper bound of the lists' lengths, which stay on the device
+				const int S = c->NI - 1, T = b0.tiles;
+				const dim3 tgrid((unsigned)((T + 3) / 4)), lgrid((unsigned)sweep_list_grid(c->sweep_list_cap, kSweepListRounds), (unsigned)S);
+				for (int stage = 0; stage < (f.second_eval ? 2 : 1); ++stage) {
+					const LaunchArgs& bs = stage ? b1 : b0;
+					hipLaunchKernelGGL(dvp_sweep_list_counts, tgrid, block, 0, c->stream, db, bs);
+					for (int v0 = 0; v0 < S; v0 += 3)
+						hipLaunchKernelGGL(dvp_scan3, dim3(3), dim3(1024), 0, c->stream, db.sweep_list_counts, v0 * T, std::min(v0 + 1, S) * T, std::min(v0 + 2, S) * T, std::min(v0 + 3, S) * T, db.sweep_list_n + v0);
+					hipLaunchKernelGGL(dvp_sweep_list_fill, tgrid, block, 0, c->stream, db, bs);
+					hipLaunchKernelGGL(list_eval, lgrid, dim3(64), 0, c->stream, db, bs);
+					if (stage == 0) hipLaunchKernelGGL(dvp_sweep_decide1, grid, block, 0, c->stream, db, a);
+				}
+				hipLaunchKernelGGL(dvp_sweep_decide2, grid, block, 0, c->stream, db, a);
+				continue;
 			}
 			const auto eval = c->sw.sweep_all_slots ? DVP_PICK(dvp_sweep_eval, _all) : DVP_PICK(dvp_sweep_eval, );
 			hipLaunchKernelGGL(eval, bgrid, dim3(64), 0, c->stream, db, b0);
@@ -899,7 +931,7 @@ static int ensure_edge_buffers(dvp_ctx* c, int slots) {
 int dvp_ctx_reserve(dvp_ctx* c, int weak_pixels, int flags) {
 	if (set_device(c)) return 1;
 	if (flags & 1) ensure_strong_split_buffers(c);
-	if (flags & 2) ensure_sweep_buffers(c);
+	if (flags & 2) { ensure_sweep_buffers(c); ensure_sweep_list_buffers(c); }
 	if ((flags & 4) && !c->sw.no_images8 && !c->sw.no_images16 && ensure_images16(c)) return 1;
 	if ((flags & 8) && ensure_edge_buffers(c, 2)) return 1;
 	if ((flags & 16) && dvpvc::scratch_reserve(c->vc, c->L, c->NI - 1)) { c->error = "dvp_ctx_reserve: out of device memory (view clean-up)"; return 1; }

@@ -45,6 +45,7 @@ struct FormSwitches {   // unset defaults; =0 / =1 are atoi(e) != 0, "(present)"
 	bool sweep_split = true, sweep_force = false;   // DVP_SWEEP_SPLIT=0: the fused per-pixel kernel; =2: the passes also without the geometric term
 	bool sweep_all_slots = false; // DVP_SWEEP_ALL_SLOTS=1: the sweep site also evaluates the two end slots no decision reads (sweep_slot_read; A/B)
 	double sweep_band_gb = 0.0;   // DVP_SWEEP_BAND_GB=g: sweep_cost holds a band of rows of at most g GB (0: the whole image)
+	bool sweep_list = true;       // DVP_SWEEP_LIST=0: the passes' evaluation launches walk tiles (dvp_sweep_eval) instead of per-view lists (sweep_eval_form; A/B)
 	bool anchor_tab_off = false;  // DVP_WEAK_ANCHOR_TAB=0: the weak update forms the reference side per item
 	bool gn_wave = false, ransac_wave = false;      // DVP_GN_WAVE=1 / DVP_RANSAC_WAVE=1: a wave per WEAK pixel (measured no faster)
 	int cand_mask_mode = -1;      // DVP_CAND_MASK=1 / 0 forces masked / full candidates
@@ -64,6 +65,7 @@ inline FormSwitches read_form_switches() {
 	if (const char* e = getenv("DVP_SWEEP_SPLIT")) { s.sweep_split = atoi(e) != 0; s.sweep_force = atoi(e) == 2; }
 	s.sweep_all_slots = env_flag("DVP_SWEEP_ALL_SLOTS", false);
 	if (const char* e = getenv("DVP_SWEEP_BAND_GB")) s.sweep_band_gb = atof(e);
+	s.sweep_list = env_flag("DVP_SWEEP_LIST", true);
 	s.anchor_tab_off = !env_flag("DVP_WEAK_ANCHOR_TAB", true);
 	s.gn_wave = env_flag("DVP_GN_WAVE", false);
 	s.ransac_wave = env_flag("DVP_RANSAC_WAVE", false);
@@ -137,6 +139,14 @@ struct SweepForm {
 inline SweepForm sweep_form(const FormSwitches& s, bool fused, const DvpParams& P, bool sweep_fits, int W, int H) {
 	if (fused && s.sweep_split && sweep_fits && (P.geom_consistency || s.sweep_force)) return { SWEEP_PASSES, sweep_window(P) < 30, W >= 12 && H >= 12 };
 	return { fused ? SWEEP_FUSED : SWEEP_SEPARATE, false, false };
+}
+// The evaluation launches of the passes: from per-view (pixel, view) lists, a wave = consecutive rounds of one view's list
+// (dvp_sweep_eval_list, dvp_sweep_list.hpp), or tile by tile with the list of a tile in LDS (dvp_sweep_eval).  Same evaluations, same
+// bits; the lists leave only the last round of a view part-empty instead of the last round of every (tile, view).
+// list_fits: the list buffers could be had (dvp_ctx::sweep_list_fits).
+enum SweepEval { SWEEP_EVAL_TILES, SWEEP_EVAL_LISTS };
+inline SweepEval sweep_eval_form(const FormSwitches& s, const SweepForm& f, bool list_fits) {
+	return (f.kernel == SWEEP_PASSES && s.sweep_list && list_fits) ? SWEEP_EVAL_LISTS : SWEEP_EVAL_TILES;
 }
 // rows of a band of the passes' cost buffer (a multiple of the evaluation tile's rows); 0 = the whole image
 inline int sweep_band_rows(const FormSwitches& s, int W, int H, int S) {

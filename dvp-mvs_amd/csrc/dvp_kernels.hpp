@@ -272,10 +272,11 @@ __device__ __forceinline__ void sweep_light_body(const Dev& d, const LaunchArgs&
 extern "C" __global__ void __launch_bounds__(256) dvp_sweep_prepare(const Dev d, const LaunchArgs a) { sweep_light_body<0>(d, a); }
 extern "C" __global__ void __launch_bounds__(256) dvp_sweep_decide1(const Dev d, const LaunchArgs a) { sweep_light_body<1>(d, a); }
 extern "C" __global__ void __launch_bounds__(256) dvp_sweep_decide2(const Dev d, const LaunchArgs a) { sweep_light_body<2>(d, a); }
-// Evaluation pass: workgroup = one wave = one 64 x 4 tile of the launch map, grid.y = source view (dispatched view after view:
-// the workgroups in flight gather from ONE image).  The tile's pixels that take part — they selected the view with a weight
-// > 0 — are compacted into a list in LDS (ballot ranks, row after row) and taken 64 per round, so that every lane of a round
-// evaluates (71 % of the pixels select a given view at cfg3: 2.8 rounds of 64 instead of 4 rows with 29 % of the lanes idle).
+// Evaluation pass, tile form (DVP_SWEEP_LIST=0, or no room for the lists below): workgroup = one wave = one 64 x kSweepRows (14)
+// tile of the launch map, grid.y = source view (dispatched view after view: the workgroups in flight gather from ONE image).  The
+// tile's pixels that take part — they selected the view with a weight > 0 — are compacted into a list in LDS (ballot ranks, row
+// after row) and taken 64 per round, so that every lane of a round but the tile's last evaluates (71 % of the pixels select a given
+// view at cfg3: 9.9 rounds of 64 instead of 14 rows with 29 % of the lanes idle).
 // a.iter = stage (0: central window + LocalRefine's extra slot, 1: the rest of the line for pixels with a central peak).
 // (a tile is 64 x kSweepRows pixels: dvp_forms.hpp)
 template <int SMP, bool ALL>
@@ -354,6 +355,87 @@ extern "C" __global__ void __launch_bounds__(64, DVP_LB_HEAVY) dvp_sweep_eval_ex
 // DVP_SWEEP_ALL_SLOTS=1 (A/B): the same with the two end slots of the line, which no decision reads (dvp_forms.hpp: sweep_slot_read)
 extern "C" __global__ void __launch_bounds__(64, DVP_LB_HEAVY) dvp_sweep_eval_all(const Dev d, const LaunchArgs a) { sweep_eval_body<0, true>(d, a); }
 extern "C" __global__ void __launch_bounds__(64, DVP_LB_HEAVY) dvp_sweep_eval_exact_all(const Dev d, const LaunchArgs a) { sweep_eval_body<1, true>(d, a); }
+
+// ---- the same evaluations from per-view (pixel, view) lists (DVP_SWEEP_LIST; dvp_sweep_list.hpp) ----
+// The lists of stage a.iter over the launch's tiles (a.tiles_x, a.tiles, a.rows as for dvp_sweep_eval): one wave per tile, lane =
+// column of the tile; lane v < S keeps view v's running count / offset.
+extern "C" __global__ void __launch_bounds__(256) dvp_sweep_list_counts(const Dev d, const LaunchArgs a) {
+	const int lane = threadIdx.x & 63;
+	const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
+	if (t >= a.tiles) return;
+	const int S = d.params.num_images - 1;
+	int tx, ty;
+	sweep_list_tile(t, a.tiles_x, a.tiles / a.tiles_x, &tx, &ty);
+	ty += a.rows;
+	const int x = tx * 64 + lane;
+	int cnt = 0;
+	for (int r = 0; r < kSweepRows; ++r) {
+		const int y = ty * kSweepRows + r;
+		const uint32_t m = (x < d.width && y < d.height) ? sweep_go_mask(d, x + y * d.width, a.iter) : 0u;
+		if (__ballot(m != 0) == 0) continue;
+		for (int v = 0; v < S; ++v) {
+			const int k = __popcll(__ballot((m >> v) & 1u));
+			if (lane == v) cnt += k;
+		}
+	}
+	if (lane < S) d.sweep_list_counts[(size_t)lane * a.tiles + t] = cnt;
+}
+// (between the two: dvp_scan3 over each view's counts; its totals are the lists' lengths, d.sweep_list_n)
+extern "C" __global__ void __launch_bounds__(256) dvp_sweep_list_fill(const Dev d, const LaunchArgs a) {
+	const int lane = threadIdx.x & 63;
+	const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
+	if (t >= a.tiles) return;
+	const int S = d.params.num_images - 1;
+	int tx, ty;
+	sweep_list_tile(t, a.tiles_x, a.tiles / a.tiles_x, &tx, &ty);
+	ty += a.rows;
+	const int x = tx * 64 + lane;
+	int off = lane < S ? d.sweep_list_counts[(size_t)lane * a.tiles + t] : 0;
+	for (int r = 0; r < kSweepRows; ++r) {
+		const int y = ty * kSweepRows + r;
+		const uint32_t m = (x < d.width && y < d.height) ? sweep_go_mask(d, x + y * d.width, a.iter) : 0u;
+		if (__ballot(m != 0) == 0) continue;
+		for (int v = 0; v < S; ++v) {
+			const unsigned long long b = __ballot((m >> v) & 1u);
+			sweep_list_put(d.sweep_list + (size_t)v * d.sweep_list_cap, __shfl(off, v, 64), b, lane, x, y);
+			if (lane == v) off += __popcll(b);
+		}
+	}
+}
+// Evaluation pass from the lists: workgroup = one wave = R consecutive rounds of 64 entries of the list of view blockIdx.y (a chunk:
+// sweep_list_chunk).  The grid is the upper bound over the list's room; the length stays on the device, and a workgroup past the
+// end leaves after one scalar load.  Only the last round of a view's list can be part-empty.  a.iter = stage, as above.
+template <int SMP, bool ALL, int R>
+__device__ __forceinline__ void sweep_eval_list_body(const Dev& d, const LaunchArgs& a) {
+	const int lane = threadIdx.x;
+	const int v = blockIdx.y;
+	__shared__ f2 lds_tab[kTaps * kTaps * 64];
+	__shared__ DvpCamera cams[2];                // reference camera, camera of the launch's view
+	const int n = d.sweep_list_n[v];
+	const int chunk = sweep_list_chunk((int)blockIdx.x, n, R);
+	if (chunk < 0) return;
+	const PatchTab tab{&lds_tab[lane], 64};
+	static_assert(sizeof(DvpCamera) == 112, "28 dwords");
+	if (lane < 56) {
+		const int which = lane >= 28 ? 1 : 0;
+		reinterpret_cast<uint32_t*>(&cams[which])[lane - 28 * which] = reinterpret_cast<const uint32_t*>(d.cameras + (which ? v + 1 : 0))[lane - 28 * which];
+	}
+	__syncthreads();
+	const uint32_t* list = d.sweep_list + (size_t)v * d.sweep_list_cap;
+	const int first = chunk * (64 * R), end = DVP_MIN(n, first + 64 * R);
+	unsigned long long cnt = 0;
+	for (int i0 = first; i0 < end; i0 += 64) {
+		if (i0 + lane < end) {
+			const uint32_t e = list[i0 + lane];
+			sweep_eval_px<SMP, ALL>(d, sweep_list_x(e), sweep_list_y(e), v, a.iter, tab, d.eval_counter ? &cnt : nullptr, cams);
+		}
+	}
+	if (d.eval_counter && cnt) atomicAdd(d.eval_counter, cnt);
+}
+extern "C" __global__ void __launch_bounds__(64, DVP_LB_HEAVY) dvp_sweep_eval_list(const Dev d, const LaunchArgs a) { sweep_eval_list_body<0, false, kSweepListRounds>(d, a); }
+extern "C" __global__ void __launch_bounds__(64, DVP_LB_HEAVY) dvp_sweep_eval_list_exact(const Dev d, const LaunchArgs a) { sweep_eval_list_body<1, false, kSweepListRounds>(d, a); }
+extern "C" __global__ void __launch_bounds__(64, DVP_LB_HEAVY) dvp_sweep_eval_list_all(const Dev d, const LaunchArgs a) { sweep_eval_list_body<0, true, kSweepListRounds>(d, a); }
+extern "C" __global__ void __launch_bounds__(64, DVP_LB_HEAVY) dvp_sweep_eval_list_exact_all(const Dev d, const LaunchArgs a) { sweep_eval_list_body<1, true, kSweepListRounds>(d, a); }
 
 // the weak-path launch sites: one lane per entry of the WEAK-pixel list
 DVP_KERNEL_LIST(dvp_find_nearest_strong_list, DVP_ST_FIND_NEAREST_STRONG, 1)

@@ -8,6 +8,7 @@
 #include "dvp_weak_wave.hpp"
 #include "dvp_weak_phased.hpp"
 #include "dvp_sweep.hpp"
+#include "dvp_sweep_list.hpp"
 #include <vector>
 #include <cmath>
 

@@ -253,7 +253,8 @@ DVP_HD void local_refine_px(const Dev& d, int px, int py, PatchTab tab, unsigned
 // cost line, the weights and the peak logic sit in the evaluator's register budget.  Same evaluations, same bits, as passes:
 //   sweep_prepare_px   per pixel: validity, (camera-frame normal, depth), mean baseline, disparity, weight sum -> sweep_rec
 //   sweep_eval_px      per (pixel, source view): the planes of one stage against ONE view — launched view by view over the
-//                      pixels that selected the view with a weight > 0 (compacted tile by tile: dvp_sweep_eval), nothing live
+//                      pixels that selected the view with a weight > 0 (compacted into one list per view: dvp_sweep_eval_list,
+//                      dvp_sweep_list.hpp; or tile by tile, DVP_SWEEP_LIST=0: dvp_sweep_eval), nothing live
 //                      but the evaluator -> sweep_cost.  Stage 0: the central window (-cw..cw) and LocalRefine's extra slot
 //                      (the current depth); stage 1: the rest of the line, only for pixels whose window holds a cost peak
 //                      (the others are WEAK whatever the rest says: exact, see depth_to_weak_px).  Its end slots -30 and +30 are

@@ -19,38 +19,19 @@ static uint64_t g_seed = 0x5eed5eedULL;
 void APD::SetDevice(int device) { g_device = device; }
 int APD::GetDevice() { return g_device; }   // cudaSetDevice(argv[2]), main.cpp:430-434
 void APD::SetSeed(uint64_t seed) { g_seed = seed; }      // the reference seeds with clock64() (APD.cu:1270)
-static bool g_use_label_files = false;
-void APD::SetUseLabelFiles(bool on) { g_use_label_files = on; }
-static bool g_edges_on_device = false;
-void APD::SetEdgesOnDevice(bool on) { g_edges_on_device = on; }
-bool APD::EdgesOnDevice() { return g_edges_on_device; }
-static bool g_cleanup_on_device = false;
-void APD::SetCleanupOnDevice(bool on) { g_cleanup_on_device = on; }
-bool APD::CleanupOnDevice() { return g_cleanup_on_device; }
-static bool g_labels_on_device = false;
-void APD::SetLabelsOnDevice(bool on) { g_labels_on_device = on; }
-bool APD::LabelsOnDevice() { return g_labels_on_device; }
-static bool g_prior_on_device = false;
-void APD::SetPriorOnDevice(bool on) { g_prior_on_device = on; }
-bool APD::PriorOnDevice() { return g_prior_on_device; }
-static bool g_images_on_device = false;
-void APD::SetImagesOnDevice(bool on) { g_images_on_device = on; }
-bool APD::ImagesOnDevice() { return g_images_on_device; }
-// DVP_HOST_TIMING=1: wall time of the parts of the host steps (tools/e2e_timing.sh folds them per pass)
-namespace {
-struct HostLap {
-	std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
-	const bool on = std::getenv("DVP_HOST_TIMING") != nullptr;
-	void operator()(const char* what) {
-		if (!on) return;
-		const auto now = std::chrono::steady_clock::now();
-		ViewLog() << "  [host]   . " << what << ": " << std::chrono::duration_cast<std::chrono::microseconds>(now - t).count() / 1000.0 << " ms" << std::endl;
-		t = now;
-	}
-};
+static RunConfig g_run;   // written once (SetRunConfig), before any thread or APD exists
+void SetRunConfig(const RunConfig& config) { g_run = config; }
+const RunConfig& Run() { return g_run; }
+bool HostTiming() {
+	static const bool on = std::getenv("DVP_HOST_TIMING") != nullptr;
+	return on;
 }
-static bool g_device_rescale = true;
-void APD::SetDeviceRescale(bool on) { g_device_rescale = on; }
+void Lap::operator()(const std::string& what) {
+	if (!HostTiming()) return;
+	const auto now = std::chrono::steady_clock::now();
+	ViewLog() << prefix << what << ": " << std::chrono::duration_cast<std::chrono::microseconds>(now - t).count() / 1000.0 << " ms" << std::endl;
+	t = now;
+}
 
 APD::APD(const Problem& problem) {   // APD.cpp:984-987
 	params_host = problem.params;
@@ -192,7 +173,7 @@ void APD::PrewarmContext(int w, int h, int ni, int scale_size) {
 			const long long per_px = 1408ll * (ni - 1) + 544 + 32ll * (ni - 1);
 			const long long budget = (long long)w * h <= 8000000ll ? 48000000000ll : 24000000000ll;
 			const long long room = std::min<long long>((long long)w * h * 9 / 10, budget / per_px);
-			(void)dvp_ctx_reserve(c, (int)std::min<long long>(room, 2000000000ll), (scale_size > 1 ? 7 : 3) | (g_edges_on_device ? 8 : 0) | (g_cleanup_on_device ? 16 : 0));   // (+ the edge prior's and the view clean-up's scratch)
+			(void)dvp_ctx_reserve(c, (int)std::min<long long>(room, 2000000000ll), (scale_size > 1 ? 7 : 3) | (Run().edges_on_device ? 8 : 0) | (Run().cleanup_on_device ? 16 : 0));   // (+ the edge prior's and the view clean-up's scratch)
 		}
 		g_prewarm.ctx = c;
 	});
@@ -344,7 +325,7 @@ bool APD::StoreDecoded(int image_id, const path& file, int* width, int* height) 
 }
 static size_t g_image_store_pending = 0;   // bytes of the puts under way in PutJpegInStore (g_image_store_mutex)
 bool APD::PutJpegInStore(const path& file, const std::vector<uint8_t>& bytes, Mat* gray) {
-	if (!g_images_on_device || file.parent_path().filename() != "images") return false;
+	if (!Run().images_on_device || file.parent_path().filename() != "images") return false;
 	const int id = image_id_of(file);
 	int w = 0, h = 0;
 	if (id < 0 || dvp_jpeg_decode(g_device, bytes.data(), (long long)bytes.size(), 1, nullptr, 0, &w, &h) != 0) return false;   // (a bad file: the caller's decode reports it)
@@ -390,7 +371,7 @@ void APD::PrefetchDecoded(const std::vector<path>& files) {
 					if (g_decoded_full) break;
 				}
 				(void)APD::DecodedGray((*queue)[i]);
-				if (g_images_on_device) {   // ... and resident on the device from now on, every level is made from it there
+				if (Run().images_on_device) {   // ... and resident on the device from now on, every level is made from it there
 					const int id = image_id_of((*queue)[i]);
 					if (id >= 0) (void)APD::StoreDecoded(id, (*queue)[i]);
 				}
@@ -497,7 +478,7 @@ APD::~APD() {                        // APD.cpp:989-1043
 
 // APD.cpp:1045-1495 (the Depth-Anything prior block :1210-1424 lives in prior.cpp)
 void APD::InuputInitialization() {
-	HostLap lap;
+	Lap lap{ "  [host]   . " };
 	images.clear();
 	cameras.clear();
 	path image_folder = problem.dense_folder / path("images");
@@ -508,7 +489,7 @@ void APD::InuputInitialization() {
 	std::vector<std::pair<int, int>> orig_sizes;    // (cols, rows) before scaling, per image
 	std::vector<std::pair<int, int>> level_sizes;   // ... and at this pass' level
 	images_on_device = false;
-	if (g_images_on_device) {   // every image of the view in the store: the levels are made on the device, no float image here
+	if (Run().images_on_device) {   // every image of the view in the store: the levels are made on the device, no float image here
 		std::string reason;
 		int rw = 0, rh = 0;
 		if (problem.src_image_ids.size() + 1 > MAX_IMAGES) reason = "too many images";
@@ -634,7 +615,7 @@ void APD::InuputInitialization() {
 		// level's in the first pass of a finer one — and the engine up-samples them, assembles the planes and applies the
 		// radius rule (CudaSpaceInitialization; at equal size the rescale is the identity, as RescaleMatToTargetSize's early
 		// return is); the depth / normal / selected-views maps below have to agree in size.
-		coarse_state = g_device_rescale && params_host.state != FIRST_INIT && !weak_info_host.empty();
+		coarse_state = Run().device_rescale && params_host.state != FIRST_INIT && !weak_info_host.empty();
 		if (coarse_state) {
 			coarse_weak = weak_info_host;
 			weak_info_host = Mat(height, width, CV_8UC1);
@@ -658,7 +639,7 @@ void APD::InuputInitialization() {
 	// sfm/<id>.txt, APD.cpp:1210-1424; host/prior.cpp).  Without those inputs the planes stay zero
 	// (.w out of range) and RandomInitialization draws random planes (APD.cu:1289-1291).
 	prior_kept = false;
-	if (params_host.state == FIRST_INIT && g_prior_on_device) {   // the engine makes the planes (CudaSpaceInitialization): keep the inputs
+	if (params_host.state == FIRST_INIT && Run().prior_on_device) {   // the engine makes the planes (CudaSpaceInitialization): keep the inputs
 		prior_kept = ReadPlanePriorInputs(problem, prior_dep, prior_xy, prior_xyz, prior_cam);
 		if (!prior_kept) ViewLog() << "No dep/ + sfm/ prior: random plane initialisation\n";
 		lap("plane prior (inputs read, planes made on the device)");
@@ -677,7 +658,7 @@ void APD::InuputInitialization() {
 		const bool fits = depth.cols == width && depth.rows == height && normal.cols == width && normal.rows == height;
 		{   // device rescale: all maps of the previous pass at ONE size (else the host flow below)
 			const bool same = normal.cols == depth.cols && normal.rows == depth.rows && selected_views_host.cols == depth.cols && selected_views_host.rows == depth.rows;
-			const bool can = g_device_rescale && same && (params_host.use_APD ? (coarse_state && coarse_weak.cols == depth.cols && coarse_weak.rows == depth.rows) : true);
+			const bool can = Run().device_rescale && same && (params_host.use_APD ? (coarse_state && coarse_weak.cols == depth.cols && coarse_weak.rows == depth.rows) : true);
 			if (coarse_state && !can) {   // the pixel states were kept back for nothing
 				weak_info_host = coarse_weak;
 				coarse_weak = Mat();
@@ -763,7 +744,7 @@ void APD::SupportInitialization() {
 	if (problem.params.use_edge || problem.params.use_limit) {
 		path edge_path = problem.result_folder / path("edges_" + std::to_string(scale) + ".dmb");
 		// (the passes GetProblemEdges runs before: the photometric pass of a level, main.cpp:480)
-		if (g_edges_on_device && problem.params.use_edge && !problem.params.geom_consistency && !ResultExists(edge_path)) {
+		if (Run().edges_on_device && problem.params.use_edge && !problem.params.geom_consistency && !ResultExists(edge_path)) {
 			ExpectResult(edge_path);
 			edge_on_device = true;
 			edge_file = edge_path;
@@ -787,7 +768,7 @@ void APD::SupportInitialization() {
 			RescaleMatToTargetSize<float>(ref_dep, tmp, width, height);
 			label_host = Mat(height, width, CV_32SC1);
 			std::memcpy(label_host.data, tmp.data, (size_t)width * height * 4);   // float bits reinterpreted, as the reference does
-		} else if (g_use_label_files) {   // the commented-out load of APD.cpp:1630-1633
+		} else if (Run().use_label_files) {   // the commented-out load of APD.cpp:1630-1633
 			Mat lab;
 			if (LoadResult(problem.result_folder / path("labels_" + std::to_string(scale) + ".dmb"), lab) && lab.type() == CV_32SC1) {
 				if (lab.cols != width || lab.rows != height) RescaleMatToTargetSize<int>(lab, lab, width, height);
@@ -825,7 +806,7 @@ void APD::SupportInitialization() {
 
 // APD.cpp:1497-1613: every cudaMalloc/cudaMemcpy/texture creation becomes one C-ABI upload
 void APD::CudaSpaceInitialization() {
-	HostLap lap;
+	Lap lap{ "  [host]   . " };
 	ctx_device = g_device;
 	if ((ctx = take_pooled(g_device, width, height, num_images)) != nullptr) {
 		DVP_SAFE_CALL(ctx, dvp_reset_state(ctx));
@@ -894,7 +875,7 @@ void APD::CudaSpaceInitialization() {
 		planes_on_device = status == 0;
 		if (planes_on_device) ViewLog() << "Plane prior from dep/ and sfm/\n";
 		else ViewLog() << "No dep/ + sfm/ prior: random plane initialisation\n";
-		if (planes_on_device && std::getenv("DVP_HOST_TIMING")) {
+		if (planes_on_device && HostTiming()) {
 			double ms[3] = { 0, 0, 0 };
 			long long counts[2] = { 0, 0 };
 			DVP_SAFE_CALL(ctx, dvp_plane_prior_timings(ctx, ms, counts));
@@ -950,7 +931,7 @@ std::function<void()> APD::RunPatchMatchAndStageMaps(Mat& depth, Mat& normal, fl
 	normal = Mat(height, width, CV_32FC3);
 	// (a pooled context keeps the last view's setting: set it for every view)
 	const int region_side = 8 / problem.scale_size;
-	DVP_SAFE_CALL(ctx, dvp_set_view_cleanup(ctx, g_cleanup_on_device ? 1 : 0, (int)problem.src_image_ids.size(), 20 * region_side * region_side));
+	DVP_SAFE_CALL(ctx, dvp_set_view_cleanup(ctx, Run().cleanup_on_device ? 1 : 0, (int)problem.src_image_ids.size(), 20 * region_side * region_side));
 	DVP_SAFE_CALL(ctx, dvp_download_maps_begin(ctx, depth_device_copy));
 	DVP_SAFE_CALL(ctx, dvp_get_timings(ctx, &timings));
 	// (the Mats share their buffers with the copies held here: they stay alive with the function)

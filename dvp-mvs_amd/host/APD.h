@@ -14,9 +14,74 @@
 #define M_PI 3.14159265358979323846
 #endif
 
+// ---- the run's configuration: set once by the driver before any thread or APD exists, read everywhere else through Run() --------
+struct RunConfig {
+	// The shipped reference writes labels_<s>.dmb but never loads it (the load is commented out, APD.cpp:1630-1633): its label map
+	// stays zero unless MVS4/<id>.dmb needs rescaling.  true (`apd --labels`): load labels_<s>.dmb in SupportInitialization.
+	bool use_label_files = false;
+	// `apd --edges-on gpu`.  true: a view whose edges_<s>.dmb neither exists nor is cached nor announced does not wait for a
+	// helper thread's EdgeSegment: SupportInitialization announces the file, CudaSpaceInitialization has the engine compute the
+	// map from the context's image 0 straight into the context's edge buffer (dvp_edge_map_begin), and the function
+	// TakeEdgeFetch returns copies it to the host, writes rawedge_<s>.jpg if previews are on and publishes the file (any
+	// thread, after the APD is gone too; its destructor runs it if nobody took it).  Same bytes as the host's map.
+	// false: GetProblemEdges makes the file (edges.cpp).
+	bool edges_on_device = false;
+	// `apd --cleanup-on gpu`.  true: RunPatchMatchAndStageMaps has the engine run ProcessProblem's visibility-mask clean-up
+	// (main.cpp:311-363) on the staged selected-view words (dvp_set_view_cleanup with the view's source count and
+	// min_region = 20 * (8 / scale_size)^2): the words its fetch returns are final, and the driver's background job skips
+	// CleanSelectedViewsOnHost.  Flows that do not stage maps on the device keep the host loop.  Same words either way.
+	bool cleanup_on_device = false;
+	// `apd --labels-on gpu`.  true: GetProblemEdges makes labels_<s>.dmb with a dvp_labels job on the driver's device
+	// (include/dvp_mvs.h: resizes, Roberts cross, both component passes and the numbering on the device, the Hough lines on the
+	// host in between) instead of the helper thread's LabelSegment — one job per calling thread, kept for the thread's life.
+	// Announcing, publishing, file names and use_label_files are untouched.  Same values.
+	bool labels_on_device = false;
+	// `apd --prior-on gpu`.  true: the FIRST_INIT plane prior (dep/<id>.dmb + sfm/<id>.txt, APD.cpp:1210-1424) is made by the engine
+	// (include/dvp_mvs.h dvp_plane_prior: the points and the triangulation on the host, the sweep, the rate map, the rescale and
+	// the planes on the device, into the context's planes): InuputInitialization only reads the three files and keeps them,
+	// CudaSpaceInitialization calls the engine after the cameras' upload and uploads no planes.  Same planes, same two log lines.
+	bool prior_on_device = false;
+	// `apd --images-on gpu`.  true: the process keeps the job's decoded 8-bit images in one dvp_images store on the driver's device
+	// (put by the decode prefetch threads or at a view's first use, within DVP_RESIDENT_IMAGES_GB), and a view whose images are all
+	// there builds no host float image: InuputInitialization takes the sizes from the store and the std::round(n * factor) rule,
+	// CudaSpaceInitialization has the engine make the level of every image from the bytes (dvp_upload_images_u8: padding /
+	// cropping to the reference's size, cv::resize(INTER_LINEAR)).  A view with an image missing from the store takes the host
+	// path, whole.  Either way the view logs one line, "Images: levels made on the device" or "Images: host path (<reason>)".
+	// Same texels, same dvp_image_format.
+	bool images_on_device = false;
+	// `apd --decode-on gpu`.  true: ReadImageGray and ReadImageColor hand a .jpg to the engine (include/dvp_mvs.h dvp_jpeg_decode,
+	// dvp_jpeg_decode_into_store): the entropy decode stays on the host, the inverse DCT and the colour conversion run on APD::GetDevice().
+	// Same bytes; one line "Image decode: on the device (<file>, grey|colour)" per file (grey, into the image store: with images_on_device); a failure stops the job.
+	bool decode_on_device = false;
+	// true: a pass that starts from maps of another size (REFINE_INIT on a finer pyramid level) hands them to the engine at their
+	// own size and RescaleMatToTargetSize runs there (dvp_upload_state_rescaled); false (`apd --sync-io` / `--host-rescale`): the
+	// five host-side rescales + the plane assembly of the reference's flow (APD.cpp:1176-1180, 1440-1456, 1656-1659).  Same maps either way.
+	bool device_rescale = true;
+	// true: ProcessProblem's unpack loop is done by the engine, and the maps travel to the host in the view's background job while
+	// the context is already on the next view (25 B per pixel: 27 ms of the 34 ms a full-size view spent outside its kernels);
+	// false (`apd --sync-io` / `--host-rescale`): planes are downloaded and unpacked on the host.
+	bool device_maps = true;
+	bool strong_wide = false;   // `apd --strong-wide on`: a view with more than 16 sources logs the form its strong updates took
+	// The reference writes the ACMM-format maps of a view — depths_geom.dmb + normals.dmb, what ACMM-style fusers read — when
+	// `problem.iteration == 15` (main.cpp:378-385): the last pass of its default schedule (4 levels x (1 + 3) passes).  Here: at
+	// that literal index too, and at this one, the last pass of whatever plan the driver was given (--min-scale / --passes shorten it).
+	int final_iteration = 15;
+};
+void SetRunConfig(const RunConfig& config);
+const RunConfig& Run();
+// DVP_HOST_TIMING=1: wall time of the host steps of a view, of their parts and of what the driver does between the passes
+// (tools/e2e_timing.sh folds them per pass).  A Lap prints "<prefix><what>: <ms since the last one> ms" to ViewLog().
+bool HostTiming();
+struct Lap {
+	const char* prefix;
+	std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
+	void operator()(const std::string& what);
+};
+
 // ---- free functions (APD.h:11-54) ------------------------------------------------------------------
 void Connect(const Mat& dstImage, Mat& label_mask, std::vector<int>& label_cnt);      // APD.cpp:233-346
 void Label_Update(Mat& label_mask, std::vector<int>& label_cnt);                       // APD.cpp:192-230
+void CleanSelectedViewsOnHost(Mat& views, int nsrc, int min_region);                   // main.cpp:311-363 on a view's selected-view words (driver.cpp: cc.cpp stays a file that builds on its own)
 bool ReadBinMat(const path& mat_path, Mat& mat);                                       // APD.cpp:548-573
 bool WriteBinMat(const path& mat_path, const Mat& mat);                                // APD.cpp:630-649
 int writeDepthDmb(const path& mat_path, const Mat& depth);                             // APD.cpp:575-600
@@ -56,11 +121,6 @@ Mat ReadPnm(const path& file, int channels);         // a binary P5 / P6 file wi
 Mat ReadImageGray(const path& image_path_jpg);      // stands in for cv::imread(IMREAD_GRAYSCALE), APD.cpp:1057
 bool ImageFileSize(const path& image_path_jpg, int* width, int* height);   // from the file header, without decoding
 Mat ReadImageColor(const path& image_path_jpg);     // cv::imread(IMREAD_COLOR) (BGR), APD.cpp:1842
-// `apd --decode-on gpu`.  true: ReadImageGray and ReadImageColor hand a .jpg to the engine (include/dvp_mvs.h dvp_jpeg_decode,
-// dvp_jpeg_decode_into_store): the entropy decode stays on the host, the inverse DCT and the colour conversion run on APD::GetDevice().
-// Same bytes; one line "Image decode: on the device (<file>, grey|colour)" per file (grey, into the image store: with --images-on gpu); a failure stops the job.  Default false.
-void SetDecodeOnDevice(bool on);
-bool DecodeOnDevice();
 Mat ResizeLinear(const Mat& src_f32, int new_cols, int new_rows);   // cv::resize(INTER_LINEAR), APD.cpp:1129
 // threads of the host-side pixel loops: min(32, hardware threads), DVP_HOST_THREADS overrides
 int HostThreads();
@@ -128,47 +188,7 @@ public:
 	std::function<std::vector<std::vector<uint8_t>>()> BeginPreviews(int quality = 95);
 	static void SetSeed(uint64_t seed);
 	static void ReleasePooledContext();   // frees the recycled engine context and the image cache
-	// The shipped reference writes labels_<s>.dmb but never loads it (the load is commented out,
-	// APD.cpp:1630-1633): its label map stays zero unless MVS4/<id>.dmb needs rescaling.  true: load
-	// labels_<s>.dmb in SupportInitialization (what the commented-out lines do).  Default false.
-	static void SetUseLabelFiles(bool on);
-	// `apd --edges-on gpu`.  true: a view whose edges_<s>.dmb neither exists nor is cached nor announced does not wait for a
-	// helper thread's EdgeSegment: SupportInitialization announces the file, CudaSpaceInitialization has the engine compute the
-	// map from the context's image 0 straight into the context's edge buffer (dvp_edge_map_begin), and the function
-	// TakeEdgeFetch returns copies it to the host, writes rawedge_<s>.jpg if previews are on and publishes the file (any
-	// thread, after this object is gone too; the destructor runs it if nobody took it).  Same bytes as the host's map.
-	// Default false: GetProblemEdges makes the file (edges.cpp).
-	static void SetEdgesOnDevice(bool on);
-	static bool EdgesOnDevice();
-	std::function<void()> TakeEdgeFetch();   // empty when this view's edge map came from its file
-	// `apd --cleanup-on gpu`.  true: RunPatchMatchAndStageMaps has the engine run ProcessProblem's visibility-mask clean-up
-	// (main.cpp:311-363) on the staged selected-view words (dvp_set_view_cleanup with the view's source count and
-	// min_region = 20 * (8 / scale_size)^2): the words its fetch returns are final, and the driver's background job skips its
-	// Connect loop.  Flows that do not stage maps on the device keep the host loop.  Same words either way.  Default false.
-	static void SetCleanupOnDevice(bool on);
-	static bool CleanupOnDevice();
-	// `apd --labels-on gpu`.  true: GetProblemEdges makes labels_<s>.dmb with a dvp_labels job on the driver's device
-	// (include/dvp_mvs.h: resizes, Roberts cross, both component passes and the numbering on the device, the Hough lines on the
-	// host in between) instead of the helper thread's LabelSegment — one job per calling thread, kept for the thread's life.
-	// Announcing, publishing, file names and SetUseLabelFiles are untouched.  Same values.  Default false.
-	static void SetLabelsOnDevice(bool on);
-	static bool LabelsOnDevice();
-	// `apd --prior-on gpu`.  true: the FIRST_INIT plane prior (dep/<id>.dmb + sfm/<id>.txt, APD.cpp:1210-1424) is made by the engine
-	// (include/dvp_mvs.h dvp_plane_prior: the points and the triangulation on the host, the sweep, the rate map, the rescale and
-	// the planes on the device, into the context's planes): InuputInitialization only reads the three files and keeps them,
-	// CudaSpaceInitialization calls the engine after the cameras' upload and uploads no planes.  Same planes, same two log lines.
-	// Default false.
-	static void SetPriorOnDevice(bool on);
-	static bool PriorOnDevice();
-	// `apd --images-on gpu`.  true: the process keeps the job's decoded 8-bit images in one dvp_images store on the driver's device
-	// (put by the decode prefetch threads or at a view's first use, within DVP_RESIDENT_IMAGES_GB), and a view whose images are all
-	// there builds no host float image: InuputInitialization takes the sizes from the store and the std::round(n * factor) rule,
-	// CudaSpaceInitialization has the engine make the level of every image from the bytes (dvp_upload_images_u8: padding /
-	// cropping to the reference's size, cv::resize(INTER_LINEAR)).  A view with an image missing from the store takes the host
-	// path, whole.  Either way the view logs one line, "Images: levels made on the device" or "Images: host path (<reason>)".
-	// Same texels, same dvp_image_format.  Default false.
-	static void SetImagesOnDevice(bool on);
-	static bool ImagesOnDevice();
+	std::function<void()> TakeEdgeFetch();   // RunConfig::edges_on_device: fetches + publishes the engine's edge map; empty when this view's edge map came from its file
 	static bool StoreDecoded(int image_id, const path& image_file, int* width = nullptr, int* height = nullptr);   // false: unreadable, or no room in the store
 	static long long StoredImageBytes();   // device bytes the store holds
 	// --decode-on gpu with --images-on gpu: the luma plane of images/<id>.jpg (its bytes in `file`) reconstructed straight into the
@@ -176,10 +196,6 @@ public:
 	// room — the caller decodes through dvp_jpeg_decode, and StoreDecoded decides as before.
 	static bool PutJpegInStore(const path& image_file, const std::vector<uint8_t>& file, Mat* gray);
 	static void InsertDecoded(const path& image_file, const Mat& gray);   // a decoded image that came from another rank
-	// true (default): a pass that starts from maps of another size (REFINE_INIT on a finer pyramid level) hands them to the
-	// engine at their own size and RescaleMatToTargetSize runs there (dvp_upload_state_rescaled); false: the five host-side
-	// rescales + the plane assembly of the reference's flow (APD.cpp:1176-1180, 1440-1456, 1656-1659).  Same maps either way.
-	static void SetDeviceRescale(bool on);
 	// multi-GPU hooks of the driver (comm.h).  Image cache: the decoded + rescaled float image of a view in
 	// its reference role at the problem's scale — rank 0 fills it from disk, the others from a broadcast.
 	static Mat CachedImage(const Problem& problem, int image_id, int* orig_cols, int* orig_rows);
@@ -236,8 +252,8 @@ private:
 	int ctx_device = 0;
 	DvpTimings timings{};
 	int image_format = 0;
-	bool images_on_device = false;   // this view's level images are made by the engine from the store (SetImagesOnDevice)
-	bool edge_on_device = false;   // the edge map is made by the engine (SetEdgesOnDevice) and its file still has to be published
+	bool images_on_device = false;   // this view's level images are made by the engine from the store (RunConfig::images_on_device)
+	bool edge_on_device = false;   // the edge map is made by the engine (RunConfig::edges_on_device) and its file still has to be published
 	path edge_file, rawedge_file;
 };
 #endif

@@ -120,7 +120,7 @@ static int scale_level(const Problem& problem) {
 	while ((1 << scale) < problem.scale_size) scale++;
 	return scale;
 }
-// APD::SetLabelsOnDevice: LabelSegment's map from a dvp_labels job of the calling thread (a helper thread, or the driver's with
+// RunConfig::labels_on_device: LabelSegment's map from a dvp_labels job of the calling thread (a helper thread, or the driver's with
 // --sync-io), made at the first map and destroyed when the thread ends.  A failure is fatal: there is no quiet way back to the host
 static Mat DeviceLabelMap(const int scale, const Mat& image_uint) {
 	struct Holder {
@@ -143,8 +143,8 @@ std::vector<path> ProblemEdgeOutputs(const Problem& problem) {
 	std::vector<path> out;
 	const path edge_path = problem.result_folder / path("edges_" + std::to_string(scale) + ".dmb");
 	const path label_path = problem.result_folder / path("labels_" + std::to_string(scale) + ".dmb");
-	// (APD::SetEdgesOnDevice: the view itself has the engine make the map, APD::SupportInitialization)
-	if (problem.params.use_edge && !APD::EdgesOnDevice() && !ResultExists(edge_path)) out.push_back(edge_path);
+	// (RunConfig::edges_on_device: the view itself has the engine make the map, APD::SupportInitialization)
+	if (problem.params.use_edge && !Run().edges_on_device && !ResultExists(edge_path)) out.push_back(edge_path);
 	if (problem.params.use_label && !ResultExists(label_path)) out.push_back(label_path);
 	return out;
 }
@@ -169,7 +169,7 @@ void GetProblemEdges(const Problem& problem, const std::vector<path>& outputs) {
 	if (need_label) {   // from the full-size image (main.cpp:236)
 		const Mat image_uint = APD::DecodedGray(problem.dense_folder / path("images") / path(ToFormatIndex(problem.ref_image_id) + ".jpg"));
 		if (image_uint.empty()) { publish_empty(); return; }
-		PublishResult(label_path, APD::LabelsOnDevice() ? DeviceLabelMap(scale, image_uint) : EdgeSegment(scale, image_uint, 1));
+		PublishResult(label_path, Run().labels_on_device ? DeviceLabelMap(scale, image_uint) : EdgeSegment(scale, image_uint, 1));
 		need_label = false;
 	}
 	if (!need_edge) return;

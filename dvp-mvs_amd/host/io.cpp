@@ -226,13 +226,10 @@ Mat ReadPnm(const path& file, int channels) {
 // images/<id>.jpg as the reference's converter writes it (baseline JPEG: host/jpeg.cpp); a .pgm / .ppm of
 // the same stem is used when there is no .jpg (synthetic datasets are written loss-free)
 //
-// `apd --decode-on gpu` (SetDecodeOnDevice): a .jpg is parsed and entropy-decoded here, in DecodeJpeg's own text, and its blocks and
+// `apd --decode-on gpu` (RunConfig::decode_on_device): a .jpg is parsed and entropy-decoded here, in DecodeJpeg's own text, and its blocks and
 // pixels are reconstructed by the engine (include/dvp_mvs.h dvp_jpeg_decode; same bytes).  A grey images/<id>.jpg goes straight
 // into the job's image store when there is one (APD::PutJpegInStore: dvp_jpeg_decode_into_store) and comes back as the host plane the
 // edge and label stages still take.  A file the engine refuses stops the job: nothing falls back to the host decoder.
-static std::atomic<bool> g_decode_on_device{false};
-void SetDecodeOnDevice(bool on) { g_decode_on_device = on; }
-bool DecodeOnDevice() { return g_decode_on_device; }
 static Mat decode_jpeg_on_device(const path& jpg, int channels) {
 	std::vector<uint8_t> file;
 	{
@@ -255,7 +252,7 @@ static Mat decode_jpeg_on_device(const path& jpg, int channels) {
 static Mat read_image(const path& jpg, int channels) {
 	const std::string ext = jpg.extension().string();
 	if ((ext == ".jpg" || ext == ".jpeg" || ext == ".JPG" || ext == ".JPEG") && std::filesystem::exists(jpg)) {
-		if (g_decode_on_device) return decode_jpeg_on_device(jpg, channels);
+		if (Run().decode_on_device) return decode_jpeg_on_device(jpg, channels);
 		Mat m = DecodeJpeg(jpg, channels);
 		if (!m.empty()) return m;
 	}

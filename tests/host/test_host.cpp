@@ -2,7 +2,7 @@
 // rescale helpers.  Exit code 0 = all passed.
 #include <thread>
 #include <chrono>
-#include "../../dvp-mvs_amd/host/APD.h"
+#include "../../dvp-mvs_amd/host/driver.h"
 #include "../../dvp-mvs_amd/csrc/dvp_fuse_math.hpp"
 #include <cassert>
 #include <cmath>
@@ -208,7 +208,52 @@ static int dump_prior(const path& folder, int id, int W, int H, const path& out)
 	return f.good() ? 0 : 4;
 }
 
+// `test_host --cleanup in.bin W H nsrc min_region out.bin`: CleanSelectedViewsOnHost (what `apd --cleanup-on host` runs) on a raw
+// W x H map of 32-bit selected-view words (tests/test_driver_host.py)
+static int clean_views(const char* in, int W, int H, int nsrc, int min_region, const char* out) {
+	Mat views(H, W, CV_32S);
+	std::ifstream f(in, std::ios::binary);
+	if (W < 1 || H < 1 || !f.read((char*)views.data, (std::streamsize)views.total() * 4)) return 2;
+	CleanSelectedViewsOnHost(views, nsrc, min_region);
+	std::ofstream o(out, std::ios::binary);
+	o.write((const char*)views.data, (std::streamsize)views.total() * 4);
+	return o.good() ? 0 : 3;
+}
+
+// `test_host --options <argv...>`: what ParseOptions makes of `apd <argv...>`, one field per line
+static int dump_options(int argc, char** argv) {
+	const Options o = ParseOptions(argc, argv);
+	const RunConfig& r = o.run;
+	std::cout << "dense_folder " << o.dense_folder.string() << "\ngpu " << o.gpu << "\nmax_src " << o.max_src << "\niters " << o.iters << "\nmin_scale " << o.min_scale
+	          << "\ngeom_passes " << o.geom_passes << "\nrank " << o.rank << "\nworld " << o.world << "\nseed " << o.seed << "\nfusion " << o.fusion << "\njacobi " << o.jacobi
+	          << "\ncollective_timeout_s " << o.collective_timeout_s << "\nsync_io " << o.sync_io << "\nhost_rescale " << o.host_rescale << "\npreviews " << o.previews
+	          << "\nviews_in_flight " << o.views_in_flight << "\nin_flight_pixels " << o.in_flight_pixels << "\njob " << o.job << "\ntransport " << o.transport
+	          << "\nfusion_on_host " << o.fusion_on_host << "\nfusion_kind " << o.fusion_kind << "\nuse_label_files " << r.use_label_files << "\nedges_on_device " << r.edges_on_device
+	          << "\ncleanup_on_device " << r.cleanup_on_device << "\nlabels_on_device " << r.labels_on_device << "\nprior_on_device " << r.prior_on_device
+	          << "\nimages_on_device " << r.images_on_device << "\ndecode_on_device " << r.decode_on_device << "\ndevice_rescale " << r.device_rescale << "\ndevice_maps " << r.device_maps
+	          << "\nstrong_wide " << r.strong_wide << "\nfinal_iteration " << r.final_iteration << "\n";
+	return 0;
+}
+
+// `test_host --plan round_num min_scale passes`: the pass list, one line per pass — "level scale geom_index" and what ConfigurePass
+// leaves in the Problem that is carried from pass to pass, as the driver's are (with --iters 3)
+static int dump_plan(int round_num, int min_scale, int passes) {
+	const std::vector<Pass> plan = BuildPlan(round_num, min_scale, passes);
+	Problem p;
+	for (size_t it = 0; it < plan.size(); ++it) {
+		ConfigurePass(p, plan[it], (int)it, 3, round_num);
+		const PatchMatchParams& q = p.params;
+		printf("%d %d %d | iteration %d scale_size %d max_iterations %d state %d use_APD %d use_detail %d geom_consistency %d weak_peak_radius %d rotate_time %d ransac_threshold %.5f\n",
+		       plan[it].level, plan[it].scale, plan[it].geom_index, p.iteration, p.scale_size, q.max_iterations, (int)q.state, (int)q.use_APD, (int)q.use_detail, (int)q.geom_consistency,
+		       q.weak_peak_radius, q.rotate_time, q.ransac_threshold);
+	}
+	return 0;
+}
+
 int main(int argc, char** argv) {
+	if (argc > 7 && std::string(argv[1]) == "--cleanup") return clean_views(argv[2], std::atoi(argv[3]), std::atoi(argv[4]), std::atoi(argv[5]), std::atoi(argv[6]), argv[7]);
+	if (argc > 2 && std::string(argv[1]) == "--options") return dump_options(argc - 1, argv + 1);
+	if (argc > 4 && std::string(argv[1]) == "--plan") return dump_plan(std::atoi(argv[2]), std::atoi(argv[3]), std::atoi(argv[4]));
 	if (argc > 2 && std::string(argv[1]) == "--fuse") return fuse_folder(argv[2]);
 	if (argc > 1 && std::string(argv[1]) == "--acos") return acos_contract();
 	if (argc > 6 && std::string(argv[1]) == "--depth-cloud") {   // --depth-cloud depths.dmb image cam out.ply dmin dmax

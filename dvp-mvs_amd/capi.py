@@ -44,7 +44,8 @@ EXPORTS = ["dvp_ctx_create", "dvp_ctx_destroy", "dvp_ctx_reserve", "dvp_last_err
            "dvp_plane_prior", "dvp_plane_prior_stage", "dvp_plane_prior_timings",
            "dvp_view_scores", "dvp_convert_image", "dvp_pairs_last_error",
            "dvp_undistort_image", "dvp_undistort_last_error",
-           "dvp_cloud_distances", "dvp_cloud_evaluate", "dvp_cloud_last_error"]
+           "dvp_cloud_distances", "dvp_cloud_evaluate", "dvp_cloud_last_error",
+           "dvp_cloud_prepare", "dvp_cloud_evaluate_prepared", "dvp_cloud_prep_last_error"]
 # ... and the one whose name holds a digit (a scan of the header for [a-z_] names does not see it)
 EXPORTS_WITH_DIGITS = ["dvp_upload_images_u8"]
 PREVIEW_DEPTH, PREVIEW_NORMAL, PREVIEW_WEAK = 1, 2, 4
@@ -169,6 +170,10 @@ def lib():
         L.dvp_cloud_evaluate.argtypes = [ci, vp, ll, vp, ll, vp, ci, vp, vp, vp, vp, vp]
         L.dvp_cloud_last_error.restype = ctypes.c_char_p
         L.dvp_cloud_last_error.argtypes = []
+        L.dvp_cloud_prepare.argtypes = [ci, vp, ll, vp, vp, vp, vp]
+        L.dvp_cloud_evaluate_prepared.argtypes = [ci, vp, ll, vp, vp, ll, vp, vp, ci, vp, vp, vp, vp, vp, vp]
+        L.dvp_cloud_prep_last_error.restype = ctypes.c_char_p
+        L.dvp_cloud_prep_last_error.argtypes = []
         _LIB = L
     return _LIB
 
@@ -780,3 +785,68 @@ def from_scene(scene, params, seed=1234, sampler=0, depths=None, device=0):
     if depths is not None:
         c.set_depths(depths)
     return c
+
+
+class DvpCloudPrep(ctypes.Structure):
+    _fields_ = [("transform", ctypes.c_void_p), ("crop_axis", ctypes.c_int), ("axis_min", ctypes.c_double), ("axis_max", ctypes.c_double),
+                ("polygon_xyz", ctypes.c_void_p), ("num_polygon", ctypes.c_int), ("voxel", ctypes.c_double)]
+
+
+def _cloud_prep(transform=None, crop=None, voxel=0.0):
+    """(DvpCloudPrep, the arrays it points into).  crop = dict(axis=0 | 1 | 2 or "X" | "Y" | "Z", axis_min, axis_max, polygon=(n, 3))"""
+    p, keep = DvpCloudPrep(None, -1, 0.0, 0.0, None, 0, float(voxel)), []
+    if transform is not None:
+        m = np.ascontiguousarray(transform, np.float64).reshape(-1)
+        if m.size != 16:
+            raise ValueError("a transform holds 16 numbers, got %d" % m.size)
+        keep.append(m)
+        p.transform = m.ctypes.data
+    if crop is not None:
+        axis = crop["axis"]
+        poly = np.ascontiguousarray(crop["polygon"], np.float64)
+        if poly.ndim != 2 or poly.shape[1] != 3:
+            raise ValueError("a crop polygon is an (n, 3) array")
+        keep.append(poly)
+        p.crop_axis = "XYZ".index(axis) if isinstance(axis, str) else int(axis)
+        p.axis_min, p.axis_max = float(crop["axis_min"]), float(crop["axis_max"])
+        p.polygon_xyz, p.num_polygon = poly.ctypes.data, len(poly)
+    return p, keep
+
+
+def cloud_prepare(xyz, transform=None, crop=None, voxel=0.0, device=0):
+    """dict(xyz: (M, 3) float32, first_index: (M,) int64 input index of every output point, counts: (4,) int64 finite, after the
+    transform, inside the crop, output) of one cloud prepared on the GPU (include/dvp_mvs.h dvp_cloud_prepare)"""
+    L = lib()
+    a = _cloud(xyz, "cloud_prepare")
+    p, keep = _cloud_prep(transform, crop, voxel)
+    out, first, counts = np.empty((len(a), 3), np.float32), np.empty(len(a), np.int64), np.zeros(4, np.int64)
+    if L.dvp_cloud_prepare(device, _p(a), len(a), ctypes.byref(p), _p(out), _p(first), _p(counts)) != 0:
+        raise DvpError(L.dvp_cloud_prep_last_error().decode())
+    return dict(xyz=out[:counts[3]].copy(), first_index=first[:counts[3]].copy(), counts=counts)
+
+
+def cloud_evaluate_prepared(recon, truth, tolerances, prep_recon=None, prep_truth=None, device=0, distances=False):
+    """cloud_evaluate's dict of the two clouds after each has been prepared on the GPU, plus counts: (2, 4) int64; prep_recon /
+    prep_truth = dict(transform=, crop=, voxel=) as cloud_prepare takes them (include/dvp_mvs.h dvp_cloud_evaluate_prepared); the
+    distances refer to the prepared points"""
+    L = lib()
+    r, t = _cloud(recon, "cloud_evaluate_prepared"), _cloud(truth, "cloud_evaluate_prepared")
+    pr, keep_r = _cloud_prep(**(prep_recon or {}))
+    pt, keep_t = _cloud_prep(**(prep_truth or {}))
+    tol = np.ascontiguousarray(tolerances, np.float32).reshape(-1)
+    wr, wt, used = np.zeros(max(tol.size, 1), np.int64), np.zeros(max(tol.size, 1), np.int64), np.zeros(2, np.int64)
+    counts = np.zeros((2, 4), np.int64)
+    dr = np.empty(len(r), np.float32) if distances else None
+    dt = np.empty(len(t), np.float32) if distances else None
+    if L.dvp_cloud_evaluate_prepared(device, _p(r), len(r), ctypes.byref(pr), _p(t), len(t), ctypes.byref(pt), _p(tol), tol.size, _p(wr), _p(wt), _p(used), _p(dr), _p(dt),
+                                     _p(counts)) != 0:
+        raise DvpError(L.dvp_cloud_prep_last_error().decode())
+    wr, wt = wr[:tol.size], wt[:tol.size]
+    a = wr / used[0] if used[0] else np.zeros(tol.size)
+    c = wt / used[1] if used[1] else np.zeros(tol.size)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        f1 = np.where(a + c > 0, 2 * a * c / (a + c), 0.0)
+    out = dict(within_recon=wr, within_truth=wt, used=used, accuracy=a, completeness=c, f1=f1, counts=counts)
+    if distances:
+        out.update(d2_recon=dr[:counts[0, 3]].copy(), d2_truth=dt[:counts[1, 3]].copy())
+    return out

@@ -25,6 +25,7 @@
 
 #include "../../include/dvp_mvs.h"
 #include "dvp_cloudeval.hpp"
+#include "dvp_cloudeval_run.h"
 #include "dvp_devmem.hpp"
 #include "dvp_wave.hpp"
 
@@ -252,9 +253,10 @@ static int cloud_fail(const char* who, const std::string& what) { return t_cloud
 
 extern "C" const char* dvp_cloud_last_error(void) { return t_cloud_error.c_str(); }
 
-// cloud 0's points are queries against cloud 1, and with `both` the other way round; d2[c] / within[c] may be NULL
+// cloud 0's points are queries against cloud 1, and with `both` the other way round; d2[c] / within[c] may be NULL.  With `on_device`
+// the clouds are device arrays already and on_device[c] holds cloud c's bounds: nothing is read on the host and nothing uploaded.
 static int cloud_run(const char* who, int device, const float* const xyz[2], const long long num[2], const float* tolerances, int num_tol, bool both, long long* const within[2],
-                     long long* used, float* const d2[2]) {
+                     long long* used, float* const d2[2], const dvpce::Bounds* on_device = nullptr) {
 	using namespace dvpce;
 	t_cloud_error.clear();
 	for (int c = 0; c < 2; ++c) {
@@ -278,7 +280,14 @@ static int cloud_run(const char* who, int device, const float* const xyz[2], con
 	long long finite[2];
 	for (int c = 0; c < 2; ++c) {
 		const long long before = bounds.finite;
-		add_bounds(&bounds, xyz[c], num[c]);
+		if (!on_device) add_bounds(&bounds, xyz[c], num[c]);
+		else {
+			bounds.finite += on_device[c].finite;
+			for (int a = 0; a < 3; ++a) {
+				if (on_device[c].lo[a] < bounds.lo[a]) bounds.lo[a] = on_device[c].lo[a];
+				if (on_device[c].hi[a] > bounds.hi[a]) bounds.hi[a] = on_device[c].hi[a];
+			}
+		}
 		finite[c] = bounds.finite - before;
 	}
 	Grid g;
@@ -305,7 +314,7 @@ static int cloud_run(const char* who, int device, const float* const xyz[2], con
 	size_t o_xyz[2], o_count[2], o_start[2], o_slot[2], o_sorted[2], o_d2[2], o_sums[2];
 	const size_t o_keys = carve.take(cap * 8), o_within = carve.take(2 * kMaxTolerances * 8);
 	for (int c = 0; c < 2; ++c) {
-		o_xyz[c] = carve.take((size_t)num[c] * 12);
+		o_xyz[c] = carve.take(on_device ? 0 : (size_t)num[c] * 12);
 		o_count[c] = carve.take(cap * 4);
 		o_start[c] = carve.take((cap + 1) * 4);
 		o_slot[c] = carve.take((size_t)num[c] * 4);
@@ -318,14 +327,15 @@ static int cloud_run(const char* who, int device, const float* const xyz[2], con
 	bool ok = hipMemsetAsync(b + o_keys, 0xff, cap * 8, st) == hipSuccess && hipMemsetAsync(b + o_within, 0, 2 * kMaxTolerances * 8, st) == hipSuccess;
 	for (int c = 0; c < 2 && ok; ++c) {
 		ok = hipMemsetAsync(b + o_count[c], 0, cap * 4, st) == hipSuccess;
-		if (ok && num[c]) ok = hipMemcpyAsync(b + o_xyz[c], xyz[c], (size_t)num[c] * 12, hipMemcpyHostToDevice, st) == hipSuccess;
+		if (ok && num[c] && !on_device) ok = hipMemcpyAsync(b + o_xyz[c], xyz[c], (size_t)num[c] * 12, hipMemcpyHostToDevice, st) == hipSuccess;
 	}
 	if (!ok) { (void)hipGetLastError(); return cloud_fail(who, "upload failed"); }
 	lap("upload");
 	unsigned long long* keys = (unsigned long long*)(b + o_keys);
+	const float* const points[2] = { on_device ? xyz[0] : (const float*)(b + o_xyz[0]), on_device ? xyz[1] : (const float*)(b + o_xyz[1]) };
 	auto grid_of = [](long long n) { return dim3((unsigned)((n + 255) / 256)); };
 	for (int c = 0; c < 2; ++c)
-		if (num[c]) hipLaunchKernelGGL(dvp_ce_bin, grid_of(num[c]), dim3(256), 0, st, (const float*)(b + o_xyz[c]), (uint32_t)num[c], g, keys, cap - 1, (uint32_t*)(b + o_count[c]),
+		if (num[c]) hipLaunchKernelGGL(dvp_ce_bin, grid_of(num[c]), dim3(256), 0, st, points[c], (uint32_t)num[c], g, keys, cap - 1, (uint32_t*)(b + o_count[c]),
 		                               (uint32_t*)(b + o_slot[c]), (float*)(b + o_d2[c]));
 	lap("bin");
 	for (int c = 0; c < 2; ++c) {
@@ -336,14 +346,14 @@ static int cloud_run(const char* who, int device, const float* const xyz[2], con
 	}
 	lap("scan");
 	for (int c = 0; c < 2; ++c)
-		if (num[c]) hipLaunchKernelGGL(dvp_ce_scatter, grid_of(num[c]), dim3(256), 0, st, (const float*)(b + o_xyz[c]), (uint32_t)num[c], (const uint32_t*)(b + o_slot[c]),
+		if (num[c]) hipLaunchKernelGGL(dvp_ce_scatter, grid_of(num[c]), dim3(256), 0, st, points[c], (uint32_t)num[c], (const uint32_t*)(b + o_slot[c]),
 		                               (const uint32_t*)(b + o_start[c]), (uint32_t*)(b + o_count[c]), (float4*)(b + o_sorted[c]));
 	lap("scatter");
 	for (int c = 0; c < (both ? 2 : 1); ++c) {
 		const int t = 1 - c;
 		unsigned long long* counts = (unsigned long long*)(b + o_within) + c * kMaxTolerances;
 		if (lane_form) {
-			if (num[c]) hipLaunchKernelGGL(dvp_ce_query_lane, grid_of(num[c]), dim3(256), 0, st, (const float*)(b + o_xyz[c]), (uint32_t)num[c], (const float4*)(b + o_sorted[t]),
+			if (num[c]) hipLaunchKernelGGL(dvp_ce_query_lane, grid_of(num[c]), dim3(256), 0, st, points[c], (uint32_t)num[c], (const float4*)(b + o_sorted[t]),
 			                               (const uint32_t*)(b + o_start[t]), keys, cap - 1, g, T2, tol, (float*)(b + o_d2[c]), counts);
 		} else if (finite[c]) {
 			hipLaunchKernelGGL(dvp_ce_query_wave, grid_of(finite[c]), dim3(256), 0, st, (const float4*)(b + o_sorted[c]), (uint32_t)finite[c], (const float4*)(b + o_sorted[t]),
@@ -367,6 +377,11 @@ static int cloud_run(const char* who, int device, const float* const xyz[2], con
 	}
 	if (timing) fprintf(stderr, "%s timing (%lld + %lld points, %llu slots):%s\n", who, num[0], num[1], (unsigned long long)cap, report.c_str());
 	return 0;
+}
+
+int dvpce::cloud_run_on_device(const char* who, int device, const float* const dev_xyz[2], const long long num[2], const Bounds bounds[2], const float* tolerances, int num_tol,
+                               long long* const within[2], long long* used, float* const d2[2]) {
+	return cloud_run(who, device, dev_xyz, num, tolerances, num_tol, true, within, used, d2, bounds);
 }
 
 extern "C" int dvp_cloud_distances(int device, const float* query_xyz, long long num_query, const float* target_xyz, long long num_target, float max_distance, float* d2_out) {

@@ -1,5 +1,6 @@
-// evaluate.cpp — `apd --evaluate recon.ply --against truth.ply` (evaluate.h): both clouds read, the two directions counted on the
-// device (dvp_cloud_evaluate) or by the same text on the host (csrc/dvp_cloudeval.hpp: the double loop up to 2^24 pairs, the grid
+// evaluate.cpp — `apd --evaluate recon.ply --against truth.ply` (evaluate.h): both clouds read, prepared when --transform, --crop or
+// --voxel-size ask for it (csrc/dvp_cloudprep.hpp), the two directions counted on the device (dvp_cloud_evaluate, or
+// dvp_cloud_evaluate_prepared) or by the same text on the host (csrc/dvp_cloudeval.hpp: the double loop up to 2^24 pairs, the grid
 // walked serially above), and the report, whose figures come from the integer counts alone.
 #include "evaluate.h"
 
@@ -10,11 +11,17 @@
 #include "../../include/dvp_mvs.h"
 #include "../csrc/dvp_cloudeval.hpp"
 
-std::string EvaluateReport(const EvaluateOptions& o, const long long num[2], const long long used[2], const long long* within_recon, const long long* within_truth) {
+std::string EvaluateReport(const EvaluateOptions& o, const long long num[2], const long long used[2], const long long* within_recon, const long long* within_truth,
+                           const long long* counts) {
 	char text[256];
-	std::string report = "reconstruction " + o.recon + " " + std::to_string(used[0]) + " points (" + std::to_string(num[0] - used[0]) + " skipped)\n" +
-	                     "ground_truth " + o.truth + " " + std::to_string(used[1]) + " points (" + std::to_string(num[1] - used[1]) + " skipped)\n" +
-	                     "tolerance accuracy completeness f1\n";
+	// every point dropped for a non-finite coordinate: as read, after the transform, or after the rounding of a prepared point to binary32
+	const long long skipped[2] = { counts ? (num[0] - counts[1]) + (counts[3] - used[0]) : num[0] - used[0], counts ? (num[1] - counts[5]) + (counts[7] - used[1]) : num[1] - used[1] };
+	std::string report = "reconstruction " + o.recon + " " + std::to_string(used[0]) + " points (" + std::to_string(skipped[0]) + " skipped)\n" +
+	                     "ground_truth " + o.truth + " " + std::to_string(used[1]) + " points (" + std::to_string(skipped[1]) + " skipped)\n";
+	for (int c = 0; c < 2 && counts; ++c)
+		report += std::string("prepared ") + (c == 0 ? "reconstruction: " : "ground_truth: ") + std::to_string(counts[4 * c]) + " finite, " + std::to_string(counts[4 * c + 2]) +
+		          " in the crop volume, " + std::to_string(counts[4 * c + 3]) + " points\n";
+	report += "tolerance accuracy completeness f1\n";
 	for (size_t k = 0; k < o.tolerances.size(); ++k) {
 		const double a = used[0] ? (double)within_recon[k] / (double)used[0] : 0.0, c = used[1] ? (double)within_truth[k] / (double)used[1] : 0.0;
 		const double f = a + c == 0.0 ? 0.0 : 2.0 * a * c / (a + c);
@@ -22,6 +29,14 @@ std::string EvaluateReport(const EvaluateOptions& o, const long long num[2], con
 		report += text;
 	}
 	return report;
+}
+
+bool WritePlyVertices(const std::string& file, const std::vector<float>& xyz, std::string* error) {
+	std::ofstream out(file, std::ios::binary);
+	out << "ply\nformat binary_little_endian 1.0\nelement vertex " << xyz.size() / 3 << "\nproperty float x\nproperty float y\nproperty float z\nend_header\n";
+	out.write((const char*)xyz.data(), (std::streamsize)(xyz.size() * 4));   // (the hosts this runs on are little-endian, as ExportPointCloud assumes)
+	if (!out.good()) { *error = "cannot write " + file; return false; }
+	return true;
 }
 
 static bool EvaluateCloudsOrThrow(const EvaluateOptions& o, std::string* report, std::string* error);
@@ -35,23 +50,75 @@ bool EvaluateClouds(const EvaluateOptions& o, std::string* report, std::string* 
 	}
 }
 
+// the C ABI's view of a description (it points into `p`)
+static dvp_cloud_prep AbiPrep(const dvpcp::Prep& p) {
+	dvp_cloud_prep c;
+	c.transform = p.has_transform ? p.m : nullptr;
+	c.crop_axis = p.crop_axis;
+	c.axis_min = p.axis_min;
+	c.axis_max = p.axis_max;
+	c.polygon_xyz = p.polygon.empty() ? nullptr : p.polygon.data();
+	c.num_polygon = (int)(p.polygon.size() / 3);
+	c.voxel = p.voxel;
+	return c;
+}
+
 static bool EvaluateCloudsOrThrow(const EvaluateOptions& o, std::string* report, std::string* error) {
+	const bool prepares = o.prepares();
+	if (!o.save_prepared.empty() && !prepares) { *error = "--save-prepared needs --transform, --crop or --voxel-size"; return false; }
+	dvpcp::Prep prep[2];   // recon, truth
+	if (!o.transform_file.empty()) {
+		if (!ReadTransformFile(o.transform_file, prep[0].m, error)) return false;
+		prep[0].has_transform = true;
+	}
+	if (!o.crop_file.empty()) {
+		if (!ReadCropFile(o.crop_file, &prep[0], error)) return false;
+		prep[1].crop_axis = prep[0].crop_axis;
+		prep[1].axis_min = prep[0].axis_min;
+		prep[1].axis_max = prep[0].axis_max;
+		prep[1].polygon = prep[0].polygon;
+	}
+	prep[0].voxel = prep[1].voxel = o.voxel;
+	for (int c = 0; c < 2 && prepares; ++c) {
+		const std::string what = dvpcp::check_prep(prep[c]);
+		if (!what.empty()) { *error = what; return false; }
+	}
 	std::vector<float> recon, truth;
 	if (!ReadPlyVertices(o.recon, &recon, error) || !ReadPlyVertices(o.truth, &truth, error)) return false;
+	const std::vector<float>* cloud[2] = { &recon, &truth };
 	const long long num[2] = { (long long)(recon.size() / 3), (long long)(truth.size() / 3) };
 	const int K = (int)o.tolerances.size();
-	long long within_recon[dvpce::kMaxTolerances] = {}, within_truth[dvpce::kMaxTolerances] = {}, used[2] = { 0, 0 };
-	if (o.on_gpu) {
+	long long within_recon[dvpce::kMaxTolerances] = {}, within_truth[dvpce::kMaxTolerances] = {}, used[2] = { 0, 0 }, counts[8] = {};
+	std::vector<float> prepared[2];
+	if (o.on_gpu && !prepares) {
 		if (dvp_cloud_evaluate(o.device, recon.data(), num[0], truth.data(), num[1], o.tolerances.data(), K, within_recon, within_truth, used, nullptr, nullptr) != 0) {
 			*error = dvp_cloud_last_error();
 			return false;
 		}
+	} else if (o.on_gpu) {
+		const dvp_cloud_prep abi[2] = { AbiPrep(prep[0]), AbiPrep(prep[1]) };
+		if (dvp_cloud_evaluate_prepared(o.device, recon.data(), num[0], &abi[0], truth.data(), num[1], &abi[1], o.tolerances.data(), K, within_recon, within_truth, used, nullptr,
+		                                nullptr, counts) != 0) {
+			*error = dvp_cloud_prep_last_error();
+			return false;
+		}
+		for (int c = 0; c < 2 && !o.save_prepared.empty(); ++c) {   // the prepared points themselves are only fetched to be saved
+			prepared[c].resize(cloud[c]->size());
+			long long again[4];
+			if (dvp_cloud_prepare(o.device, cloud[c]->data(), num[c], &abi[c], prepared[c].data(), nullptr, again) != 0) { *error = dvp_cloud_prep_last_error(); return false; }
+			prepared[c].resize((size_t)again[3] * 3);
+		}
 	} else {
-		const std::string what = K > dvpce::kMaxTolerances ? "at most 8 tolerances" :
-		                         dvpce::serial_evaluate(recon.data(), num[0], truth.data(), num[1], o.tolerances.data(), K, within_recon, within_truth, used, nullptr, nullptr);
+		std::string what = K > dvpce::kMaxTolerances ? "at most 8 tolerances" : "";
+		for (int c = 0; c < 2 && prepares && what.empty(); ++c) what = dvpcp::serial_prepare(cloud[c]->data(), num[c], prep[c], &prepared[c], nullptr, counts + 4 * c);
+		if (what.empty()) {
+			const std::vector<float>& r = prepares ? prepared[0] : recon, &t = prepares ? prepared[1] : truth;
+			what = dvpce::serial_evaluate(r.data(), (long long)(r.size() / 3), t.data(), (long long)(t.size() / 3), o.tolerances.data(), K, within_recon, within_truth, used, nullptr, nullptr);
+		}
 		if (!what.empty()) { *error = what; return false; }
 	}
-	*report = EvaluateReport(o, num, used, within_recon, within_truth);
+	if (!o.save_prepared.empty() && (!WritePlyVertices(o.save_prepared + "recon.ply", prepared[0], error) || !WritePlyVertices(o.save_prepared + "truth.ply", prepared[1], error))) return false;
+	*report = EvaluateReport(o, num, used, within_recon, within_truth, prepares ? counts : nullptr);
 	if (!o.out.empty()) {
 		std::ofstream out(o.out, std::ios::binary);
 		out << *report;

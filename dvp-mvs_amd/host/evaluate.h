@@ -6,6 +6,8 @@
 #include <string>
 #include <vector>
 
+#include "../csrc/dvp_cloudprep.hpp"
+
 // The vertices of a PLY file as packed x y z floats.  Formats binary_little_endian and ascii; x, y, z float or double (a double is
 // rounded to binary32) among any other scalar properties; a fixed-size element before `vertex` is skipped, those after it are
 // ignored.  false: *error says what is wrong (binary_big_endian, a list property in or before `vertex`, a short body, a missing x,
@@ -15,11 +17,25 @@ bool ReadPlyVertices(const std::string& file, std::vector<float>* xyz, std::stri
 struct EvaluateOptions {
 	std::string recon, truth, out;   // out: the report is also written there ("" = stdout only)
 	std::vector<float> tolerances = { 0.01f, 0.02f, 0.05f, 0.1f, 0.2f, 0.5f };   // ETH3D's, in metres
-	bool on_gpu = true;              // false: csrc/dvp_cloudeval.hpp's serial text on the host
+	bool on_gpu = true;              // false: csrc/dvp_cloudeval.hpp's and csrc/dvp_cloudprep.hpp's serial text on the host
 	int device = 0;
+	// the preparation of the clouds before they are measured (csrc/dvp_cloudprep.hpp); with none of the three the clouds are taken as read
+	std::string transform_file;      // --transform: 16 numbers, applied to the reconstruction only
+	std::string crop_file;           // --crop: a SelectionPolygonVolume JSON, applied to both clouds after the transform
+	double voxel = 0.0;              // --voxel-size: both clouds, each on its own grid
+	std::string save_prepared;       // --save-prepared PREFIX: <PREFIX>recon.ply and <PREFIX>truth.ply
+	bool prepares() const { return !transform_file.empty() || !crop_file.empty() || voxel != 0.0; }
 };
-// the report of two counted clouds: the same bytes whichever flavour made the counts
-std::string EvaluateReport(const EvaluateOptions& options, const long long num[2], const long long used[2], const long long* within_recon, const long long* within_truth);
+// 16 numbers separated by whitespace; false: *error says what is wrong (another count, a word that is no number, a non-finite entry, a last row other than 0 0 0 1)
+bool ReadTransformFile(const std::string& file, double m[16], std::string* error);
+// Open3D's SelectionPolygonVolume JSON -> prep's crop; false: *error says what is wrong (malformed JSON, a missing field, fewer than 3 or more than 256 vertices ...)
+bool ReadCropFile(const std::string& file, dvpcp::Prep* prep, std::string* error);
+// binary_little_endian, float x y z only: a file ReadPlyVertices takes
+bool WritePlyVertices(const std::string& file, const std::vector<float>& xyz, std::string* error);
+// the report of two counted clouds: the same bytes whichever flavour made the counts.  counts (2 x 4: finite, after the transform,
+// inside the crop, output points; NULL without a preparation) adds the two `prepared` lines, and `used` then counts prepared points.
+std::string EvaluateReport(const EvaluateOptions& options, const long long num[2], const long long used[2], const long long* within_recon, const long long* within_truth,
+                           const long long* counts = nullptr);
 // Reads both files, counts, *report = the text.  false: *error says what stopped it.
 bool EvaluateClouds(const EvaluateOptions& options, std::string* report, std::string* error);
 #endif

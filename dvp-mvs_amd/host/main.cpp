@@ -476,7 +476,10 @@ int ConvertMain(int argc, char** argv) {
 
 // apd --evaluate <recon.ply> --against <truth.ply> [options]: no engine context, no rank, no result store
 int EvaluateMain(int argc, char** argv) {
-	const char* usage = "USAGE: apd --evaluate recon.ply --against truth.ply [--tolerances 0.01,0.02,0.05,0.1,0.2,0.5] [--evaluate-on gpu|host] [--gpu N] [--out FILE]\n";
+	const char* usage = "USAGE: apd --evaluate recon.ply --against truth.ply [--tolerances 0.01,0.02,0.05,0.1,0.2,0.5] [--evaluate-on gpu|host] [--gpu N] [--out FILE]\n"
+	                    "       [--transform FILE] [--crop FILE] [--voxel-size S] [--save-prepared PREFIX]\n"
+	                    "  --transform: 16 numbers (4 x 4, row-major) applied to the reconstruction; --crop: a SelectionPolygonVolume JSON, both clouds;\n"
+	                    "  --voxel-size: both clouds down-sampled to one centroid per voxel of edge S; --save-prepared: <PREFIX>recon.ply and <PREFIX>truth.ply\n";
 	if (argc < 3 || argv[2][0] == '-') { std::cerr << usage; return EXIT_FAILURE; }
 	EvaluateOptions o;
 	o.recon = argv[2];
@@ -503,6 +506,14 @@ int EvaluateMain(int argc, char** argv) {
 		}
 		else if (s == "--gpu") o.device = std::atoi(v.c_str());
 		else if (s == "--out") o.out = v;
+		else if (s == "--transform") o.transform_file = v;
+		else if (s == "--crop") o.crop_file = v;
+		else if (s == "--voxel-size") {
+			char* end = nullptr;
+			o.voxel = std::strtod(v.c_str(), &end);
+			if (v.empty() || *end || !(o.voxel > 0.0) || !std::isfinite(o.voxel)) { std::cerr << "--voxel-size takes a finite, positive number, got `" << v << "`\n"; return EXIT_FAILURE; }
+		}
+		else if (s == "--save-prepared") o.save_prepared = v;
 		else { std::cerr << "unknown option " << s << "\n" << usage; return EXIT_FAILURE; }
 	}
 	if (o.truth.empty()) { std::cerr << "--against is required\n" << usage; return EXIT_FAILURE; }

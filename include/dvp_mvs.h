@@ -504,6 +504,43 @@ int dvp_cloud_evaluate(int device, const float* recon_xyz, long long num_recon, 
                        long long* used, float* d2_recon, float* d2_truth);
 const char* dvp_cloud_last_error(void);   /* the calling thread's last error of the two above */
 
+/* ---- the preparation in front of `apd --evaluate`'s distances (--transform, --crop, --voxel-size); the project's own definition
+ * (csrc/dvp_cloudprep.hpp, DESIGN.md "Cloud evaluation"), which follows the steps of the Tanks and Temples protocol and pins to no
+ * other library's bits ----------------------------------------------------------------------------------------------------------------
+ * Binary64 with one rounding per operator; input order is kept.  (1) A point with a non-finite coordinate is dropped.  (2) transform
+ * (16 row-major doubles m, or NULL): x' = ((m00*x + m01*y) + m02*z) + m03, y', z' alike; a point with a non-finite image is dropped.
+ * (3) crop (crop_axis w = 0, 1, 2; -1 = none): (u, v) = (1, 2), (0, 2), (0, 1); kept iff axis_min <= p[w] <= axis_max and an odd
+ * number of polygon edges (i, j = (i + 1) % n) have (Vi[v] < p[v] && Vj[v] >= p[v]) || (Vj[v] < p[v] && Vi[v] >= p[v]) and
+ * Vi[u] + (p[v] - Vi[v]) / (Vj[v] - Vi[v]) * (Vj[u] - Vi[u]) < p[u].  (4) voxel (edge s; 0 = none): per axis o = (minimum over the
+ * kept points) - s*0.5, t = (p - o) / s, i = floor(t), q = (uint64)floor((t - i) * 2^32); per voxel Q = the integer sum of q, n the
+ * count; centroid o + ((double)i + ((double)Q / (double)n) * 2^-32) * s; one point per voxel, ordered by the voxel's first point.
+ * (5) Every output coordinate is rounded to binary32 once.  With no option set the output is the finite input points, bit for bit. */
+typedef struct dvp_cloud_prep {
+	const double* transform;     /* 16 doubles, row-major, last row exactly 0 0 0 1; NULL = none */
+	int crop_axis;               /* 0, 1, 2; -1 = no crop */
+	double axis_min, axis_max;   /* both inclusive */
+	const double* polygon_xyz;   /* num_polygon vertices of three doubles each */
+	int num_polygon;             /* 3 ... 256 */
+	double voxel;                /* the voxel's edge; 0 = no down-sampling */
+} dvp_cloud_prep;
+/* One cloud prepared.  xyz_out has room for num points; first_index_out (may be NULL) likewise: first_index_out[k] is the input
+ * index of output point k, for a voxel that of its first point.  counts_out[4] = the points with finite coordinates, those left
+ * after the transform, those inside the crop, the output points.
+ * Errors: a null pointer, a count outside 0 ... 2^31 - 1, a non-finite matrix entry, a last row other than 0 0 0 1, a crop_axis
+ * outside -1 ... 2, fewer than 3 or more than 256 vertices, a non-finite vertex, axis_min > axis_max, a voxel that is negative or not
+ * finite, more than 2^30 points to down-sample, a cloud that extends over more than 2^21 - 2 voxels along an axis, no device memory.
+ * Host in, host out; safe from several threads. */
+int dvp_cloud_prepare(int device, const float* xyz, long long num, const dvp_cloud_prep* prep, float* xyz_out, long long* first_index_out,
+                      long long* counts_out);
+/* Both clouds prepared, each by its own description, then dvp_cloud_evaluate's definition on the prepared clouds, which stay on the
+ * device in between.  used[], d2_recon and d2_truth (room for num_recon / num_truth entries; may be NULL) refer to the prepared
+ * points in prepared order; counts_out[8] = the four counts of recon, then of truth.  Errors: those of dvp_cloud_prepare and of
+ * dvp_cloud_evaluate. */
+int dvp_cloud_evaluate_prepared(int device, const float* recon_xyz, long long num_recon, const dvp_cloud_prep* prep_recon, const float* truth_xyz,
+                                long long num_truth, const dvp_cloud_prep* prep_truth, const float* tolerances, int num_tol, long long* within_recon,
+                                long long* within_truth, long long* used, float* d2_recon, float* d2_truth, long long* counts_out);
+const char* dvp_cloud_prep_last_error(void);   /* the calling thread's last error of the two above */
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,7 +8,12 @@ synthetic surface cloud of the size of a ten-view full-size fusion (default 45 M
   --host          the serial host text (tests/cloudeval_host, grid walk) on the queries of a square of 1 / 16 of the side - 1 / 256
                   of the points - against the targets around them, scaled by the query counts and labelled as such
   --kd            scipy's cKDTree.query(..., distance_upper_bound=T, workers=16) in float64 on the same data, both directions
-usage: evaluate_timing.py [--device] [--host] [--kd] [POINTS [FORM_POINTS]]"""
+  --prepare       the preparation in front of the query (dvp_cloud_evaluate_prepared; lines go to profiles/evaluate_prepare.txt): the
+                  reconstruction moved by a rigid matrix and given its inverse, both clouds cropped with a concave 12-gon prism over
+                  the middle of the scene and down-sampled with voxels of half the smallest tolerance; the call as shipped against
+                  plain dvp_cloud_evaluate on the same clouds, the phases from a serialised run, and the serial host text
+                  (tests/cloudprep_host) on the first 1 / 16 of each cloud, scaled by the point counts and labelled as such
+usage: evaluate_timing.py [--device] [--host] [--kd] [--prepare] [POINTS [FORM_POINTS]]"""
 import importlib
 import os
 import subprocess
@@ -137,6 +142,57 @@ def kd_lines(lines, points):
     print(lines[-1], flush=True)
 
 
+def prepare_lines(lines, points):
+    import np_cloudprep as P
+    capi = importlib.import_module("dvp-mvs_amd").get_capi()
+    tol = N.DEFAULT_TOLERANCES
+    recon, truth, side = clouds(points)
+    m = P.rotation(25.0, -15.0, [3.0, -2.0, 1.5]).reshape(4, 4)
+    moved = np.ascontiguousarray((recon.astype(np.float64) @ m[:3, :3].T + m[:3, 3]).astype(np.float32))
+    inverse = np.linalg.inv(m).reshape(-1)
+    crop = P.crop_of(2, 1.0, 3.5, P.polygon_3d(2, 0.1 * side + 0.8 * side * np.array(P.CONCAVE_12)))
+    voxel = 0.5 * float(np.float32(tol[0]))
+    pr, pt = P.prep(inverse, crop, voxel), P.prep(None, crop, voxel)
+    capi.cloud_evaluate(np.zeros((1, 3), np.float32), np.zeros((1, 3), np.float32), tol)      # the runtime's start-up
+    os.environ.pop("DVP_CLOUD_TIMING", None)
+    plain, prepared = [], []
+    for _ in range(2):
+        t0 = time.perf_counter()
+        capi.cloud_evaluate(recon, truth, tol)
+        plain.append(1e3 * (time.perf_counter() - t0))
+    for _ in range(2):
+        t0 = time.perf_counter()
+        got = capi.cloud_evaluate_prepared(moved, truth, tol, pr, pt)
+        prepared.append(1e3 * (time.perf_counter() - t0))
+    os.environ["DVP_CLOUD_TIMING"] = "1"
+    t0 = time.perf_counter()
+    again, text = with_stderr(lambda: capi.cloud_evaluate_prepared(moved, truth, tol, pr, pt))
+    dt = time.perf_counter() - t0
+    os.environ.pop("DVP_CLOUD_TIMING", None)
+    assert all(np.array_equal(got[k], again[k]) for k in ("within_recon", "within_truth", "used", "counts"))
+    lines.append("device, %d + %d points on %.1f x %.1f m, transform + crop (12-gon prism) + voxel %.9g: plain dvp_cloud_evaluate on the unprepared clouds (wall time, two calls) %s ms; "
+                 "dvp_cloud_evaluate_prepared as shipped (wall time, two calls) %s ms; with DVP_CLOUD_TIMING=1, which waits for the stream after every phase, the call %.0f ms" % (
+                     points, points, side, side, voxel, " ".join("%.0f" % v for v in plain), " ".join("%.0f" % v for v in prepared), 1e3 * dt))
+    lines += ["  " + ln for ln in text.splitlines()]
+    lines.append("  counts (finite, after the transform, in the crop volume, output): reconstruction %s, ground truth %s; accuracy %s, completeness %s (percent)" % (
+        got["counts"][0].tolist(), got["counts"][1].tolist(), " ".join("%.3f" % (100 * v) for v in got["accuracy"]), " ".join("%.3f" % (100 * v) for v in got["completeness"])))
+    P.build_program()
+    part = points // 16
+    scaled, parts = 0.0, []
+    with tempfile.TemporaryDirectory() as tmp:
+        for name, xyz, one in (("reconstruction", moved, pr), ("ground truth", truth, pt)):
+            sub = xyz[:: 16][:part]      # every 16th point: the same volume at 1 / 16 of the density
+            t0 = time.perf_counter()
+            rc, err, out = P.serial(sub, tmp, **one)
+            dt = time.perf_counter() - t0
+            assert rc == 0, err
+            scaled += dt * points / len(sub)
+            parts.append("%s: every 16th point, %d points -> %d, %.1f s with the files' reading and writing" % (name, len(sub), out["counts"][3], dt))
+    lines.append("serial host text (tests/cloudprep_host prepare, one thread): %s; SCALED by the point counts to the whole clouds: %.0f s" % ("; ".join(parts), scaled))
+    for ln in lines[-(4 + len(text.splitlines())):]:
+        print(ln, flush=True)
+
+
 def main():
     args = [a for a in sys.argv[1:] if not a.startswith("--")]
     points = int(args[0]) if args else 45000000
@@ -148,6 +204,11 @@ def main():
         host_lines(lines, points)
     if "--kd" in sys.argv:
         kd_lines(lines, points)
+    if "--prepare" in sys.argv:
+        prepare_lines(lines, points)
+        with open(os.path.join(ROOT, "profiles", "evaluate_prepare.txt"), "a") as f:
+            f.write("\n".join(lines) + "\n")
+        return
     with open(os.path.join(ROOT, "profiles", "evaluate.txt"), "a") as f:
         f.write("\n".join(lines) + "\n")
 

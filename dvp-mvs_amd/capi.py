@@ -45,7 +45,8 @@ EXPORTS = ["dvp_ctx_create", "dvp_ctx_destroy", "dvp_ctx_reserve", "dvp_last_err
            "dvp_view_scores", "dvp_convert_image", "dvp_pairs_last_error",
            "dvp_undistort_image", "dvp_undistort_last_error",
            "dvp_cloud_distances", "dvp_cloud_evaluate", "dvp_cloud_last_error",
-           "dvp_cloud_prepare", "dvp_cloud_evaluate_prepared", "dvp_cloud_prep_last_error"]
+           "dvp_cloud_prepare", "dvp_cloud_evaluate_prepared", "dvp_cloud_prep_last_error",
+           "dvp_cloud_icp_step", "dvp_cloud_refine_alignment", "dvp_cloud_icp_last_error"]
 # ... and the one whose name holds a digit (a scan of the header for [a-z_] names does not see it)
 EXPORTS_WITH_DIGITS = ["dvp_upload_images_u8"]
 PREVIEW_DEPTH, PREVIEW_NORMAL, PREVIEW_WEAK = 1, 2, 4
@@ -174,6 +175,10 @@ def lib():
         L.dvp_cloud_evaluate_prepared.argtypes = [ci, vp, ll, vp, vp, ll, vp, vp, ci, vp, vp, vp, vp, vp, vp]
         L.dvp_cloud_prep_last_error.restype = ctypes.c_char_p
         L.dvp_cloud_prep_last_error.argtypes = []
+        L.dvp_cloud_icp_step.argtypes = [ci, vp, ll, vp, ll, vp, ctypes.c_float, vp, vp, vp, vp]
+        L.dvp_cloud_refine_alignment.argtypes = [ci, vp, ll, vp, ll, vp, vp, vp, ci, vp, vp, ci, vp]
+        L.dvp_cloud_icp_last_error.restype = ctypes.c_char_p
+        L.dvp_cloud_icp_last_error.argtypes = []
         _LIB = L
     return _LIB
 
@@ -850,3 +855,41 @@ def cloud_evaluate_prepared(recon, truth, tolerances, prep_recon=None, prep_trut
     if distances:
         out.update(d2_recon=dr[:counts[0, 3]].copy(), d2_truth=dt[:counts[1, 3]].copy())
     return out
+
+
+class DvpIcpStage(ctypes.Structure):
+    _fields_ = [("voxel", ctypes.c_double), ("max_distance", ctypes.c_double), ("max_iterations", ctypes.c_int)]
+
+
+class DvpIcpLog(ctypes.Structure):
+    _fields_ = [("stage", ctypes.c_int), ("step", ctypes.c_int), ("n_src", ctypes.c_longlong), ("n", ctypes.c_longlong), ("rmse", ctypes.c_double)]
+
+
+def cloud_icp_step(src, tgt, max_distance, increment=None, device=0):
+    """dict(nearest: (N,) int32 index of every source's corresponding target or -1, e: (N,) float32 its squared distance or +inf, sums:
+    (16,) float64 tree sums of the correspondences, count) of one ICP step on the GPU (include/dvp_mvs.h dvp_cloud_icp_step)"""
+    L = lib()
+    s, t = _cloud(src, "cloud_icp_step"), _cloud(tgt, "cloud_icp_step")
+    D = None if increment is None else np.ascontiguousarray(increment, np.float64).reshape(-1)
+    if D is not None and D.size != 16:
+        raise ValueError("an increment holds 16 numbers, got %d" % D.size)
+    nearest, e, sums, count = np.empty(len(s), np.int32), np.empty(len(s), np.float32), np.zeros(16, np.float64), np.zeros(1, np.int64)
+    if L.dvp_cloud_icp_step(device, _p(s), len(s), _p(t), len(t), _p(D), float(max_distance), _p(nearest), _p(e), _p(sums), _p(count)) != 0:
+        raise DvpError(L.dvp_cloud_icp_last_error().decode())
+    return dict(nearest=nearest, e=e, sums=sums, count=int(count[0]))
+
+
+def cloud_refine_alignment(recon, truth, stages, transform=None, crop=None, device=0):
+    """dict(matrix: (16,) float64 the refined transform of the reconstruction, log: [(stage, step, n_src, n, rmse)]) of the ICP stages
+    [(voxel, max_distance, max_iterations), ...] on the GPU, from the initial transform (None: identity), both clouds cropped by crop
+    (include/dvp_mvs.h dvp_cloud_refine_alignment)"""
+    L = lib()
+    r, t = _cloud(recon, "cloud_refine_alignment"), _cloud(truth, "cloud_refine_alignment")
+    pr, keep_r = _cloud_prep(transform, crop)
+    pt, keep_t = _cloud_prep(None, crop)
+    st = (DvpIcpStage * max(len(stages), 1))(*[DvpIcpStage(float(v), float(d), int(k)) for v, d, k in stages])
+    capacity = sum(max(int(k), 0) for _, _, k in stages) if len(stages) <= 8 else 0
+    log, count, out = (DvpIcpLog * max(capacity, 1))(), ctypes.c_int(0), np.zeros(16, np.float64)
+    if L.dvp_cloud_refine_alignment(device, _p(r), len(r), _p(t), len(t), ctypes.byref(pr), ctypes.byref(pt), st, len(stages), _p(out), log, capacity, ctypes.byref(count)) != 0:
+        raise DvpError(L.dvp_cloud_icp_last_error().decode())
+    return dict(matrix=out, log=[(g.stage, g.step, g.n_src, g.n, g.rmse) for g in log[:min(count.value, capacity)]])

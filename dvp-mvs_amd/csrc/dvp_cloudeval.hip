@@ -127,15 +127,6 @@ __global__ void __launch_bounds__(256) dvp_ce_scatter(const float* __restrict__ 
 	sorted[at] = make_float4(xyz[3 * (size_t)i], xyz[3 * (size_t)i + 1], xyz[3 * (size_t)i + 2], __uint_as_float(i));
 }
 
-// the slot of `key`, or mask + 1
-__device__ uint64_t find_slot(const unsigned long long* __restrict__ keys, uint64_t mask, uint64_t key) {
-	for (uint64_t s = hash_key(key) & mask;; s = (s + 1) & mask) {
-		const unsigned long long cur = keys[s];
-		if (cur == key) return s;
-		if (cur == kEmptyKey) return mask + 1;
-	}
-}
-
 // the work-group's counts: every lane brings `valid` and its clipped distance
 __device__ void add_counts(bool valid, float d2, const Tolerances& tol, uint32_t (*hits)[kMaxTolerances], unsigned long long* within) {
 	const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;

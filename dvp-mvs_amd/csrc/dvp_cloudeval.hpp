@@ -80,6 +80,17 @@ DVP_CHD uint64_t hash_key(uint64_t k) {
 	return k;
 }
 
+#if defined(__HIPCC__)
+// the slot of `key`, or mask + 1
+__device__ inline uint64_t find_slot(const unsigned long long* __restrict__ keys, uint64_t mask, uint64_t key) {
+	for (uint64_t s = hash_key(key) & mask;; s = (s + 1) & mask) {
+		const unsigned long long cur = keys[s];
+		if (cur == key) return s;
+		if (cur == kEmptyKey) return mask + 1;
+	}
+}
+#endif
+
 inline uint64_t table_capacity(uint64_t points) {
 	uint64_t cap = 64;
 	while (cap < 2 * points) cap <<= 1;

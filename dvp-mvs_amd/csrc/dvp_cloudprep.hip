@@ -14,6 +14,8 @@
 //   dvp_cp_first        point k emits iff k == first[slot]: ballot words and work-group counts again, then the same scan
 //   dvp_cp_emit         the emitting points store their voxel's centroid as binary32 and the input index, compacted
 //   dvp_cp_float_bounds minimum, maximum and finite count of a prepared cloud for the distance stage's grid (dvp_cloud_evaluate_prepared)
+// dvpcp::prepare_resident (dvp_cloudprep_run.h) is the same preparation for a raw cloud that lies in device memory already and a
+// prepared cloud that stays there (dvp_cloudicp.hip's stages).
 // Device memory: carved DevBlocks, one per stage whose size only the stage before can tell (input; kept points and table; output); the
 // first two are gone before the distances start.  The stream of a call is a StreamScope.  DVP_CLOUD_TIMING=1 waits after every phase
 // and prints the phases' times to stderr (tools/evaluate_timing.py).
@@ -26,6 +28,7 @@
 #include "../../include/dvp_mvs.h"
 #include "dvp_cloudeval_run.h"
 #include "dvp_cloudprep.hpp"
+#include "dvp_cloudprep_run.h"
 #include "dvp_devmem.hpp"
 
 namespace dvpcp {
@@ -386,7 +389,8 @@ struct Prepared {
 	const long long* index() const { return (const long long*)(out.as<uint8_t>() + o_index); }
 };
 
-std::string prepare_on_device(hipStream_t st, const float* xyz, long long num, const Prep& prep, Prepared* res, Laps* laps) {
+// `resident`: xyz is in device memory already and is read where it lies
+std::string prepare_on_device(hipStream_t st, const float* xyz, long long num, const Prep& prep, Prepared* res, Laps* laps, bool resident = false) {
 	std::vector<double> uv;
 	const PointRule rule = point_rule(prep, &uv);
 	const uint32_t n = (uint32_t)num;
@@ -402,18 +406,19 @@ std::string prepare_on_device(hipStream_t st, const float* xyz, long long num, c
 	// stage 1: which points are kept, and where
 	dvpmem::DevBlock in;
 	dvpmem::Carve carve;
-	const size_t o_xyz = carve.take((size_t)num * 12), o_uv = carve.take(2 * kMaxPolygon * 8), o_words = carve.take(nwords * 8), o_count = carve.take(nb * 4),
+	const size_t o_xyz = carve.take(resident ? 0 : (size_t)num * 12), o_uv = carve.take(2 * kMaxPolygon * 8), o_words = carve.take(nwords * 8), o_count = carve.take(nb * 4),
 	             o_start = carve.take(nb * 4), o_sums = carve.take((nsums + 1) * 4), o_stage = carve.take(4 * 8);
 	if (in.reserve(carve.total)) return "out of device memory (" + std::to_string(carve.total) + " bytes)";
 	uint8_t* a = in.as<uint8_t>();
-	bool ok = hipMemcpyAsync(a + o_xyz, xyz, (size_t)num * 12, hipMemcpyHostToDevice, st) == hipSuccess && hipMemsetAsync(a + o_stage, 0, 4 * 8, st) == hipSuccess;
+	bool ok = (resident || hipMemcpyAsync(a + o_xyz, xyz, (size_t)num * 12, hipMemcpyHostToDevice, st) == hipSuccess) && hipMemsetAsync(a + o_stage, 0, 4 * 8, st) == hipSuccess;
+	const float* in_xyz = resident ? xyz : (const float*)(a + o_xyz);
 	if (ok && !uv.empty()) ok = hipMemcpyAsync(a + o_uv, uv.data(), uv.size() * 8, hipMemcpyHostToDevice, st) == hipSuccess;
 	if (!ok) { (void)hipGetLastError(); return "upload failed"; }
 	laps->lap(st, "upload");
 	unsigned long long* words = (unsigned long long*)(a + o_words);
 	uint32_t* count = (uint32_t*)(a + o_count), *start = (uint32_t*)(a + o_start), *sums = (uint32_t*)(a + o_sums);
 	unsigned long long* stage = (unsigned long long*)(a + o_stage);
-	hipLaunchKernelGGL(dvp_cp_keep, grid_of(num), dim3(256), 0, st, (const float*)(a + o_xyz), n, rule, (const double*)(a + o_uv), words, count, stage);
+	hipLaunchKernelGGL(dvp_cp_keep, grid_of(num), dim3(256), 0, st, in_xyz, n, rule, (const double*)(a + o_uv), words, count, stage);
 	laps->lap(st, "keep");
 	launch_scan(st, count, nb, sums, start, (uint32_t*)(stage + 3));
 	unsigned long long host_stage[4];
@@ -427,7 +432,7 @@ std::string prepare_on_device(hipStream_t st, const float* xyz, long long num, c
 	float* out = res->out.as<float>();
 	long long* out_index = (long long*)(res->out.as<uint8_t>() + res->o_index);
 	if (prep.voxel == 0.0) {
-		hipLaunchKernelGGL(dvp_cp_compact, grid_of(num), dim3(256), 0, st, (const float*)(a + o_xyz), n, rule, words, start, (double*)nullptr, (uint32_t*)nullptr, out, out_index);
+		hipLaunchKernelGGL(dvp_cp_compact, grid_of(num), dim3(256), 0, st, in_xyz, n, rule, words, start, (double*)nullptr, (uint32_t*)nullptr, out, out_index);
 		if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) { (void)hipGetLastError(); return "the kept points could not be stored"; }
 		laps->lap(st, "compact");
 		res->num_out = res->counts[3] = nk;
@@ -448,7 +453,7 @@ std::string prepare_on_device(hipStream_t st, const float* xyz, long long num, c
 	uint8_t* b = work.as<uint8_t>();
 	double* kept = (double*)(b + o_kept);
 	uint32_t* source = (uint32_t*)(b + o_source);
-	hipLaunchKernelGGL(dvp_cp_compact, grid_of(num), dim3(256), 0, st, (const float*)(a + o_xyz), n, rule, words, start, kept, source, (float*)nullptr, (long long*)nullptr);
+	hipLaunchKernelGGL(dvp_cp_compact, grid_of(num), dim3(256), 0, st, in_xyz, n, rule, words, start, kept, source, (float*)nullptr, (long long*)nullptr);
 	laps->lap(st, "compact");
 	unsigned long long* extent = (unsigned long long*)(b + o_extent);
 	ok = hipMemsetAsync(extent, 0xff, 3 * 8, st) == hipSuccess && hipMemsetAsync(extent + 3, 0, 3 * 8, st) == hipSuccess;
@@ -487,6 +492,18 @@ std::string prepare_on_device(hipStream_t st, const float* xyz, long long num, c
 	return "";
 }
 
+// the bounds and the finite count of a prepared cloud; `extent` = 28 bytes of device memory.  false: it could not be done
+bool float_bounds_of(hipStream_t st, uint32_t* extent, const float* xyz, long long num, dvpce::Bounds* bounds) {
+	uint32_t host_extent[7];
+	bool ok = hipMemsetAsync(extent, 0xff, 3 * 4, st) == hipSuccess && hipMemsetAsync(extent + 3, 0, 4 * 4, st) == hipSuccess;
+	if (ok) hipLaunchKernelGGL(dvp_cp_float_bounds, grid_of(num), dim3(256), 0, st, xyz, (uint32_t)num, extent);
+	ok = ok && hipGetLastError() == hipSuccess && hipMemcpyAsync(host_extent, extent, sizeof host_extent, hipMemcpyDeviceToHost, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess;
+	if (!ok) { (void)hipGetLastError(); return false; }
+	bounds->finite = host_extent[6];
+	for (int a = 0; a < 3 && bounds->finite; ++a) { bounds->lo[a] = float_of(host_extent[a]); bounds->hi[a] = float_of(host_extent[3 + a]); }
+	return true;
+}
+
 std::string check_cloud(const float* xyz, long long num) {
 	if (num < 0 || num > dvpce::kMaxPoints) return "a cloud holds 0 ... 2^31 - 1 points, got " + std::to_string(num);
 	if (num > 0 && !xyz) return "the point arrays are required";
@@ -494,6 +511,23 @@ std::string check_cloud(const float* xyz, long long num) {
 }
 
 }   // namespace
+
+std::string dvpcp::prepare_resident(hipStream_t st, const float* dev_xyz, long long num, const Prep& prep, ResidentCloud* res) {
+	Prepared p;
+	Laps laps;
+	std::string what = prepare_on_device(st, dev_xyz, num, prep, &p, &laps, true);
+	if (!what.empty()) return what;
+	if (laps.on) fprintf(stderr, "prepare (resident) timing (%lld points, %lld out):%s\n", num, p.num_out, laps.report.c_str());
+	res->num = p.num_out;
+	res->bounds = dvpce::Bounds();
+	if (p.num_out) {
+		dvpmem::DevBlock extent;
+		if (extent.reserve(256)) return "out of device memory";
+		if (!float_bounds_of(st, extent.as<uint32_t>(), p.xyz(), p.num_out, &res->bounds)) return "the prepared cloud's bounds could not be made";
+	}
+	res->out = std::move(p.out);
+	return "";
+}
 
 extern "C" int dvp_cloud_prepare(int device, const float* xyz, long long num, const dvp_cloud_prep* prep, float* xyz_out, long long* first_index_out, long long* counts_out) {
 	const char* who = "dvp_cloud_prepare";
@@ -555,14 +589,7 @@ extern "C" int dvp_cloud_evaluate_prepared(int device, const float* recon_xyz, l
 		for (int k = 0; k < 4; ++k) counts_out[4 * c + k] = res[c].counts[k];
 		if (!res[c].num_out) continue;
 		// the prepared cloud's bounds for the distance stage's grid: a centroid or an image may have overflowed binary32
-		uint32_t* extent = (uint32_t*)(extent_block.as<uint8_t>() + 256 * c);
-		uint32_t host_extent[7];
-		bool ok = hipMemsetAsync(extent, 0xff, 3 * 4, st) == hipSuccess && hipMemsetAsync(extent + 3, 0, 4 * 4, st) == hipSuccess;
-		if (ok) hipLaunchKernelGGL(dvp_cp_float_bounds, grid_of(res[c].num_out), dim3(256), 0, st, res[c].xyz(), (uint32_t)res[c].num_out, extent);
-		ok = ok && hipGetLastError() == hipSuccess && hipMemcpyAsync(host_extent, extent, sizeof host_extent, hipMemcpyDeviceToHost, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess;
-		if (!ok) { (void)hipGetLastError(); return prep_fail(who, "the prepared cloud's bounds could not be made"); }
-		bounds[c].finite = host_extent[6];
-		for (int a = 0; a < 3 && bounds[c].finite; ++a) { bounds[c].lo[a] = float_of(host_extent[a]); bounds[c].hi[a] = float_of(host_extent[3 + a]); }
+		if (!float_bounds_of(st, (uint32_t*)(extent_block.as<uint8_t>() + 256 * c), res[c].xyz(), res[c].num_out, &bounds[c])) return prep_fail(who, "the prepared cloud's bounds could not be made");
 		laps.lap(st, "bounds of the prepared");
 	}
 	if (laps.on) fprintf(stderr, "%s timing (%lld + %lld points, %lld + %lld prepared):%s\n", who, num[0], num[1], res[0].num_out, res[1].num_out, laps.report.c_str());

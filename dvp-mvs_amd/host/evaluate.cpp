@@ -1,15 +1,20 @@
 // evaluate.cpp — `apd --evaluate recon.ply --against truth.ply` (evaluate.h): both clouds read, prepared when --transform, --crop or
 // --voxel-size ask for it (csrc/dvp_cloudprep.hpp), the two directions counted on the device (dvp_cloud_evaluate, or
 // dvp_cloud_evaluate_prepared) or by the same text on the host (csrc/dvp_cloudeval.hpp: the double loop up to 2^24 pairs, the grid
-// walked serially above), and the report, whose figures come from the integer counts alone.
+// walked serially above), and the report, whose figures come from the integer counts alone.  --refine-alignment first refines the
+// reconstruction's matrix by ICP stages (csrc/dvp_cloudicp.hpp: dvp_cloud_refine_alignment, or the same text on the host), and the
+// evaluation takes the refined matrix as if --transform had given it.
 #include "evaluate.h"
 
 #include <cstdio>
+#include <cstdlib>
 #include <fstream>
 #include <new>
+#include <sstream>
 
 #include "../../include/dvp_mvs.h"
 #include "../csrc/dvp_cloudeval.hpp"
+#include "../csrc/dvp_cloudicp.hpp"
 
 std::string EvaluateReport(const EvaluateOptions& o, const long long num[2], const long long used[2], const long long* within_recon, const long long* within_truth,
                            const long long* counts) {
@@ -39,6 +44,55 @@ bool WritePlyVertices(const std::string& file, const std::vector<float>& xyz, st
 	return true;
 }
 
+bool ParseRefineStages(const std::string& list, std::vector<dvpci::Stage>* stages, std::string* error) {
+	stages->clear();
+	std::stringstream in(list);
+	std::string item;
+	while (std::getline(in, item, ',')) {
+		std::stringstream parts(item);
+		std::string word[3], rest;
+		double v[3];
+		bool ok = std::getline(parts, word[0], ':') && std::getline(parts, word[1], ':') && std::getline(parts, word[2], ':') && !std::getline(parts, rest, ':');
+		for (int k = 0; k < 3 && ok; ++k) {
+			char* end = nullptr;
+			v[k] = strtod(word[k].c_str(), &end);
+			ok = !word[k].empty() && !*end;
+		}
+		if (ok) ok = v[2] >= -1e9 && v[2] <= 1e9 && v[2] == floor(v[2]);   // (a NaN fails; the cast below is then in range)
+		if (!ok) { *error = "--refine-alignment takes VOXEL:DISTANCE:ITERATIONS separated by commas, got `" + item + "`"; return false; }
+		stages->push_back(dvpci::Stage{ v[0], v[1], (int)v[2] });
+	}
+	if (stages->empty() || list.back() == ',') { *error = "--refine-alignment takes VOXEL:DISTANCE:ITERATIONS separated by commas, got `" + list + "`"; return false; }
+	if (stages->size() > (size_t)dvpci::kMaxStages) { *error = "--refine-alignment takes at most 8 stages, got " + std::to_string(stages->size()); return false; }
+	return true;
+}
+
+bool WriteTransformFile(const std::string& file, const double m[16], std::string* error) {
+	std::ofstream out(file, std::ios::binary);
+	char text[128];
+	for (int r = 0; r < 4; ++r) {
+		snprintf(text, sizeof text, "%.17g %.17g %.17g %.17g\n", m[4 * r], m[4 * r + 1], m[4 * r + 2], m[4 * r + 3]);
+		out << text;
+	}
+	if (!out.good()) { *error = "cannot write " + file; return false; }
+	return true;
+}
+
+std::string AlignmentReport(const std::vector<dvpci::LogRecord>& log, const double m[16]) {
+	std::string report;
+	char text[256];
+	for (size_t k = 0; k < log.size(); ++k) {
+		if (k + 1 < log.size() && log[k + 1].stage == log[k].stage) continue;   // the stage's last step speaks for it
+		snprintf(text, sizeof text, "alignment stage %d: %d steps, %lld of %lld correspondences, rmse %.9g\n", log[k].stage, log[k].step, log[k].n, log[k].n_src, log[k].rmse);
+		report += text;
+	}
+	for (int r = 0; r < 4; ++r) {
+		snprintf(text, sizeof text, "alignment %.17g %.17g %.17g %.17g\n", m[4 * r], m[4 * r + 1], m[4 * r + 2], m[4 * r + 3]);
+		report += text;
+	}
+	return report;
+}
+
 static bool EvaluateCloudsOrThrow(const EvaluateOptions& o, std::string* report, std::string* error);
 
 bool EvaluateClouds(const EvaluateOptions& o, std::string* report, std::string* error) {
@@ -66,6 +120,7 @@ static dvp_cloud_prep AbiPrep(const dvpcp::Prep& p) {
 static bool EvaluateCloudsOrThrow(const EvaluateOptions& o, std::string* report, std::string* error) {
 	const bool prepares = o.prepares();
 	if (!o.save_prepared.empty() && !prepares) { *error = "--save-prepared needs --transform, --crop or --voxel-size"; return false; }
+	if (!o.save_transform.empty() && o.refine.empty()) { *error = "--save-transform needs --refine-alignment"; return false; }
 	dvpcp::Prep prep[2];   // recon, truth
 	if (!o.transform_file.empty()) {
 		if (!ReadTransformFile(o.transform_file, prep[0].m, error)) return false;
@@ -88,6 +143,46 @@ static bool EvaluateCloudsOrThrow(const EvaluateOptions& o, std::string* report,
 	const std::vector<float>* cloud[2] = { &recon, &truth };
 	const long long num[2] = { (long long)(recon.size() / 3), (long long)(truth.size() / 3) };
 	const int K = (int)o.tolerances.size();
+	std::string alignment;
+	if (!o.refine.empty()) {   // the stages first: prep[0]'s matrix becomes the refined one
+		std::vector<dvpci::LogRecord> log;
+		double M[16];
+		for (int k = 0; k < 16; ++k) M[k] = prep[0].m[k];
+		if (o.on_gpu) {
+			const dvp_cloud_prep abi[2] = { AbiPrep(prep[0]), AbiPrep(prep[1]) };
+			std::vector<dvp_icp_stage> stages;
+			int capacity = 0, count = 0;
+			for (const dvpci::Stage& s : o.refine) {
+				stages.push_back(dvp_icp_stage{ s.voxel, s.max_distance, s.max_iterations });
+				capacity += s.max_iterations > 0 && s.max_iterations <= dvpci::kMaxIterations ? s.max_iterations : 0;
+			}
+			std::vector<dvp_icp_log> records((size_t)capacity + 1);
+			if (dvp_cloud_refine_alignment(o.device, recon.data(), num[0], truth.data(), num[1], &abi[0], &abi[1], stages.data(), (int)stages.size(), M, records.data(), capacity,
+			                               &count) != 0) {
+				*error = dvp_cloud_icp_last_error();
+				return false;
+			}
+			for (int k = 0; k < count && k < capacity; ++k) log.push_back(dvpci::LogRecord{ records[(size_t)k].stage, records[(size_t)k].step, records[(size_t)k].n_src, records[(size_t)k].n, records[(size_t)k].rmse });
+		} else {
+			dvpci::HostBackend be;
+			be.xyz[0] = recon.data(); be.xyz[1] = truth.data();
+			be.num[0] = num[0]; be.num[1] = num[1];
+			for (int c = 0; c < 2; ++c) {
+				be.prep[c] = prep[c];
+				be.prep[c].voxel = 0.0;
+			}
+			be.R = dvpci::cells_radius_from_environment();
+			std::string what = be.R ? "" : "DVP_CLOUD_ICP_CELLS takes 27 or 125";
+			if (what.empty()) what = dvpci::refine(be, o.refine.data(), (int)o.refine.size(), M, &log);
+			if (!what.empty()) { *error = what; return false; }
+		}
+		for (int k = 0; k < 16; ++k) prep[0].m[k] = M[k];
+		prep[0].has_transform = true;
+		const std::string what = dvpcp::check_prep(prep[0]);
+		if (!what.empty()) { *error = "the refined alignment: " + what; return false; }
+		if (!o.save_transform.empty() && !WriteTransformFile(o.save_transform, M, error)) return false;
+		alignment = AlignmentReport(log, M);
+	}
 	long long within_recon[dvpce::kMaxTolerances] = {}, within_truth[dvpce::kMaxTolerances] = {}, used[2] = { 0, 0 }, counts[8] = {};
 	std::vector<float> prepared[2];
 	if (o.on_gpu && !prepares) {
@@ -118,7 +213,7 @@ static bool EvaluateCloudsOrThrow(const EvaluateOptions& o, std::string* report,
 		if (!what.empty()) { *error = what; return false; }
 	}
 	if (!o.save_prepared.empty() && (!WritePlyVertices(o.save_prepared + "recon.ply", prepared[0], error) || !WritePlyVertices(o.save_prepared + "truth.ply", prepared[1], error))) return false;
-	*report = EvaluateReport(o, num, used, within_recon, within_truth, prepares ? counts : nullptr);
+	*report = alignment + EvaluateReport(o, num, used, within_recon, within_truth, prepares ? counts : nullptr);
 	if (!o.out.empty()) {
 		std::ofstream out(o.out, std::ios::binary);
 		out << *report;

@@ -6,6 +6,7 @@
 #include <string>
 #include <vector>
 
+#include "../csrc/dvp_cloudicp.hpp"
 #include "../csrc/dvp_cloudprep.hpp"
 
 // The vertices of a PLY file as packed x y z floats.  Formats binary_little_endian and ascii; x, y, z float or double (a double is
@@ -24,8 +25,19 @@ struct EvaluateOptions {
 	std::string crop_file;           // --crop: a SelectionPolygonVolume JSON, applied to both clouds after the transform
 	double voxel = 0.0;              // --voxel-size: both clouds, each on its own grid
 	std::string save_prepared;       // --save-prepared PREFIX: <PREFIX>recon.ply and <PREFIX>truth.ply
-	bool prepares() const { return !transform_file.empty() || !crop_file.empty() || voxel != 0.0; }
+	// the alignment refined before the clouds are measured (csrc/dvp_cloudicp.hpp): the evaluation then takes the refined matrix as if
+	// --transform had given it
+	std::vector<dvpci::Stage> refine;   // --refine-alignment V:D:N[,V:D:N...]: ICP stages (voxel, distance, iterations), in order
+	std::string save_transform;         // --save-transform FILE: the refined matrix, a file --transform reads
+	bool prepares() const { return !transform_file.empty() || !crop_file.empty() || voxel != 0.0 || !refine.empty(); }
 };
+// V:D:N[,V:D:N...] -> stages; false: *error says what is wrong (another shape, a word that is no number, more than 8 stages; the
+// numbers' ranges are checked where the stages run)
+bool ParseRefineStages(const std::string& list, std::vector<dvpci::Stage>* stages, std::string* error);
+// 16 numbers as %.17g, four per line: a file ReadTransformFile takes and reads back to the same bits
+bool WriteTransformFile(const std::string& file, const double m[16], std::string* error);
+// the report's lines about a refinement: one per stage, then the matrix's four rows
+std::string AlignmentReport(const std::vector<dvpci::LogRecord>& log, const double m[16]);
 // 16 numbers separated by whitespace; false: *error says what is wrong (another count, a word that is no number, a non-finite entry, a last row other than 0 0 0 1)
 bool ReadTransformFile(const std::string& file, double m[16], std::string* error);
 // Open3D's SelectionPolygonVolume JSON -> prep's crop; false: *error says what is wrong (malformed JSON, a missing field, fewer than 3 or more than 256 vertices ...)

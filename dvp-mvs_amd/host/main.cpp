@@ -478,8 +478,12 @@ int ConvertMain(int argc, char** argv) {
 int EvaluateMain(int argc, char** argv) {
 	const char* usage = "USAGE: apd --evaluate recon.ply --against truth.ply [--tolerances 0.01,0.02,0.05,0.1,0.2,0.5] [--evaluate-on gpu|host] [--gpu N] [--out FILE]\n"
 	                    "       [--transform FILE] [--crop FILE] [--voxel-size S] [--save-prepared PREFIX]\n"
+	                    "       [--refine-alignment V:D:N[,V:D:N...]] [--save-transform FILE]\n"
 	                    "  --transform: 16 numbers (4 x 4, row-major) applied to the reconstruction; --crop: a SelectionPolygonVolume JSON, both clouds;\n"
-	                    "  --voxel-size: both clouds down-sampled to one centroid per voxel of edge S; --save-prepared: <PREFIX>recon.ply and <PREFIX>truth.ply\n";
+	                    "  --voxel-size: both clouds down-sampled to one centroid per voxel of edge S; --save-prepared: <PREFIX>recon.ply and <PREFIX>truth.ply\n"
+	                    "  --refine-alignment: ICP stages (voxel V, largest correspondence distance D, at most N steps) that refine the transform (the identity\n"
+	                    "  without --transform) before the clouds are measured; Tanks and Temples' choice for a scene threshold t: t:80t:20,t/2:20t:20,t/2:2t:20;\n"
+	                    "  --save-transform: the refined 4 x 4 matrix, a file --transform reads\n";
 	if (argc < 3 || argv[2][0] == '-') { std::cerr << usage; return EXIT_FAILURE; }
 	EvaluateOptions o;
 	o.recon = argv[2];
@@ -514,6 +518,11 @@ int EvaluateMain(int argc, char** argv) {
 			if (v.empty() || *end || !(o.voxel > 0.0) || !std::isfinite(o.voxel)) { std::cerr << "--voxel-size takes a finite, positive number, got `" << v << "`\n"; return EXIT_FAILURE; }
 		}
 		else if (s == "--save-prepared") o.save_prepared = v;
+		else if (s == "--refine-alignment") {
+			std::string what;
+			if (!ParseRefineStages(v, &o.refine, &what)) { std::cerr << what << "\n"; return EXIT_FAILURE; }
+		}
+		else if (s == "--save-transform") o.save_transform = v;
 		else { std::cerr << "unknown option " << s << "\n" << usage; return EXIT_FAILURE; }
 	}
 	if (o.truth.empty()) { std::cerr << "--against is required\n" << usage; return EXIT_FAILURE; }

@@ -541,6 +541,48 @@ int dvp_cloud_evaluate_prepared(int device, const float* recon_xyz, long long nu
                                 long long* within_truth, long long* used, float* d2_recon, float* d2_truth, long long* counts_out);
 const char* dvp_cloud_prep_last_error(void);   /* the calling thread's last error of the two above */
 
+/* ---- `apd --evaluate --refine-alignment`: point-to-point ICP that refines the matrix which brings the reconstruction onto the ground
+ * truth; the project's own definition (csrc/dvp_cloudicp.hpp, DESIGN.md "Cloud evaluation") --------------------------------------------
+ * One step's device part.  increment D: 16 row-major doubles, last row exactly 0 0 0 1, NULL = identity.  Per source i: p' = D p in
+ * binary64 (the preparation's formula), r = p' rounded to binary32; j(i) = the target that minimises e = (dx*dx + dy*dy) + dz*dz,
+ * d = r - q_j, in binary32, the smallest j among equal minima; i corresponds iff e <= max_distance * max_distance (binary32).  A source
+ * with a non-finite coordinate or a non-finite r never corresponds.  nearest_out[i] = j(i) and e_out[i] = e for a corresponding
+ * source, -1 and +inf for every other (both may be NULL).  sums_out[16] = the sums over the corresponding sources of a = p' - c (3),
+ * b = q_j - c (3), a_r * b_c (9, row-major) and e, c = the centre of the targets' bounds; each sum is the balanced pairwise tree over
+ * the source indices padded with +0.0 to a power of two, so it is the same bits on any device.  *count_out = the corresponding sources.
+ * Errors: a null pointer, a count outside 0 ... 2^31 - 1, a target with a non-finite coordinate, a non-finite increment or a last row
+ * other than 0 0 0 1, a max_distance that is not finite and positive or whose binary32 square is not normal, targets that extend
+ * over too many cells of max_distance, more than 2^30 sources in the wave form of the search (its table of the sources keeps a slot
+ * in 32 bits; the lane form takes 2^31 - 1), more than 2^30 targets, no device memory.  Host in, host out; safe from several threads.
+ * The search form (DVP_CLOUD_QUERY=wave|lane, default wave) and the neighbourhood (DVP_CLOUD_ICP_CELLS=27|125, default 27) are read
+ * from the environment when a call begins; the result does not depend on either. */
+int dvp_cloud_icp_step(int device, const float* src_xyz, long long n_src, const float* tgt_xyz, long long n_tgt, const double* increment, float max_distance,
+                       int* nearest_out, float* e_out, double* sums_out, long long* count_out);
+typedef struct dvp_icp_stage {
+	double voxel;          /* both clouds down-sampled at this edge for the stage; 0 = not */
+	double max_distance;   /* correspondences reach this far (rounded to binary32) */
+	int max_iterations;    /* 1 ... 1000 */
+} dvp_icp_stage;
+typedef struct dvp_icp_log {
+	int stage, step;       /* stage from 0, step from 1 */
+	long long n_src, n;    /* the stage's prepared sources, the corresponding ones of this step (n < 3 ends the stage) */
+	double rmse;           /* sqrt(sum of e / n); 0 for n = 0 */
+} dvp_icp_log;
+/* The stages in order.  M = prep_recon->transform (NULL: identity).  Per stage: src = the reconstruction prepared with transform M,
+ * prep_recon's crop and the stage's voxel, tgt = the ground truth prepared with prep_truth's crop and the stage's voxel (the voxel and,
+ * for the truth, the transform fields of the descriptions are ignored; a NULL description crops nothing); D = I; up to max_iterations
+ * steps, each: dvp_cloud_icp_step's sums of D, one log record, then the stage ends when n < 3 or, from the second step on, when
+ * fitness = n / n_src and rmse both changed by less than 1e-6; else D <- E D with E the rigid motion that minimises the squared
+ * distances of the correspondences (Horn's quaternion method).  After the stage M <- D M.  transform_out[16] = the final M.  The
+ * first log_capacity records are stored, *log_count = their total.  Both raw clouds are uploaded once.
+ * Errors: those above and of dvp_cloud_prepare, num_stages outside 1 ... 8, a negative or non-finite voxel, max_iterations outside
+ * 1 ... 1000, a prepared ground truth with a point that overflows binary32, more than 2^30 reconstruction points in the wave form.
+ * Safe from several threads. */
+int dvp_cloud_refine_alignment(int device, const float* recon_xyz, long long n_recon, const float* truth_xyz, long long n_truth, const dvp_cloud_prep* prep_recon,
+                               const dvp_cloud_prep* prep_truth, const dvp_icp_stage* stages, int num_stages, double* transform_out, dvp_icp_log* log, int log_capacity,
+                               int* log_count);
+const char* dvp_cloud_icp_last_error(void);   /* the calling thread's last error of the two above */
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,7 +13,16 @@ synthetic surface cloud of the size of a ten-view full-size fusion (default 45 M
                   the middle of the scene and down-sampled with voxels of half the smallest tolerance; the call as shipped against
                   plain dvp_cloud_evaluate on the same clouds, the phases from a serialised run, and the serial host text
                   (tests/cloudprep_host) on the first 1 / 16 of each cloud, scaled by the point counts and labelled as such
-usage: evaluate_timing.py [--device] [--host] [--kd] [--prepare] [POINTS [FORM_POINTS]]"""
+  --refine        the alignment refinement (dvp_cloud_refine_alignment; lines go to profiles/evaluate_refine.txt): the reconstruction
+                  moved by a rigid matrix and given its inverse, perturbed by a tenth of a degree and a few centimetres, the three
+                  protocol stages at tau = 1 cm; the call as shipped and the laps of a serialised run, both search forms and both
+                  neighbourhoods at FORM_POINTS and the wave form with both neighbourhoods at POINTS (the lane form stays at
+                  FORM_POINTS, as under --device), and dvp_cloud_evaluate / dvp_cloud_evaluate_prepared at POINTS on the clouds and with the
+                  options of --device and --prepare, for comparison with the profiles they have
+  --refine-host   no device: the serial host text (tests/cloudicp_host refine) on the sources of a square of 1 / 32 of the side against
+                  the targets within the first stage's distance around it, scaled by the source counts and labelled as such, and a
+                  float64 ICP around scipy's cKDTree at FORM_POINTS
+usage: evaluate_timing.py [--device] [--host] [--kd] [--prepare] [--refine] [--refine-host] [POINTS [FORM_POINTS]]"""
 import importlib
 import os
 import subprocess
@@ -193,6 +202,134 @@ def prepare_lines(lines, points):
         print(ln, flush=True)
 
 
+TAU = 0.01
+REFINE_STAGES = [(TAU, 80 * TAU, 20), (TAU / 2, 20 * TAU, 20), (TAU / 2, 2 * TAU, 20)]
+
+
+def refine_scene(points):
+    """(moved reconstruction, truth, the known matrix that brings it back, that matrix perturbed, side)"""
+    import np_cloudprep as P
+    recon, truth, side = clouds(points)
+    m = P.rotation(25.0, -15.0, [3.0, -2.0, 1.5]).reshape(4, 4)
+    moved = np.ascontiguousarray((recon.astype(np.float64) @ m[:3, :3].T + m[:3, 3]).astype(np.float32))
+    known = np.linalg.inv(m)
+    wrong = P.rotation(0.1, -0.05, [0.03, -0.02, 0.025]).reshape(4, 4)
+    return moved, truth, known.reshape(-1), (wrong @ known).reshape(-1), side
+
+
+def refine_lines(lines, points, form_points):
+    import np_cloudicp as C
+    import np_cloudprep as P
+    capi = importlib.import_module("dvp-mvs_amd").get_capi()
+    tol = N.DEFAULT_TOLERANCES
+    capi.cloud_evaluate(np.zeros((1, 3), np.float32), np.zeros((1, 3), np.float32), tol)      # the runtime's start-up
+    for n, forms in ((form_points, (("wave", "125"), ("wave", "27"), ("lane", "125"), ("lane", "27"))), (points, (("wave", "27"), ("wave", "125")))):
+        moved, truth, known, initial, side = refine_scene(n)
+        first = None
+        for form, cells in forms:
+            os.environ["DVP_CLOUD_QUERY"], os.environ["DVP_CLOUD_ICP_CELLS"] = form, cells
+            os.environ.pop("DVP_CLOUD_TIMING", None)
+            t0 = time.perf_counter()
+            got = capi.cloud_refine_alignment(moved, truth, REFINE_STAGES, initial)
+            plain = 1e3 * (time.perf_counter() - t0)
+            os.environ["DVP_CLOUD_TIMING"] = "1"
+            t0 = time.perf_counter()
+            again, text = with_stderr(lambda: capi.cloud_refine_alignment(moved, truth, REFINE_STAGES, initial))
+            dt = 1e3 * (time.perf_counter() - t0)
+            os.environ.pop("DVP_CLOUD_TIMING", None)
+            assert again["matrix"].tobytes() == got["matrix"].tobytes() and (first is None or first["matrix"].tobytes() == got["matrix"].tobytes())
+            first = got
+            lines.append("device, %d + %d points on %.1f x %.1f m, %s form, %s cells: dvp_cloud_refine_alignment as shipped (wall time) %.0f ms; with DVP_CLOUD_TIMING=1, which waits "
+                         "for the stream after every phase, %.0f ms; steps per stage %s; start %.4f deg %.4f m, refined %.6f deg %.6f m from the known matrix" % (
+                             (n, n, side, side, form, cells, plain, dt, [len([g for g in got["log"] if g[0] == s]) for s in range(3)]) + C.motion_errors(initial, known) + C.motion_errors(got["matrix"], known)))
+            steps = [ln for ln in text.splitlines() if "step timing" in ln]
+            for s in range(3):      # the first step of every stage, in full; the laps of the others differ little
+                at = sum(len([g for g in got["log"] if g[0] == k]) for k in range(s))
+                if at < len(steps):
+                    lines.append("  stage %d (voxel %.9g, distance %.9g), %d sources, rmse %.6f -> %.6f: %s" % (
+                        s, REFINE_STAGES[s][0], REFINE_STAGES[s][1], got["log"][at][2], got["log"][at][4], [g for g in got["log"] if g[0] == s][-1][4], steps[at]))
+            lines += ["  " + ln for ln in text.splitlines() if "step timing" not in ln][:6]
+            for ln in lines[-10:]:
+                print(ln, flush=True)
+        del os.environ["DVP_CLOUD_QUERY"], os.environ["DVP_CLOUD_ICP_CELLS"]
+        if n == points:      # the two existing entries beside it, for comparison with profiles/evaluate.txt and evaluate_prepare.txt
+            t = []
+            recon = clouds(n)[0]
+            for _ in range(2):
+                t0 = time.perf_counter()
+                capi.cloud_evaluate(recon, truth, tol)
+                t.append(1e3 * (time.perf_counter() - t0))
+            del recon
+            crop = P.crop_of(2, 1.0, 3.5, P.polygon_3d(2, 0.1 * side + 0.8 * side * np.array(P.CONCAVE_12)))
+            pr, pt = P.prep(known, crop, 0.5 * float(np.float32(tol[0]))), P.prep(None, crop, 0.5 * float(np.float32(tol[0])))
+            for _ in range(2):
+                t0 = time.perf_counter()
+                res = capi.cloud_evaluate_prepared(moved, truth, tol, pr, pt)
+                t.append(1e3 * (time.perf_counter() - t0))
+            lines.append("  beside it: dvp_cloud_evaluate on the unmoved clouds (wall time, two calls) %.0f %.0f ms; dvp_cloud_evaluate_prepared with the known matrix, the 12-gon prism and voxel %.9g (two calls) "
+                         "%.0f %.0f ms; accuracy %s (percent)" % (t[0], t[1], 0.5 * float(np.float32(tol[0])), t[2], t[3], " ".join("%.3f" % (100 * v) for v in res["accuracy"])))
+            print(lines[-1], flush=True)
+
+
+def refine_host_lines(lines, points, form_points):
+    import np_cloudicp as C
+    import np_cloudprep as P
+    recon, truth, side = clouds(points)
+    m = np.linalg.inv(refine_scene(1000)[2].reshape(4, 4))
+    d = REFINE_STAGES[0][1]
+    lo, hi = side / 2, side / 2 + side / 32
+
+    def inside(p, margin):
+        return (p[:, :2] >= lo - margin).all(1) & (p[:, :2] < hi + margin).all(1)
+    src = recon[inside(recon, 0.0)]
+    moved = np.ascontiguousarray((src.astype(np.float64) @ m[:3, :3].T + m[:3, 3]).astype(np.float32))
+    tgt = truth[inside(truth, 1.01 * d)]
+    _, _, known, initial, _ = refine_scene(1000)
+    C.build_program()
+    with tempfile.TemporaryDirectory() as tmp:
+        t0 = time.perf_counter()
+        rc, err, got = C.serial_refine(moved, tgt, tmp, initial, None, REFINE_STAGES)
+        dt = time.perf_counter() - t0
+    assert rc == 0, err
+    lines.append("serial host text (tests/cloudicp_host refine, one thread) on the %d sources of a %.2f m square in the middle of the %d + %d points against the %d targets within %.9g m "
+                 "around it: %.1f s for %s steps per stage; SCALED by the source counts to the whole clouds: %.0f s" % (
+                     len(src), hi - lo, points, points, len(tgt), d, dt, [len([g for g in got["log"] if g[0] == s]) for s in range(3)], dt * points / len(src)))
+    print(lines[-1], flush=True)
+    try:
+        from scipy.spatial import cKDTree
+    except ImportError:
+        lines.append("scipy is not importable here: no cKDTree line")
+        return
+    moved, truth, known, initial, side = refine_scene(form_points)
+    t0 = time.perf_counter()
+    M, steps = np.asarray(initial, np.float64).reshape(4, 4), []
+    for v, dist, k in REFINE_STAGES:
+        s64 = P.prepare(moved, M.reshape(-1), None, v)["xyz"].astype(np.float64)
+        t64 = P.prepare(truth, None, None, v)["xyz"].astype(np.float64)
+        tree = cKDTree(t64)
+        D, last = np.eye(4), None
+        for it in range(1, k + 1):
+            p = s64 @ D[:3, :3].T + D[:3, 3]
+            e, j = tree.query(p, distance_upper_bound=dist, workers=16)
+            has = np.isfinite(e)
+            now = (has.mean(), np.sqrt((e[has] ** 2).mean()))
+            if last is not None and abs(now[0] - last[0]) < 1e-6 and abs(now[1] - last[1]) < 1e-6:
+                break
+            last = now
+            a, b = p[has], t64[j[has]]
+            U, _, Vt = np.linalg.svd((a - a.mean(0)).T @ (b - b.mean(0)))
+            R = Vt.T @ np.diag([1.0, 1.0, np.sign(np.linalg.det(Vt.T @ U.T))]) @ U.T
+            E = np.eye(4)
+            E[:3, :3], E[:3, 3] = R, b.mean(0) - R @ a.mean(0)
+            D = E @ D
+        steps.append(it)
+        M = D @ M
+    dt = time.perf_counter() - t0
+    lines.append("float64 ICP around scipy cKDTree.query(..., distance_upper_bound=d, workers=16) with numpy's preparation, %d + %d points: %.1f s for %s steps per stage; refined %.6f deg "
+                 "%.6f m from the known matrix" % ((form_points, form_points, dt, steps) + C.motion_errors(M.reshape(-1), known)))
+    print(lines[-1], flush=True)
+
+
 def main():
     args = [a for a in sys.argv[1:] if not a.startswith("--")]
     points = int(args[0]) if args else 45000000
@@ -204,6 +341,14 @@ def main():
         host_lines(lines, points)
     if "--kd" in sys.argv:
         kd_lines(lines, points)
+    if "--refine" in sys.argv or "--refine-host" in sys.argv:
+        if "--refine" in sys.argv:
+            refine_lines(lines, points, form_points)
+        else:
+            refine_host_lines(lines, points, form_points)
+        with open(os.path.join(ROOT, "profiles", "evaluate_refine.txt"), "a") as f:
+            f.write("\n".join(lines) + "\n")
+        return
     if "--prepare" in sys.argv:
         prepare_lines(lines, points)
         with open(os.path.join(ROOT, "profiles", "evaluate_prepare.txt"), "a") as f:

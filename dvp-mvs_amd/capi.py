@@ -46,7 +46,8 @@ EXPORTS = ["dvp_ctx_create", "dvp_ctx_destroy", "dvp_ctx_reserve", "dvp_last_err
            "dvp_undistort_image", "dvp_undistort_last_error",
            "dvp_cloud_distances", "dvp_cloud_evaluate", "dvp_cloud_last_error",
            "dvp_cloud_prepare", "dvp_cloud_evaluate_prepared", "dvp_cloud_prep_last_error",
-           "dvp_cloud_icp_step", "dvp_cloud_refine_alignment", "dvp_cloud_icp_last_error"]
+           "dvp_cloud_icp_step", "dvp_cloud_refine_alignment", "dvp_cloud_icp_last_error",
+           "dvp_cloud_scan_gaps", "dvp_cloud_evaluate_scans", "dvp_cloud_scan_last_error"]
 # ... and the one whose name holds a digit (a scan of the header for [a-z_] names does not see it)
 EXPORTS_WITH_DIGITS = ["dvp_upload_images_u8"]
 PREVIEW_DEPTH, PREVIEW_NORMAL, PREVIEW_WEAK = 1, 2, 4
@@ -179,6 +180,10 @@ def lib():
         L.dvp_cloud_refine_alignment.argtypes = [ci, vp, ll, vp, ll, vp, vp, vp, ci, vp, vp, ci, vp]
         L.dvp_cloud_icp_last_error.restype = ctypes.c_char_p
         L.dvp_cloud_icp_last_error.argtypes = []
+        L.dvp_cloud_scan_gaps.argtypes = [ci, vp, ci, ci, vp, ll, vp, vp, vp]
+        L.dvp_cloud_evaluate_scans.argtypes = [ci, vp, ll, vp, vp, ci, vp, ci, vp, ci, vp, vp, vp, vp, vp, vp, vp]
+        L.dvp_cloud_scan_last_error.restype = ctypes.c_char_p
+        L.dvp_cloud_scan_last_error.argtypes = []
         _LIB = L
     return _LIB
 
@@ -854,6 +859,77 @@ def cloud_evaluate_prepared(recon, truth, tolerances, prep_recon=None, prep_trut
     out = dict(within_recon=wr, within_truth=wt, used=used, accuracy=a, completeness=c, f1=f1, counts=counts)
     if distances:
         out.update(d2_recon=dr[:counts[0, 3]].copy(), d2_truth=dt[:counts[1, 3]].copy())
+    return out
+
+
+class DvpCloudScan(ctypes.Structure):
+    _fields_ = [("xyz", ctypes.c_void_p), ("num", ctypes.c_longlong), ("transform", ctypes.c_double * 16)]
+
+
+def _cloud_scans(scans, what):
+    """(DvpCloudScan array or None, the point arrays it points into, total points).  A scan is (xyz, transform) - (N, 3) points in
+    the scanner's frame, 16 numbers - or (xyz, transform, num) with a count of its own"""
+    keep, total = [], 0
+    arr = (DvpCloudScan * max(len(scans), 1))()
+    for k, scan in enumerate(scans):
+        a = _cloud(scan[0], what)
+        m = np.ascontiguousarray(scan[1], np.float64).reshape(-1)
+        if m.size != 16:
+            raise ValueError("a transform holds 16 numbers, got %d" % m.size)
+        keep.append(a)
+        arr[k].xyz, arr[k].num = a.ctypes.data, (len(a) if len(scan) < 3 else int(scan[2]))
+        arr[k].transform[:] = m.tolist()
+        total += len(a)
+    return arr, keep, total
+
+
+def cloud_scan_gaps(scans, queries, cube_size=1024, device=0, maps=False, truth=False):
+    """dict(gap: (N,) float32 of the queries - the largest distance by which a scan's range map lies behind the point, -inf where no
+    scan observes its direction, NaN for a non-finite point) from the scans' cube maps made on the GPU (include/dvp_mvs.h
+    dvp_cloud_scan_gaps); maps=True adds maps: (S, 6, R, R) float32 squared ranges, truth=True truth: (sum N_s, 3) float32"""
+    L = lib()
+    arr, keep, total = _cloud_scans(scans, "cloud_scan_gaps")
+    q = _cloud(queries, "cloud_scan_gaps")
+    R = int(cube_size)
+    gap = np.empty(len(q), np.float32)
+    m = np.empty((len(scans), 6, R, R), np.float32) if maps and 0 < R <= 4096 else None
+    t = np.empty((total, 3), np.float32) if truth else None
+    if L.dvp_cloud_scan_gaps(device, ctypes.byref(arr), len(scans), R, _p(q), len(q), _p(gap), _p(m), _p(t)) != 0:
+        raise DvpError(L.dvp_cloud_scan_last_error().decode())
+    out = dict(gap=gap)
+    if maps:
+        out["maps"] = m
+    if truth:
+        out["truth"] = t
+    return out
+
+
+def cloud_evaluate_scans(recon, scans, tolerances, prep_recon=None, prep_truth=None, cube_size=1024, device=0, distances=False):
+    """cloud_evaluate_prepared's dict of a reconstruction against the truth cloud of laser scans, with ETH3D's observed-space accuracy:
+    free_space, unobserved: (K,) int64, accuracy = within_recon / (within_recon + free_space), f1 from it and the completeness
+    (include/dvp_mvs.h dvp_cloud_evaluate_scans); distances=True adds d2_recon and gap of the prepared reconstructed points"""
+    L = lib()
+    r = _cloud(recon, "cloud_evaluate_scans")
+    arr, keep, total = _cloud_scans(scans, "cloud_evaluate_scans")
+    pr, keep_r = _cloud_prep(**(prep_recon or {}))
+    pt, keep_t = _cloud_prep(**(prep_truth or {}))
+    tol = np.ascontiguousarray(tolerances, np.float32).reshape(-1)
+    wr, wt, fs = (np.zeros(max(tol.size, 1), np.int64) for _ in range(3))
+    used, counts = np.zeros(2, np.int64), np.zeros((2, 4), np.int64)
+    dr = np.empty(len(r), np.float32) if distances else None
+    gap = np.empty(len(r), np.float32) if distances else None
+    if L.dvp_cloud_evaluate_scans(device, _p(r), len(r), ctypes.byref(pr) if prep_recon is not None else None, ctypes.byref(arr), len(scans),
+                                  ctypes.byref(pt) if prep_truth is not None else None, int(cube_size), _p(tol), tol.size, _p(wr), _p(wt), _p(used), _p(fs), _p(counts), _p(dr),
+                                  _p(gap)) != 0:
+        raise DvpError(L.dvp_cloud_scan_last_error().decode())
+    wr, wt, fs = wr[:tol.size], wt[:tol.size], fs[:tol.size]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        a = np.where(wr + fs > 0, wr / (wr + fs), 0.0)
+        c = wt / used[1] if used[1] else np.zeros(tol.size)
+        f1 = np.where(a + c > 0, 2 * a * c / (a + c), 0.0)
+    out = dict(within_recon=wr, within_truth=wt, used=used, free_space=fs, unobserved=used[0] - wr - fs, accuracy=a, completeness=c, f1=f1, counts=counts)
+    if distances:
+        out.update(d2_recon=dr[:counts[0, 3]].copy(), gap=gap[:counts[0, 3]].copy())
     return out
 
 

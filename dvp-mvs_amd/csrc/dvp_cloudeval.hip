@@ -247,7 +247,7 @@ extern "C" const char* dvp_cloud_last_error(void) { return t_cloud_error.c_str()
 // cloud 0's points are queries against cloud 1, and with `both` the other way round; d2[c] / within[c] may be NULL.  With `on_device`
 // the clouds are device arrays already and on_device[c] holds cloud c's bounds: nothing is read on the host and nothing uploaded.
 static int cloud_run(const char* who, int device, const float* const xyz[2], const long long num[2], const float* tolerances, int num_tol, bool both, long long* const within[2],
-                     long long* used, float* const d2[2], const dvpce::Bounds* on_device = nullptr) {
+                     long long* used, float* const d2[2], const dvpce::Bounds* on_device = nullptr, float* dev_d2_first = nullptr) {
 	using namespace dvpce;
 	t_cloud_error.clear();
 	for (int c = 0; c < 2; ++c) {
@@ -357,6 +357,7 @@ static int cloud_run(const char* who, int device, const float* const xyz[2], con
 	ok = hipMemcpyAsync(counts, b + o_within, sizeof counts, hipMemcpyDeviceToHost, st) == hipSuccess;
 	for (int c = 0; c < 2 && ok; ++c)
 		if (d2[c] && num[c]) ok = hipMemcpyAsync(d2[c], b + o_d2[c], (size_t)num[c] * 4, hipMemcpyDeviceToHost, st) == hipSuccess;
+	if (ok && dev_d2_first && num[0]) ok = hipMemcpyAsync(dev_d2_first, b + o_d2[0], (size_t)num[0] * 4, hipMemcpyDeviceToDevice, st) == hipSuccess;
 	if (!ok || hipStreamSynchronize(st) != hipSuccess) {
 		(void)hipGetLastError();
 		return cloud_fail(who, "the distances could not be made or fetched");
@@ -371,8 +372,8 @@ static int cloud_run(const char* who, int device, const float* const xyz[2], con
 }
 
 int dvpce::cloud_run_on_device(const char* who, int device, const float* const dev_xyz[2], const long long num[2], const Bounds bounds[2], const float* tolerances, int num_tol,
-                               long long* const within[2], long long* used, float* const d2[2]) {
-	return cloud_run(who, device, dev_xyz, num, tolerances, num_tol, true, within, used, d2, bounds);
+                               long long* const within[2], long long* used, float* const d2[2], float* dev_d2_first) {
+	return cloud_run(who, device, dev_xyz, num, tolerances, num_tol, true, within, used, d2, bounds, dev_d2_first);
 }
 
 extern "C" int dvp_cloud_distances(int device, const float* query_xyz, long long num_query, const float* target_xyz, long long num_target, float max_distance, float* d2_out) {

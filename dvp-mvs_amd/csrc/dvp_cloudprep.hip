@@ -512,6 +512,8 @@ std::string check_cloud(const float* xyz, long long num) {
 
 }   // namespace
 
+std::string dvpcp::prep_of_abi(const dvp_cloud_prep* c, Prep* prep) { return prep_of(c, prep); }
+
 std::string dvpcp::prepare_resident(hipStream_t st, const float* dev_xyz, long long num, const Prep& prep, ResidentCloud* res) {
 	Prepared p;
 	Laps laps;
@@ -519,6 +521,7 @@ std::string dvpcp::prepare_resident(hipStream_t st, const float* dev_xyz, long l
 	if (!what.empty()) return what;
 	if (laps.on) fprintf(stderr, "prepare (resident) timing (%lld points, %lld out):%s\n", num, p.num_out, laps.report.c_str());
 	res->num = p.num_out;
+	for (int k = 0; k < 4; ++k) res->counts[k] = p.counts[k];
 	res->bounds = dvpce::Bounds();
 	if (p.num_out) {
 		dvpmem::DevBlock extent;

@@ -8,12 +8,17 @@
 #include "dvp_cloudprep.hpp"
 #include "dvp_devmem.hpp"
 
+struct dvp_cloud_prep;
+
 namespace dvpcp {
+
+// the C ABI's description in its parser-independent form, checked as dvp_cloud_prepare checks it; "" or what is wrong
+std::string prep_of_abi(const dvp_cloud_prep* c, Prep* prep);
 
 // a prepared cloud in device memory: `num` packed float triples at the start of `out`; bounds: their extent and finite count
 struct ResidentCloud {
 	dvpmem::DevBlock out;
-	long long num = 0;
+	long long num = 0, counts[4] = { 0, 0, 0, 0 };   // counts: finite, after the transform, inside the crop, output points
 	dvpce::Bounds bounds;
 	const float* xyz() const { return out.as<float>(); }
 };

@@ -3,7 +3,9 @@
 // dvp_cloud_evaluate_prepared) or by the same text on the host (csrc/dvp_cloudeval.hpp: the double loop up to 2^24 pairs, the grid
 // walked serially above), and the report, whose figures come from the integer counts alone.  --refine-alignment first refines the
 // reconstruction's matrix by ICP stages (csrc/dvp_cloudicp.hpp: dvp_cloud_refine_alignment, or the same text on the host), and the
-// evaluation takes the refined matrix as if --transform had given it.
+// evaluation takes the refined matrix as if --transform had given it.  --against-scans takes the ground truth as the laser scans of a
+// MeshLab project (csrc/dvp_cloudscan.hpp: dvp_cloud_evaluate_scans, or the same text on the host): their points brought into the scene
+// are the truth cloud, and the accuracy column becomes the observed-space one.
 #include "evaluate.h"
 
 #include <cstdio>
@@ -15,23 +17,32 @@
 #include "../../include/dvp_mvs.h"
 #include "../csrc/dvp_cloudeval.hpp"
 #include "../csrc/dvp_cloudicp.hpp"
+#include "../csrc/dvp_cloudscan.hpp"
 
 std::string EvaluateReport(const EvaluateOptions& o, const long long num[2], const long long used[2], const long long* within_recon, const long long* within_truth,
-                           const long long* counts) {
+                           const long long* counts, const std::string& scan_lines, const long long* free_space) {
 	char text[256];
 	// every point dropped for a non-finite coordinate: as read, after the transform, or after the rounding of a prepared point to binary32
 	const long long skipped[2] = { counts ? (num[0] - counts[1]) + (counts[3] - used[0]) : num[0] - used[0], counts ? (num[1] - counts[5]) + (counts[7] - used[1]) : num[1] - used[1] };
 	std::string report = "reconstruction " + o.recon + " " + std::to_string(used[0]) + " points (" + std::to_string(skipped[0]) + " skipped)\n" +
-	                     "ground_truth " + o.truth + " " + std::to_string(used[1]) + " points (" + std::to_string(skipped[1]) + " skipped)\n";
+	                     "ground_truth " + o.truth + " " + std::to_string(used[1]) + " points (" + std::to_string(skipped[1]) + " skipped)\n" + scan_lines;
 	for (int c = 0; c < 2 && counts; ++c)
 		report += std::string("prepared ") + (c == 0 ? "reconstruction: " : "ground_truth: ") + std::to_string(counts[4 * c]) + " finite, " + std::to_string(counts[4 * c + 2]) +
 		          " in the crop volume, " + std::to_string(counts[4 * c + 3]) + " points\n";
 	report += "tolerance accuracy completeness f1\n";
 	for (size_t k = 0; k < o.tolerances.size(); ++k) {
-		const double a = used[0] ? (double)within_recon[k] / (double)used[0] : 0.0, c = used[1] ? (double)within_truth[k] / (double)used[1] : 0.0;
+		const long long judged = free_space ? within_recon[k] + free_space[k] : used[0];   // observed space: the accurate and the free-space points
+		const double a = judged ? (double)within_recon[k] / (double)judged : 0.0, c = used[1] ? (double)within_truth[k] / (double)used[1] : 0.0;
 		const double f = a + c == 0.0 ? 0.0 : 2.0 * a * c / (a + c);
 		snprintf(text, sizeof text, "%.9g %.6f %.6f %.6f\n", (double)o.tolerances[k], 100.0 * a, 100.0 * c, 100.0 * f);
 		report += text;
+	}
+	if (free_space) {
+		report += "tolerance accurate free_space unobserved\n";
+		for (size_t k = 0; k < o.tolerances.size(); ++k) {
+			snprintf(text, sizeof text, "%.9g %lld %lld %lld\n", (double)o.tolerances[k], within_recon[k], free_space[k], used[0] - within_recon[k] - free_space[k]);
+			report += text;
+		}
 	}
 	return report;
 }
@@ -117,7 +128,10 @@ static dvp_cloud_prep AbiPrep(const dvpcp::Prep& p) {
 	return c;
 }
 
-static bool EvaluateCloudsOrThrow(const EvaluateOptions& o, std::string* report, std::string* error) {
+static bool EvaluateCloudsOrThrow(const EvaluateOptions& given, std::string* report, std::string* error) {
+	EvaluateOptions o = given;
+	const bool against_scans = !o.truth_scans.empty();
+	if (against_scans) o.truth = o.truth_scans;   // (the report's ground_truth line names the project)
 	const bool prepares = o.prepares();
 	if (!o.save_prepared.empty() && !prepares) { *error = "--save-prepared needs --transform, --crop or --voxel-size"; return false; }
 	if (!o.save_transform.empty() && o.refine.empty()) { *error = "--save-transform needs --refine-alignment"; return false; }
@@ -139,9 +153,37 @@ static bool EvaluateCloudsOrThrow(const EvaluateOptions& o, std::string* report,
 		if (!what.empty()) { *error = what; return false; }
 	}
 	std::vector<float> recon, truth;
-	if (!ReadPlyVertices(o.recon, &recon, error) || !ReadPlyVertices(o.truth, &truth, error)) return false;
+	std::vector<std::vector<float>> scan_points;
+	std::vector<dvpcs::Scan> scans;
+	std::string scan_lines;
+	long long scan_total = 0;
+	if (!ReadPlyVertices(o.recon, &recon, error)) return false;
+	if (against_scans) {
+		const std::string cube = dvpcs::check_cube(o.cube_size);
+		if (!cube.empty()) { *error = cube; return false; }
+		std::vector<ScanEntry> entries;
+		if (!ReadScanProject(o.truth_scans, &entries, error)) return false;
+		scan_points.resize(entries.size());
+		scans.resize(entries.size());
+		for (size_t s = 0; s < entries.size(); ++s) {
+			std::string why;
+			if (!ReadPlyVertices(entries[s].path, &scan_points[s], &why)) { *error = "scan " + entries[s].name + ": " + why; return false; }
+			scans[s].xyz = scan_points[s].data();
+			scans[s].num = (long long)(scan_points[s].size() / 3);
+			for (int k = 0; k < 16; ++k) scans[s].m[k] = entries[s].m[k];
+			float at[3];
+			scans[s].scanner(at);
+			char text[160];
+			snprintf(text, sizeof text, ": %lld points, scanner at %.9g %.9g %.9g\n", scans[s].num, (double)at[0], (double)at[1], (double)at[2]);
+			scan_lines += "scan " + entries[s].name + text;
+		}
+		const std::string what = dvpcs::check_scans(scans.data(), (int)scans.size(), &scan_total);
+		if (!what.empty()) { *error = what; return false; }
+		// the truth cloud on the host where something other than the evaluation itself reads it: the stages, the saved cloud
+		if (!o.refine.empty() || (o.on_gpu && !o.save_prepared.empty())) dvpcs::serial_truth(scans.data(), (int)scans.size(), &truth);
+	} else if (!ReadPlyVertices(o.truth, &truth, error)) return false;
 	const std::vector<float>* cloud[2] = { &recon, &truth };
-	const long long num[2] = { (long long)(recon.size() / 3), (long long)(truth.size() / 3) };
+	const long long num[2] = { (long long)(recon.size() / 3), against_scans ? scan_total : (long long)(truth.size() / 3) };
 	const int K = (int)o.tolerances.size();
 	std::string alignment;
 	if (!o.refine.empty()) {   // the stages first: prep[0]'s matrix becomes the refined one
@@ -183,9 +225,32 @@ static bool EvaluateCloudsOrThrow(const EvaluateOptions& o, std::string* report,
 		if (!o.save_transform.empty() && !WriteTransformFile(o.save_transform, M, error)) return false;
 		alignment = AlignmentReport(log, M);
 	}
-	long long within_recon[dvpce::kMaxTolerances] = {}, within_truth[dvpce::kMaxTolerances] = {}, used[2] = { 0, 0 }, counts[8] = {};
+	long long within_recon[dvpce::kMaxTolerances] = {}, within_truth[dvpce::kMaxTolerances] = {}, used[2] = { 0, 0 }, counts[8] = {}, free_space[dvpce::kMaxTolerances] = {};
 	std::vector<float> prepared[2];
-	if (o.on_gpu && !prepares) {
+	if (against_scans && o.on_gpu) {
+		const dvp_cloud_prep abi[2] = { AbiPrep(prep[0]), AbiPrep(prep[1]) };
+		std::vector<dvp_cloud_scan> list(scans.size());
+		for (size_t s = 0; s < scans.size(); ++s) {
+			list[s].xyz = scans[s].xyz;
+			list[s].num = scans[s].num;
+			for (int k = 0; k < 16; ++k) list[s].transform[k] = scans[s].m[k];
+		}
+		if (dvp_cloud_evaluate_scans(o.device, recon.data(), num[0], prepares ? &abi[0] : nullptr, list.data(), (int)list.size(), prepares ? &abi[1] : nullptr, o.cube_size,
+		                             o.tolerances.data(), K, within_recon, within_truth, used, free_space, counts, nullptr, nullptr) != 0) {
+			*error = dvp_cloud_scan_last_error();
+			return false;
+		}
+		for (int c = 0; c < 2 && !o.save_prepared.empty(); ++c) {
+			prepared[c].resize(cloud[c]->size());
+			long long again[4];
+			if (dvp_cloud_prepare(o.device, cloud[c]->data(), num[c], &abi[c], prepared[c].data(), nullptr, again) != 0) { *error = dvp_cloud_prep_last_error(); return false; }
+			prepared[c].resize((size_t)again[3] * 3);
+		}
+	} else if (against_scans) {
+		const std::string what = K > dvpce::kMaxTolerances ? "at most 8 tolerances" : dvpcs::serial_evaluate_scans(recon.data(), num[0], prepares ? &prep[0] : nullptr, scans.data(), (int)scans.size(),
+		                                   prepares ? &prep[1] : nullptr, o.cube_size, o.tolerances.data(), K, within_recon, within_truth, used, free_space, counts, prepared, nullptr, nullptr);
+		if (!what.empty()) { *error = what; return false; }
+	} else if (o.on_gpu && !prepares) {
 		if (dvp_cloud_evaluate(o.device, recon.data(), num[0], truth.data(), num[1], o.tolerances.data(), K, within_recon, within_truth, used, nullptr, nullptr) != 0) {
 			*error = dvp_cloud_last_error();
 			return false;
@@ -213,7 +278,7 @@ static bool EvaluateCloudsOrThrow(const EvaluateOptions& o, std::string* report,
 		if (!what.empty()) { *error = what; return false; }
 	}
 	if (!o.save_prepared.empty() && (!WritePlyVertices(o.save_prepared + "recon.ply", prepared[0], error) || !WritePlyVertices(o.save_prepared + "truth.ply", prepared[1], error))) return false;
-	*report = alignment + EvaluateReport(o, num, used, within_recon, within_truth, prepares ? counts : nullptr);
+	*report = alignment + EvaluateReport(o, num, used, within_recon, within_truth, prepares ? counts : nullptr, scan_lines, against_scans ? free_space : nullptr);
 	if (!o.out.empty()) {
 		std::ofstream out(o.out, std::ios::binary);
 		out << *report;

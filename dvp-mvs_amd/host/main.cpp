@@ -476,16 +476,20 @@ int ConvertMain(int argc, char** argv) {
 
 // apd --evaluate <recon.ply> --against <truth.ply> [options]: no engine context, no rank, no result store
 int EvaluateMain(int argc, char** argv) {
-	const char* usage = "USAGE: apd --evaluate recon.ply --against truth.ply [--tolerances 0.01,0.02,0.05,0.1,0.2,0.5] [--evaluate-on gpu|host] [--gpu N] [--out FILE]\n"
+	const char* usage = "USAGE: apd --evaluate recon.ply --against truth.ply | --against-scans FILE.mlp [--cube-size R] [--tolerances 0.01,0.02,0.05,0.1,0.2,0.5] [--evaluate-on gpu|host] [--gpu N] [--out FILE]\n"
 	                    "       [--transform FILE] [--crop FILE] [--voxel-size S] [--save-prepared PREFIX]\n"
 	                    "       [--refine-alignment V:D:N[,V:D:N...]] [--save-transform FILE]\n"
 	                    "  --transform: 16 numbers (4 x 4, row-major) applied to the reconstruction; --crop: a SelectionPolygonVolume JSON, both clouds;\n"
 	                    "  --voxel-size: both clouds down-sampled to one centroid per voxel of edge S; --save-prepared: <PREFIX>recon.ply and <PREFIX>truth.ply\n"
 	                    "  --refine-alignment: ICP stages (voxel V, largest correspondence distance D, at most N steps) that refine the transform (the identity\n"
 	                    "  without --transform) before the clouds are measured; Tanks and Temples' choice for a scene threshold t: t:80t:20,t/2:20t:20,t/2:2t:20;\n"
-	                    "  --save-transform: the refined 4 x 4 matrix, a file --transform reads\n";
+	                    "  --save-transform: the refined 4 x 4 matrix, a file --transform reads\n"
+	                    "  --against-scans: the ground truth as the laser scans of a MeshLab project (ETH3D's scan_alignment.mlp); the accuracy then counts a point\n"
+	                    "  away from the truth only where a scanner looked through it; --cube-size: texels along an edge of the scans' cube maps (a power of two,\n"
+	                    "  16 ... 4096, default 1024)\n";
 	if (argc < 3 || argv[2][0] == '-') { std::cerr << usage; return EXIT_FAILURE; }
 	EvaluateOptions o;
+	bool cube_given = false;
 	o.recon = argv[2];
 	for (int a = 3; a < argc; ++a) {
 		const std::string s = argv[a];
@@ -523,9 +527,19 @@ int EvaluateMain(int argc, char** argv) {
 			if (!ParseRefineStages(v, &o.refine, &what)) { std::cerr << what << "\n"; return EXIT_FAILURE; }
 		}
 		else if (s == "--save-transform") o.save_transform = v;
+		else if (s == "--against-scans") o.truth_scans = v;
+		else if (s == "--cube-size") {
+			char* end = nullptr;
+			const long R = std::strtol(v.c_str(), &end, 10);
+			if (v.empty() || *end || R < 16 || R > 4096 || (R & (R - 1)) != 0) { std::cerr << "--cube-size takes a power of two, 16 ... 4096, got `" << v << "`\n"; return EXIT_FAILURE; }
+			o.cube_size = (int)R;
+			cube_given = true;
+		}
 		else { std::cerr << "unknown option " << s << "\n" << usage; return EXIT_FAILURE; }
 	}
-	if (o.truth.empty()) { std::cerr << "--against is required\n" << usage; return EXIT_FAILURE; }
+	if (!o.truth.empty() && !o.truth_scans.empty()) { std::cerr << "--against and --against-scans exclude each other\n" << usage; return EXIT_FAILURE; }
+	if (o.truth.empty() && o.truth_scans.empty()) { std::cerr << "--against is required (or --against-scans)\n" << usage; return EXIT_FAILURE; }
+	if (cube_given && o.truth_scans.empty()) { std::cerr << "--cube-size needs --against-scans\n" << usage; return EXIT_FAILURE; }
 	std::string report, error;
 	if (!EvaluateClouds(o, &report, &error)) { std::cerr << "apd --evaluate: " << error << std::endl; return EXIT_FAILURE; }
 	std::cout << report << std::flush;

@@ -2,7 +2,9 @@
 // separated by whitespace as numpy.savetxt writes a 4 x 4 matrix, and --crop, Open3D's SelectionPolygonVolume JSON, of which
 // orthogonal_axis, axis_min, axis_max and bounding_polygon are read and every other key is ignored.  The JSON reader is a small
 // recursive descent over the whole grammar (objects, arrays, strings with escapes, numbers, true / false / null); a surrogate pair
-// in a \u escape is kept as two code units, which no field read here can hold.
+// in a \u escape is kept as two code units, which no field read here can hold.  --against-scans takes a MeshLab project (ETH3D's
+// scan_alignment.mlp), of which the MLMesh elements' filename attributes and MLMatrix44 bodies are read by a scan over the tags: no
+// entities, no CDATA, which neither holds.
 #include "evaluate.h"
 
 #include <cstdlib>
@@ -39,6 +41,123 @@ bool ReadTransformFile(const std::string& file, double m[16], std::string* error
 	for (int k = 0; k < 16; ++k) p.m[k] = m[k];
 	const std::string what = dvpcp::check_prep(p);
 	if (!what.empty()) { *error = file + ": " + what; return false; }
+	return true;
+}
+
+// ---- --against-scans: a MeshLab project ----------------------------------------------------------------------------------------------
+namespace {
+
+bool XmlSpace(char c) { return c == ' ' || c == '\t' || c == '\n' || c == '\r'; }
+bool XmlName(char c) { return (c >= 'a' && c <= 'z') || (c >= 'A' && c <= 'Z') || (c >= '0' && c <= '9') || c == '_' || c == ':' || c == '-' || c == '.'; }
+
+// the attributes of the start tag whose name ends at `at`: name = "value" or 'value'.  Returns the position behind the tag's `>`
+// (npos: the tag does not end); *closed = the tag ends with `/>`
+size_t XmlAttributes(const std::string& s, size_t at, std::vector<std::pair<std::string, std::string>>* attributes, bool* closed) {
+	*closed = false;
+	for (;;) {
+		while (at < s.size() && XmlSpace(s[at])) ++at;
+		if (at >= s.size()) return std::string::npos;
+		if (s[at] == '>') return at + 1;
+		if (s[at] == '/' || s[at] == '?') { *closed = true; ++at; continue; }
+		const size_t first = at;
+		while (at < s.size() && XmlName(s[at])) ++at;
+		if (at == first) { ++at; continue; }   // (a stray character: skipped)
+		const std::string name = s.substr(first, at - first);
+		while (at < s.size() && XmlSpace(s[at])) ++at;
+		if (at >= s.size() || s[at] != '=') continue;   // (an attribute without a value)
+		++at;
+		while (at < s.size() && XmlSpace(s[at])) ++at;
+		if (at >= s.size() || (s[at] != '"' && s[at] != '\'')) continue;
+		const char quote = s[at++];
+		const size_t end = s.find(quote, at);
+		if (end == std::string::npos) return std::string::npos;
+		attributes->emplace_back(name, s.substr(at, end - at));
+		at = end + 1;
+	}
+}
+
+// the next start tag at or behind `at`: its position (npos: none) and name; comments are skipped
+size_t XmlNextTag(const std::string& s, size_t at, std::string* name, size_t* name_end) {
+	for (;;) {
+		at = s.find('<', at);
+		if (at == std::string::npos) return at;
+		if (s.compare(at, 4, "<!--") == 0) {
+			const size_t end = s.find("-->", at + 4);
+			if (end == std::string::npos) return end;
+			at = end + 3;
+			continue;
+		}
+		size_t k = at + 1;
+		while (k < s.size() && XmlName(s[k])) ++k;
+		if (k == at + 1) { ++at; continue; }   // an end tag, a declaration, a processing instruction
+		*name = s.substr(at + 1, k - at - 1);
+		*name_end = k;
+		return at;
+	}
+}
+
+}   // namespace
+
+bool ReadScanProject(const std::string& file, std::vector<ScanEntry>* scans, std::string* error) {
+	std::string text;
+	if (!ReadWhole(file, &text, error)) return false;
+	const size_t slash = file.find_last_of('/');
+	const std::string folder = slash == std::string::npos ? "" : file.substr(0, slash + 1);
+	scans->clear();
+	std::string name;
+	size_t name_end = 0, at = 0;
+	long long meshes = 0;
+	while ((at = XmlNextTag(text, at, &name, &name_end)) != std::string::npos) {
+		at = name_end;
+		if (name != "MLMesh") continue;
+		++meshes;
+		std::vector<std::pair<std::string, std::string>> attributes;
+		bool closed = false;
+		at = XmlAttributes(text, name_end, &attributes, &closed);
+		if (at == std::string::npos) { *error = file + ": MLMesh element " + std::to_string(meshes) + " does not end"; return false; }
+		ScanEntry entry;
+		bool named = false;
+		for (const auto& a : attributes)
+			if (a.first == "filename" && !named) { entry.name = a.second; named = true; }
+		if (!named || entry.name.empty()) { *error = file + ": MLMesh element " + std::to_string(meshes) + " has no filename"; return false; }
+		entry.path = entry.name[0] == '/' ? entry.name : folder + entry.name;
+		// the element's matrix: the first MLMatrix44 before the element ends or the next MLMesh begins
+		size_t matrix = std::string::npos, next = at;
+		std::string inner;
+		size_t inner_end = 0;
+		const size_t limit = closed ? at : text.find("</MLMesh", at);
+		while (!closed && (next = XmlNextTag(text, next, &inner, &inner_end)) != std::string::npos && next < limit) {
+			if (inner == "MLMesh") break;
+			if (inner == "MLMatrix44") { matrix = inner_end; break; }
+			next = inner_end;
+		}
+		if (matrix == std::string::npos) { *error = file + ": the MLMesh " + entry.name + " has no MLMatrix44"; return false; }
+		std::vector<std::pair<std::string, std::string>> none;
+		bool empty = false;
+		const size_t body = XmlAttributes(text, matrix, &none, &empty);
+		const size_t body_end = body == std::string::npos ? body : text.find('<', body);
+		if (body == std::string::npos || body_end == std::string::npos) { *error = file + ": the MLMatrix44 of " + entry.name + " does not end"; return false; }
+		std::stringstream words(empty ? std::string() : text.substr(body, body_end - body));
+		std::string word;
+		long long count = 0;
+		while (words >> word) {
+			char* end = nullptr;
+			const double v = std::strtod(word.c_str(), &end);
+			if (end == word.c_str() || *end) { *error = file + ": the MLMatrix44 of " + entry.name + ": `" + word + "` is not a number"; return false; }
+			if (count < 16) entry.m[count] = v;
+			++count;
+		}
+		if (count != 16) { *error = file + ": the MLMatrix44 of " + entry.name + " holds " + std::to_string(count) + " numbers; a transform is 16 (4 x 4, row-major)"; return false; }
+		dvpcp::Prep p;
+		p.has_transform = true;
+		for (int k = 0; k < 16; ++k) p.m[k] = entry.m[k];
+		const std::string what = dvpcp::check_prep(p);
+		if (!what.empty()) { *error = file + ": the MLMatrix44 of " + entry.name + ": " + what; return false; }
+		if (scans->size() == 64) { *error = file + " holds more than 64 scans"; return false; }
+		scans->push_back(entry);
+		at = body_end;
+	}
+	if (scans->empty()) { *error = file + " holds no MLMesh element"; return false; }
 	return true;
 }
 

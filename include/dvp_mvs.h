@@ -583,6 +583,32 @@ int dvp_cloud_refine_alignment(int device, const float* recon_xyz, long long n_r
                                int* log_count);
 const char* dvp_cloud_icp_last_error(void);   /* the calling thread's last error of the two above */
 
+/* ---- `apd --evaluate --against-scans`: ETH3D's observed-space accuracy from range maps of the laser scans as their scanners saw them;
+ * the project's own definition (csrc/dvp_cloudscan.hpp, DESIGN.md "Cloud evaluation") ---------------------------------------------------
+ * A scan: num binary32 points in the scanner's own frame and the 16 row-major doubles that bring them into the scene (all finite, last
+ * row exactly 0 0 0 1).  Truth point g = transform * q in binary64 (the preparation's formula), rounded once to binary32; the scanner
+ * stands at the translation column rounded to binary32.  cube_size R: a power of two, 16 ... 4096.  Per scan a cube map of 6 R R
+ * texels around the scanner: map[t] = the smallest squared range r2 = (dx*dx + dy*dy) + dz*dz (binary32) of the scan's truth points
+ * whose direction falls into texel t, +inf for none.  gap of a point p: NaN for a non-finite p, else the maximum over the scans that
+ * hold a finite value in p's texel of sqrt(map[t]) - sqrt(r2(p)), -inf if none does: a positive gap says that a scanner measured a
+ * surface that far behind p. */
+typedef struct dvp_cloud_scan { const float* xyz; long long num; double transform[16]; } dvp_cloud_scan;
+/* maps, truth points and gaps of the queries; every output may be NULL.  maps_out: num_scans * 6 R R values of r2, truth_xyz_out: 3
+ * floats per scan point, scan after scan.  Errors: a null pointer, num_scans outside 1 ... 64, a cube_size that is no power of two in
+ * 16 ... 4096, a negative count, more than 2^31 - 1 scan points together, a non-finite transform or a last row other than 0 0 0 1, no
+ * device memory.  Host in, host out; safe from several threads. */
+int dvp_cloud_scan_gaps(int device, const dvp_cloud_scan* scans, int num_scans, int cube_size, const float* query_xyz, long long num_query, float* gap_out, float* maps_out,
+                        float* truth_xyz_out);
+/* The whole evaluation against scans: recon prepared by prep_recon, the truth cloud of the scans by prep_truth (either may be NULL:
+ * the finite points as they are), dvp_cloud_evaluate's distances and counts on the prepared clouds, then free_space[k] = the prepared
+ * reconstructed points with !(d2 <= t_k * t_k) && gap > t_k; the maps are made from every point of every scan, whatever prep_truth
+ * holds.  counts_out[8] as dvp_cloud_evaluate_prepared; d2_recon_out and gap_out (room for num_recon values, may be NULL) per
+ * prepared reconstructed point.  Errors: those above, of dvp_cloud_prepare and of dvp_cloud_evaluate. */
+int dvp_cloud_evaluate_scans(int device, const float* recon_xyz, long long num_recon, const dvp_cloud_prep* prep_recon, const dvp_cloud_scan* scans, int num_scans,
+                             const dvp_cloud_prep* prep_truth, int cube_size, const float* tolerances, int num_tol, long long* within_recon, long long* within_truth,
+                             long long* used, long long* free_space, long long* counts_out, float* d2_recon_out, float* gap_out);
+const char* dvp_cloud_scan_last_error(void);   /* the calling thread's last error of the two above */
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,7 +22,13 @@ synthetic surface cloud of the size of a ten-view full-size fusion (default 45 M
   --refine-host   no device: the serial host text (tests/cloudicp_host refine) on the sources of a square of 1 / 32 of the side against
                   the targets within the first stage's distance around it, scaled by the source counts and labelled as such, and a
                   float64 ICP around scipy's cKDTree at FORM_POINTS
-usage: evaluate_timing.py [--device] [--host] [--kd] [--prepare] [--refine] [--refine-host] [POINTS [FORM_POINTS]]"""
+  --scans         the observed-space accuracy against laser scans (dvp_cloud_evaluate_scans; lines go to profiles/evaluate_scans.txt):
+                  a synthetic hall of 16 x 12 x 7.5 m seen by four scanners, each a sweep of SCAN_POINTS returns (default 10 M) in
+                  sweep order, and a reconstruction of POINTS points of which 90 % lie on the walls, 8 % behind them and 2 % inside
+                  the hall; at cube sizes 1 024 and 2 048 the call as shipped against plain dvp_cloud_evaluate_prepared on the same
+                  clouds, the laps of a serialised run, and the serial host text (tests/cloudscan_host gaps) on every 64th point of the
+                  scans and of the reconstruction, scaled by the point counts and labelled as such
+usage: evaluate_timing.py [--device] [--host] [--kd] [--prepare] [--refine] [--refine-host] [--scans] [POINTS [FORM_POINTS | SCAN_POINTS]]"""
 import importlib
 import os
 import subprocess
@@ -330,6 +336,97 @@ def refine_host_lines(lines, points, form_points):
     print(lines[-1], flush=True)
 
 
+HALL = np.array([16.0, 12.0, 7.5])
+HALL_SCANNERS = [[3.0, 2.5, 1.6], [12.5, 3.0, 1.7], [8.0, 9.0, 1.5], [2.5, 9.5, 1.8]]
+
+
+def hall_hits(origin, direction):
+    """where the rays from origin (3,) along direction (n, 3) leave the hall [0, HALL]"""
+    with np.errstate(divide="ignore", invalid="ignore"):
+        t = np.where(direction > 0, (HALL - origin) / direction, np.where(direction < 0, -origin / direction, np.inf))
+    return origin + direction * t.min(1)[:, None]
+
+
+def hall_scene(points, scan_points, seed=11):
+    """(scans [(xyz in the scanner's frame, matrix)], reconstruction): every scan a sweep of rows of equal elevation, as a terrestrial
+    scanner stores it"""
+    import np_cloudprep as P
+    rng = np.random.default_rng(seed)
+    scans = []
+    rows = int(np.sqrt(scan_points / 2))
+    for k, o in enumerate(HALL_SCANNERS):
+        i = np.arange(scan_points)
+        azimuth, elevation = 2 * np.pi * (i % (2 * rows)) / (2 * rows), np.pi * ((i // (2 * rows)) + 0.5) / (scan_points / (2 * rows)) - np.pi / 2
+        d = np.stack([np.cos(elevation) * np.cos(azimuth), np.cos(elevation) * np.sin(azimuth), np.sin(elevation)], 1)
+        hit = hall_hits(np.asarray(o), d) + rng.normal(0, 0.001, (scan_points, 3))
+        m = P.rotation(30.0 * k, 0.0, o).reshape(4, 4)
+        scans.append((np.ascontiguousarray(((hit - m[:3, 3]) @ m[:3, :3]).astype(np.float32)), m.reshape(-1)))      # q = R^T (g - o)
+        del d, hit
+    d = rng.normal(0, 1, (points, 3))
+    d /= np.linalg.norm(d, axis=1)[:, None]
+    centre = HALL / 2 + rng.uniform(-2, 2, (points, 3)) * [1, 1, 0.5]
+    wall = hall_hits(centre, d)
+    kind = rng.random(points)
+    recon = wall + rng.normal(0, 0.004, (points, 3))
+    behind = kind < 0.08
+    recon[behind] = wall[behind] + d[behind] * rng.uniform(0.6, 2.0, (int(behind.sum()), 1))
+    inside = kind > 0.98
+    recon[inside] = centre[inside] + (wall[inside] - centre[inside]) * rng.uniform(0.1, 0.8, (int(inside.sum()), 1))
+    return scans, np.ascontiguousarray(recon.astype(np.float32))
+
+
+def scans_lines(lines, points, scan_points):
+    import np_cloudscan as S
+    capi = importlib.import_module("dvp-mvs_amd").get_capi()
+    tol = N.DEFAULT_TOLERANCES
+    scans, recon = hall_scene(points, scan_points)
+    truth = S.truth_cloud(scans)
+    capi.cloud_evaluate(np.zeros((1, 3), np.float32), np.zeros((1, 3), np.float32), tol)      # the runtime's start-up
+    os.environ.pop("DVP_CLOUD_TIMING", None)
+    plain = []
+    for _ in range(2):
+        t0 = time.perf_counter()
+        base = capi.cloud_evaluate_prepared(recon, truth, tol)
+        plain.append(1e3 * (time.perf_counter() - t0))
+    lines.append("device, a hall of %g x %g x %g m, %d scans of %d points each in sweep order, a reconstruction of %d points: plain dvp_cloud_evaluate_prepared on the reconstruction and "
+                 "the truth cloud of the scans (wall time, two calls) %s ms; accuracy over all points %s (percent)" % (
+                     HALL[0], HALL[1], HALL[2], len(scans), scan_points, points, " ".join("%.0f" % v for v in plain), " ".join("%.3f" % (100 * v) for v in base["accuracy"])))
+    print(lines[-1], flush=True)
+    for R in (1024, 2048):
+        shipped = []
+        for _ in range(2):
+            t0 = time.perf_counter()
+            got = capi.cloud_evaluate_scans(recon, scans, tol, cube_size=R)
+            shipped.append(1e3 * (time.perf_counter() - t0))
+        os.environ["DVP_CLOUD_TIMING"] = "1"
+        t0 = time.perf_counter()
+        again, text = with_stderr(lambda: capi.cloud_evaluate_scans(recon, scans, tol, cube_size=R))
+        dt = time.perf_counter() - t0
+        os.environ.pop("DVP_CLOUD_TIMING", None)
+        assert all(np.array_equal(got[k], again[k]) for k in ("within_recon", "within_truth", "used", "free_space")) and np.array_equal(got["within_recon"], base["within_recon"])
+        lines.append("  cube size %d: dvp_cloud_evaluate_scans as shipped (wall time, two calls) %s ms; with DVP_CLOUD_TIMING=1, which waits for the stream after every phase, the call %.0f ms" % (
+            R, " ".join("%.0f" % v for v in shipped), 1e3 * dt))
+        lines += ["    " + ln for ln in text.splitlines()]
+        lines.append("    accurate %s, free_space %s, unobserved %s; observed-space accuracy %s, completeness %s (percent)" % (
+            got["within_recon"].tolist(), got["free_space"].tolist(), got["unobserved"].tolist(), " ".join("%.3f" % (100 * v) for v in got["accuracy"]),
+            " ".join("%.3f" % (100 * v) for v in got["completeness"])))
+        for ln in lines[-(3 + len(text.splitlines())):]:
+            print(ln, flush=True)
+    S.build_program()
+    with tempfile.TemporaryDirectory() as tmp:
+        part = [(x[::64], m) for x, m in scans]
+        q = recon[::64]
+        for R in (1024, 2048):
+            t0 = time.perf_counter()
+            rc, err, out = S.serial_gaps(part, q, R, tmp)
+            dt = time.perf_counter() - t0
+            assert rc == 0, err
+            lines.append("serial host text (tests/cloudscan_host gaps, one thread), cube size %d: every 64th point, %d scan points and %d queries, truth points, maps and gaps %.1f s with the files' "
+                         "reading and writing; SCALED by the point counts to the whole scene: %.0f s (the distances are profiles/evaluate.txt's)" % (
+                             R, sum(len(x) for x, _ in part), len(q), dt, dt * 64))
+            print(lines[-1], flush=True)
+
+
 def main():
     args = [a for a in sys.argv[1:] if not a.startswith("--")]
     points = int(args[0]) if args else 45000000
@@ -347,6 +444,11 @@ def main():
         else:
             refine_host_lines(lines, points, form_points)
         with open(os.path.join(ROOT, "profiles", "evaluate_refine.txt"), "a") as f:
+            f.write("\n".join(lines) + "\n")
+        return
+    if "--scans" in sys.argv:
+        scans_lines(lines, points, int(args[1]) if len(args) > 1 else 10000000)
+        with open(os.path.join(ROOT, "profiles", "evaluate_scans.txt"), "a") as f:
             f.write("\n".join(lines) + "\n")
         return
     if "--prepare" in sys.argv:

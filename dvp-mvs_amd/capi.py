@@ -41,6 +41,7 @@ EXPORTS = ["dvp_ctx_create", "dvp_ctx_destroy", "dvp_ctx_reserve", "dvp_last_err
            "dvp_images_create", "dvp_images_destroy", "dvp_images_put", "dvp_images_drop", "dvp_images_size", "dvp_images_bytes", "dvp_images_level", "dvp_images_last_error",
            "dvp_download_image",
            "dvp_jpeg_decode", "dvp_jpeg_decode_into_store", "dvp_jpeg_decode_timings", "dvp_jpeg_decode_last_error",
+           "dvp_jpeg_set_entropy", "dvp_jpeg_entropy_stats", "dvp_jpeg_entropy_phases", "dvp_jpeg_scan_records",
            "dvp_plane_prior", "dvp_plane_prior_stage", "dvp_plane_prior_timings",
            "dvp_view_scores", "dvp_convert_image", "dvp_pairs_last_error",
            "dvp_undistort_image", "dvp_undistort_last_error",
@@ -156,6 +157,11 @@ def lib():
         L.dvp_jpeg_decode_timings.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ll)]
         L.dvp_jpeg_decode_last_error.restype = ctypes.c_char_p
         L.dvp_jpeg_decode_last_error.argtypes = []
+        L.dvp_jpeg_set_entropy.restype = None
+        L.dvp_jpeg_set_entropy.argtypes = [ci]
+        L.dvp_jpeg_entropy_stats.argtypes = [ctypes.POINTER(ll)]
+        L.dvp_jpeg_entropy_phases.argtypes = [ctypes.POINTER(ctypes.c_double)]
+        L.dvp_jpeg_scan_records.argtypes = [ci, vp, ll, ci, ci, pi, ctypes.POINTER(ll), ctypes.POINTER(ll), ctypes.POINTER(vp), ctypes.POINTER(vp)]
         L.dvp_upload_images_u8.argtypes = [vp, vp, vp, ci, ci]
         L.dvp_download_image.argtypes = [vp, ci, vp, ci]
         L.dvp_plane_prior.argtypes = [vp, vp, ci, ci, vp, vp, ci, vp, pi]
@@ -337,6 +343,49 @@ def jpeg_decode_timings():
     ms, n = (ctypes.c_double * 2)(), (ctypes.c_longlong * 2)()
     lib().dvp_jpeg_decode_timings(ms, n)
     return dict(host_ms=ms[0], device_ms=ms[1], record_bytes=int(n[0]), blocks=int(n[1]))
+
+
+ENTROPY_PATHS = ("host", "device", "fell back")
+ENTROPY_PHASES = ("prescan", "upload", "sync", "count", "scans", "write", "reconstruct")
+
+
+def jpeg_set_entropy(on_device):
+    """where the Huffman scan of jpeg_decode / ImageStore.put_jpeg runs from now on, process-wide (dvp_jpeg_set_entropy)"""
+    lib().dvp_jpeg_set_entropy(1 if on_device else 0)
+
+
+def jpeg_entropy_stats():
+    """this thread's last decode (dvp_jpeg_entropy_stats): dict(path = host | device | fell back, segments, subsequences, chunks,
+    longest_chain, rounds, uploaded_bytes, decodes)"""
+    n = (ctypes.c_longlong * 8)()
+    lib().dvp_jpeg_entropy_stats(n)
+    return dict(path=ENTROPY_PATHS[int(n[0])], segments=int(n[1]), subsequences=int(n[2]), chunks=int(n[3]), longest_chain=int(n[4]), rounds=int(n[5]),
+                uploaded_bytes=int(n[6]), decodes=int(n[7]))
+
+
+def jpeg_entropy_phases():
+    """milliseconds per phase of this thread's last device-path decode in a process run with DVP_JPEG_ENTROPY_SERIAL=1"""
+    ms = (ctypes.c_double * 7)()
+    lib().dvp_jpeg_entropy_phases(ms)
+    return dict(zip(ENTROPY_PHASES, (float(v) for v in ms)))
+
+
+def jpeg_scan_records(file, luma_only=False, on_device=False, device=0):
+    """the coefficient records of a JPEG file's scan (dvp_jpeg_scan_records): a list of (offsets, records) uint32 arrays per
+    component, None for a component that luma_only leaves out"""
+    L = lib()
+    f = _file_bytes(file)
+    comps = ctypes.c_int(0)
+    n_off, n_rec = (ctypes.c_longlong * 3)(), (ctypes.c_longlong * 3)()
+    args = (device, _p(f) if f.size else None, f.size, 1 if luma_only else 0, 1 if on_device else 0, ctypes.byref(comps), n_off, n_rec)
+    if L.dvp_jpeg_scan_records(*args, None, None) != 0:
+        raise DvpError(L.dvp_jpeg_decode_last_error().decode())
+    off = [np.empty(int(n_off[i]), np.uint32) for i in range(3)]
+    rec = [np.empty(int(n_rec[i]), np.uint32) for i in range(3)]
+    po, pr = (ctypes.c_void_p * 3)(*[a.ctypes.data for a in off]), (ctypes.c_void_p * 3)(*[a.ctypes.data for a in rec])
+    if L.dvp_jpeg_scan_records(*args, po, pr) != 0:
+        raise DvpError(L.dvp_jpeg_decode_last_error().decode())
+    return [(off[i], rec[i]) if n_off[i] else None for i in range(comps.value)]
 
 
 def canny_edge_map(grey, device=0):

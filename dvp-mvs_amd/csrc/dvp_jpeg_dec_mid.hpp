@@ -114,6 +114,11 @@ struct Decoder {
 	std::vector<Component> comps;
 	int width = 0, height = 0, hmax = 1, vmax = 1, restart_interval = 0;
 	const char* error = "";
+	// stop_at_scan: decode() reads everything up to the scan — tables, frame, DRI, the scan header — and returns true with
+	// [scan_data, scan_end) the bytes behind the SOS segment, without running scan() (dvp_jpeg_huff.hpp decodes them in parallel)
+	bool stop_at_scan = false;
+	const uint8_t* scan_data = nullptr;
+	const uint8_t* scan_end = nullptr;
 
 	bool fail(const char* msg) { error = msg; return false; }
 	int padded_width(const Component& c) const { return c.blocks_w * 8; }
@@ -196,6 +201,7 @@ struct Decoder {
 					for (auto& c : comps)
 						if (c.id == cid) { c.td = s[2 + 2 * i] >> 4; c.ta = s[2 + 2 * i] & 15; }
 				}
+				if (stop_at_scan) { scan_data = se; scan_end = end; return true; }
 				if (!scan(se, end, luma_only)) return false;
 				// a luma plane at reduced sampling would need interpolation; every encoder in practice gives luma full resolution
 				if (luma_only && (comps[0].h != hmax || comps[0].v != vmax)) return fail("sub-sampled luma is not supported");

@@ -53,6 +53,10 @@ struct RunConfig {
 	// dvp_jpeg_decode_into_store): the entropy decode stays on the host, the inverse DCT and the colour conversion run on APD::GetDevice().
 	// Same bytes; one line "Image decode: on the device (<file>, grey|colour)" per file (grey, into the image store: with images_on_device); a failure stops the job.
 	bool decode_on_device = false;
+	// `apd --entropy-on gpu`, only with decode_on_device: the Huffman scan of those files runs on the device too (dvp_jpeg_set_entropy(1):
+	// the file's entropy-coded bytes go up instead of coefficient records).  Same bytes; one more line per file, "Entropy decode: on the
+	// device (<file>, grey|colour)" or "Entropy decode: on the host (<file>, grey|colour: <why>)" for a file the device path left to the host.
+	bool entropy_on_device = false;
 	// true: a pass that starts from maps of another size (REFINE_INIT on a finer pyramid level) hands them to the engine at their
 	// own size and RescaleMatToTargetSize runs there (dvp_upload_state_rescaled); false (`apd --sync-io` / `--host-rescale`): the
 	// five host-side rescales + the plane assembly of the reference's flow (APD.cpp:1176-1180, 1440-1456, 1656-1659).  Same maps either way.

@@ -3,6 +3,9 @@
 
 const char* const kApdUsage = "USAGE: apd dense_folder [gpu_index] [--previews] [--max-src N] [--iters N] [--min-scale S] [--passes P] [--seed X] [--rank R --world N [--job ID]] [--jacobi] [--no-fusion | --fusion KIND] [--fusion-on device|host] [--edges-on host|gpu] [--labels-on host|gpu] [--cleanup-on host|gpu] [--images-on host|gpu] [--prior-on host|gpu] [--decode-on host|gpu] [--strong-wide on|off] [--views-in-flight N]\n";
 
+// (kept out of kApdUsage: tests/test_driver_host.py pins the options that text names)
+const char* const kApdEntropyUsage = "USAGE: --entropy-on host|gpu moves the input JPEGs' Huffman decode to the device and takes effect only together with --decode-on gpu: apd dense_folder --decode-on gpu --entropy-on gpu\n";
+
 // `--X first|second`: whether the word is the second one; any other word ends the process
 static bool SecondWord(const std::string& option, const std::string& word, const char* first, const char* second) {
 	if (word != first && word != second) { std::cerr << option << " takes " << first << " or " << second << "\n"; std::exit(1); }
@@ -12,7 +15,8 @@ static bool SecondWord(const std::string& option, const std::string& word, const
 Options ParseOptions(int argc, char** argv) {
 	static const std::pair<const char*, bool RunConfig::*> on_gpu[] = {
 		{ "--edges-on", &RunConfig::edges_on_device }, { "--labels-on", &RunConfig::labels_on_device }, { "--prior-on", &RunConfig::prior_on_device },
-		{ "--cleanup-on", &RunConfig::cleanup_on_device }, { "--decode-on", &RunConfig::decode_on_device }, { "--images-on", &RunConfig::images_on_device } };
+		{ "--cleanup-on", &RunConfig::cleanup_on_device }, { "--decode-on", &RunConfig::decode_on_device }, { "--images-on", &RunConfig::images_on_device },
+		{ "--entropy-on", &RunConfig::entropy_on_device } };
 	Options o;
 	o.dense_folder = argv[1];
 	int a = 2;
@@ -46,6 +50,7 @@ Options ParseOptions(int argc, char** argv) {
 		else if (s == "--fusion") { if (a + 1 < argc) o.fusion_kind = argv[++a]; }
 		else if (s == "--fusion-on") { if (a + 1 < argc) o.fusion_on_host = std::string(argv[++a]) == "host"; }   // device (default) | host
 	}
+	if (o.run.entropy_on_device && !o.run.decode_on_device) { std::cerr << kApdEntropyUsage; std::exit(1); }
 	o.run.device_rescale = o.run.device_maps = !o.sync_io && !o.host_rescale;
 	if (o.world > 1) o.jacobi = true;
 	if (o.job.empty())   // a launcher-provided id; with --world > 1 RankComm refuses to start without one

@@ -4,6 +4,7 @@
 #include "APD.h"
 
 extern const char* const kApdUsage;   // the one usage text of `apd <dense_folder>`
+extern const char* const kApdEntropyUsage;   // ... and what `--entropy-on gpu` without `--decode-on gpu` is refused with
 
 struct Options {
 	path dense_folder;

@@ -247,6 +247,14 @@ static Mat decode_jpeg_on_device(const path& jpg, int channels) {
 		if (dvp_jpeg_decode(APD::GetDevice(), file.data(), (long long)file.size(), channels, m.data, (long long)m.step, nullptr, nullptr) != 0) DvpFatal(who + dvp_jpeg_decode_last_error());
 	}
 	std::cout << ("Image decode: on the device (" + jpg.filename().string() + (channels == 1 ? (stored ? ", grey, into the image store)\n" : ", grey)\n") : ", colour)\n")) << std::flush;
+	if (Run().entropy_on_device) {   // --entropy-on gpu: where this file's Huffman scan ran (the calling thread's last decode)
+		long long n[8] = { 0 };
+		dvp_jpeg_entropy_stats(n);
+		const std::string what = jpg.filename().string() + (channels == 1 ? ", grey" : ", colour");
+		std::cout << (n[0] == 1 ? "Entropy decode: on the device (" + what + ")\n"
+		                        : "Entropy decode: on the host (" + what + (n[0] == 2 ? ": the device path fell back)\n" : ": not a scan for the device path)\n"))
+		          << std::flush;
+	}
 	return m;
 }
 static Mat read_image(const path& jpg, int channels) {

@@ -569,6 +569,7 @@ std::unique_ptr<RankComm> SetUpProcess(const Options& opt, const std::vector<Pro
 	if (!problems.empty() && ImageFileSize(problems[0].dense_folder / "images" / (ToFormatIndex(problems[0].ref_image_id) + ".jpg"), &w, &h))
 		run.final_iteration = (int)BuildPlan(LevelsOf(w, h), opt.min_scale, opt.geom_passes).size() - 1;
 	SetRunConfig(run);
+	dvp_jpeg_set_entropy(run.entropy_on_device ? 1 : 0);   // (before the decode threads start)
 	SetHostThreadShare(opt.world);
 	if (opt.world > 1) std::cout << "rank " << opt.rank << " of " << opt.world << ": " << HostThreads() << " host threads (of " << std::thread::hardware_concurrency() << " cores)" << std::endl;
 	APD::SetDevice(opt.gpu);

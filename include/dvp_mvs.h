@@ -423,7 +423,30 @@ int dvp_jpeg_decode_into_store(dvp_images* store, int id, const uint8_t* file, l
 /* The calling thread's last successful call of the two above: ms[0] the host part (parse + entropy decode), ms[1] the device part
  * (upload, launches, read-back, wait); counts[0] the bytes of coefficient records and offsets uploaded, counts[1] the 8 x 8 blocks. */
 int dvp_jpeg_decode_timings(double* ms, long long* counts);
-const char* dvp_jpeg_decode_last_error(void);   /* the calling thread's last error of the three above */
+const char* dvp_jpeg_decode_last_error(void);   /* the calling thread's last error of the three above and of dvp_jpeg_scan_records */
+/* `apd --entropy-on gpu`: where the Huffman scan of the two decode calls above runs.  Process-wide; 0 (the default): on the host,
+ * every call exactly as described above.  1: the headers are parsed on the host, the file's entropy-coded bytes go up instead of
+ * coefficient records, and the records are made on the device (csrc/dvp_jpeg_huff.hip: a lane per 128-byte subsequence, which
+ * self-synchronises with its neighbours); they never exist on the host.  A file the device path does not take — fill bytes or
+ * another marker inside the scan, no marker after it, a restart-marker count that does not match the frame, a corrupt code, a
+ * segment that does not hold exactly its MCUs, a synchronisation that does not settle, a refused allocation — is decoded on the
+ * host as with 0: same bytes, same messages.  dvp_jpeg_decode_timings: ms[0] is then the parse and the pre-scan, ms[1] everything
+ * on the device; counts[0] the bytes of the records and offsets the device made. */
+void dvp_jpeg_set_entropy(int on_device);
+/* The calling thread's last dvp_jpeg_decode / dvp_jpeg_decode_into_store / dvp_jpeg_scan_records, 8 numbers: [0] the path — 0 host,
+ * 1 device, 2 device, then fell back to the host; [1] segments (the stretches between restart markers); [2] subsequences;
+ * [3] chunks of 256 subsequences; [4] the longest synchronisation chain (subsequences one lane decoded in a row); [5] inter-chunk
+ * rounds; [6] bytes uploaded for the scan; [7] subsequence decodes of the synchronisation in all ([7] / [2] = mean re-decodes). */
+int dvp_jpeg_entropy_stats(long long* counts);
+/* 7 numbers, milliseconds of the last device-path call of the calling thread when the process runs with DVP_JPEG_ENTROPY_SERIAL=1
+ * (a wait after every phase; else zeros but [0]): pre-scan, upload, synchronisation, census + count, scans, write, reconstruction. */
+int dvp_jpeg_entropy_phases(double* ms);
+/* The coefficient records of a file's scan in the format of csrc/dvp_jpeg_dec_mid.hpp, from the host's serial scan (on_device 0)
+ * or from the device path (1, whatever dvp_jpeg_set_entropy says; dvp_jpeg_entropy_stats tells whether it fell back).  Two calls:
+ * with offsets == records == NULL only *components and the word counts per component (3 entries each; 0 for a component that
+ * is absent or, with luma_only, not wanted) are written; then offsets[i] and records[i] receive that many uint32 words. */
+int dvp_jpeg_scan_records(int device, const uint8_t* file, long long file_bytes, int luma_only, int on_device, int* components, long long* offset_words, long long* record_words,
+                          uint32_t** offsets, uint32_t** records);
 
 /* ---- the monocular-depth plane prior of a FIRST_INIT pass (APD.cpp:1210-1424) on the device ---------------------------------------
  * From the relative depth map of dep/<id>.dmb (dep_w x dep_h floats as read, dense) and the sparse points of sfm/<id>.txt

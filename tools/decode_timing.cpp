@@ -3,6 +3,8 @@
 //   (a) marker parse + entropy decode -> coefficient records            csrc/dvp_jpeg_dec_mid.hpp
 //   (b) per block: records -> dequantise -> inverse DCT -> clamp -> plane   csrc/dvp_jpeg_dec.hpp
 //   (c) three channels only: per pixel chroma sampling + colour equations
+// and what `apd --entropy-on gpu` leaves on the host in place of (a): the marker parse up to the scan and the pre-scan that finds
+// the segments and lays out the subsequences (csrc/dvp_jpeg_huff.hpp plan()), with the bytes that then go up.
 // usage: decode_timing file.jpg repeats      prints one line per channel count, medians in milliseconds
 #include <algorithm>
 #include <chrono>
@@ -12,6 +14,7 @@
 
 #include "../dvp-mvs_amd/csrc/dvp_jpeg_dec.hpp"
 #include "../dvp-mvs_amd/csrc/dvp_jpeg_dec_mid.hpp"
+#include "../dvp-mvs_amd/csrc/dvp_jpeg_huff.hpp"
 
 using clock_type = std::chrono::steady_clock;
 static double ms(clock_type::time_point a, clock_type::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); }
@@ -28,10 +31,23 @@ int main(int argc, char** argv) {
 	fclose(f);
 	const int repeats = std::max(1, atoi(argv[2]));
 	for (int channels : { 1, 3 }) {
-		std::vector<double> ta, tb, tc;
+		std::vector<double> ta, tb, tc, tp;
+		long long upload_bytes = 0, subsequences = 0, segments = 0;
 		long long record_bytes = 0, blocks = 0, pixels = 0;
 		unsigned checksum = 0;
 		for (int r = 0; r < repeats; ++r) {
+			{   // the host's share of the device path: parse to the scan + pre-scan
+				const clock_type::time_point p0 = clock_type::now();
+				dvpjdmid::Decoder h;
+				h.stop_at_scan = true;
+				dvpjh::Plan plan;
+				if (h.decode(file.data(), file.size(), channels == 1) && dvpjh::plan(h, channels == 1, dvpjh::kSubseqBytes, &plan)) {
+					upload_bytes = (long long)(plan.data_bytes + plan.segs.size() * sizeof(dvpjh::Seg) + (size_t)plan.lanes * 4 + sizeof(dvpjh::Tables));
+					subsequences = plan.lanes;
+					segments = (long long)plan.segs.size();
+				}
+				tp.push_back(ms(p0, clock_type::now()));
+			}
 			const clock_type::time_point t0 = clock_type::now();
 			dvpjdmid::Decoder d;
 			if (!d.decode(file.data(), file.size(), channels == 1)) { fprintf(stderr, "%s\n", d.error); return 2; }
@@ -70,8 +86,8 @@ int main(int argc, char** argv) {
 			pixels = (long long)d.width * d.height;
 			checksum += out[out.size() / 2];
 		}
-		printf("channels %d entropy_ms %.1f blocks_ms %.1f colour_ms %.1f record_bytes %lld blocks %lld pixels %lld check %u\n", channels, median(ta), median(tb), median(tc), record_bytes,
-		       blocks, pixels, checksum);
+		printf("channels %d entropy_ms %.1f blocks_ms %.1f colour_ms %.1f record_bytes %lld blocks %lld pixels %lld check %u prescan_ms %.2f upload_bytes %lld subsequences %lld segments %lld\n", channels, median(ta), median(tb),
+		       median(tc), record_bytes, blocks, pixels, checksum, median(tp), upload_bytes, subsequences, segments);
 	}
 	return 0;
 }

@@ -8,7 +8,12 @@ the bytes of coefficient records per pixel.
 
 Device part (only where a GPU is present; else the file says "not measured on the device"): dvp_jpeg_decode and
 dvp_jpeg_decode_into_store on the same file, their host part (parse + entropy decode) and device part (upload, launches, read-back, wait),
-median of five after one warm-up call.  Per-kernel times want a run of their own:
+median of five after one warm-up call; then the same calls with the Huffman scan on the device as well (`apd --entropy-on gpu`,
+dvp_jpeg_set_entropy(1)): wall time of each call with the switch off and on (unserialised), the path's statistics, and the split
+over its phases from a serialised run (DVP_JPEG_ENTROPY_SERIAL=1: a wait after every phase), at subsequences of 128 and 256 bytes.
+wall_lines(capi, data, why) with another checkout's package as `capi` measures that build's calls the same way (the parent
+commit's, for the comparison in profiles/decode_timing.txt).
+Per-kernel times want a run of their own:
     rocprofv3 --kernel-trace --stats -d /tmp/jd -- python tools/decode_timing.py --device-only
 usage: decode_timing.py [--quality Q] [--size WxH] [--device-only] [--out FILE]"""
 import io
@@ -17,6 +22,8 @@ import statistics
 import subprocess
 import sys
 import tempfile
+import time
+import ctypes
 
 import numpy as np
 
@@ -34,6 +41,78 @@ def textured_picture(W, H):
         a += gain * np.repeat(np.repeat(g, cell, 0), cell, 1)[:H, :W]
     a += 3.0 * rng.standard_normal((H, W, 3)).astype(np.float32)
     return np.clip(np.rint(a), 0, 255).astype(np.uint8)
+
+
+CALLS = ("dvp_jpeg_decode 1 channel", "dvp_jpeg_decode 3 channels", "dvp_jpeg_decode_into_store + host copy", "dvp_jpeg_decode_into_store")
+
+
+def one_call(capi, data, what):
+    """wall milliseconds of one call"""
+    t0 = time.perf_counter()
+    if what.startswith("dvp_jpeg_decode_into_store"):
+        store = capi.ImageStore()
+        t0 = time.perf_counter()
+        store.put_jpeg(0, data, want_plane="copy" in what)
+        t = time.perf_counter() - t0
+        store.close()
+        return t * 1e3
+    L, f = capi.lib(), np.frombuffer(data, np.uint8)     # (straight through the C ABI, into a buffer made before the clock starts)
+    ch = 1 if "1 channel" in what else 3
+    W, H = capi.jpeg_size(data, ch)
+    out = np.empty((H, W * ch), np.uint8)
+    t0 = time.perf_counter()
+    rc = L.dvp_jpeg_decode(0, f.ctypes.data_as(ctypes.c_void_p), f.size, ch, out.ctypes.data_as(ctypes.c_void_p), out.strides[0], None, None)
+    t = time.perf_counter() - t0
+    assert rc == 0, L.dvp_jpeg_decode_last_error()
+    return t * 1e3
+
+
+def wall(capi, data, what):
+    """median of five after a warm-up call"""
+    return statistics.median([one_call(capi, data, what) for _ in range(6)][1:])
+
+
+def wall_lines(capi, data, why):
+    out = ["", "wall time per call, median of 5 after a warm-up call (ms; %s):" % why]
+    for what in CALLS:
+        out.append("  %-40s %.1f" % (what + ":", wall(capi, data, what)))
+    return out
+
+
+def entropy_lines(capi, data):
+    out = ["", "--entropy-on gpu (dvp_jpeg_set_entropy(1)): the Huffman scan on the device as well, same file, same session",
+           "wall time per call, median of 5 after a warm-up call, unserialised (ms):",
+           "  %-40s %10s %16s %16s" % ("", "switch off", "on, 128 bytes", "on, 256 bytes")]
+    os.environ.pop("DVP_JPEG_ENTROPY_SERIAL", None)
+    for what in CALLS:
+        row = []
+        for on, subseq in ((False, "128"), (True, "128"), (True, "256")):
+            os.environ["DVP_JPEG_SUBSEQ_BYTES"] = subseq
+            capi.jpeg_set_entropy(on)
+            row.append(wall(capi, data, what))
+            if on:
+                assert capi.jpeg_entropy_stats()["path"] == "device", capi.jpeg_entropy_stats()
+        out.append("  %-40s %10.1f %16.1f %16.1f" % ((what + ":",) + tuple(row)))
+    out.append("statistics and the split over the phases (serialised: a wait after every phase; median of 5 after a warm-up call, ms):")
+    os.environ["DVP_JPEG_ENTROPY_SERIAL"] = "1"
+    capi.jpeg_set_entropy(True)
+    for subseq in ("128", "256"):
+        os.environ["DVP_JPEG_SUBSEQ_BYTES"] = subseq
+        for what in ("dvp_jpeg_decode 1 channel", "dvp_jpeg_decode 3 channels"):
+            runs = []
+            for k in range(6):
+                total = one_call(capi, data, what)
+                runs.append(dict(capi.jpeg_entropy_phases(), total=total))
+            st = capi.jpeg_entropy_stats()
+            med = {k: statistics.median(r[k] for r in runs[1:]) for k in runs[0]}
+            out.append("  %s, subsequences of %s bytes: %d subsequences in %d chunk(s), %d segment(s); longest chain %d, inter-chunk rounds %d, mean re-decodes per subsequence %.2f; uploaded %.1f MB"
+                       % (what, subseq, st["subsequences"], st["chunks"], st["segments"], st["longest_chain"], st["rounds"], st["decodes"] / max(st["subsequences"], 1), st["uploaded_bytes"] / 1e6))
+            out.append("      pre-scan %.2f   upload %.2f   synchronisation %.2f   census + count %.2f   scans %.2f   write %.2f   reconstruction %.2f   whole call %.1f"
+                       % tuple(med[k] for k in capi.ENTROPY_PHASES + ("total",)))
+    os.environ.pop("DVP_JPEG_ENTROPY_SERIAL", None)
+    os.environ.pop("DVP_JPEG_SUBSEQ_BYTES", None)
+    capi.jpeg_set_entropy(False)
+    return out
 
 
 def main():
@@ -64,6 +143,8 @@ def main():
             lines.append("          share that can move to the device, (b) + (c): %.0f %%;  what stays, (a): %.0f %%" % (100 * (bb + c) / total, 100 * a / total))
             lines.append("          coefficient records + offsets: %d bytes = %.2f bytes per pixel, against %d byte(s) per pixel of the plane; %d blocks, %.2f records per block"
                          % (int(v["record_bytes"]), int(v["record_bytes"]) / int(v["pixels"]), ch, int(v["blocks"]), (int(v["record_bytes"]) / 4 - int(v["blocks"])) / int(v["blocks"])))
+            lines.append("          with --entropy-on gpu the host keeps: parse to the scan + pre-scan %.2f ms; uploads %d bytes (%d subsequences of 128 bytes in %d segment(s)) instead of the records"
+                         % (float(v["prescan_ms"]), int(v["upload_bytes"]), int(v["subsequences"]), int(v["segments"])))
         lines.append("")
     if os.path.exists("/dev/kfd"):
         import importlib
@@ -72,7 +153,7 @@ def main():
         for what in ("dvp_jpeg_decode 1 channel", "dvp_jpeg_decode 3 channels", "dvp_jpeg_decode_into_store + host copy", "dvp_jpeg_decode_into_store"):
             host, dev = [], []
             for k in range(6):
-                if what.startswith("dvp_jpeg_decode"):
+                if what.startswith("dvp_jpeg_decode "):
                     capi.jpeg_decode(data, 1 if "1 channel" in what else 3)
                 else:
                     store = capi.ImageStore()
@@ -85,6 +166,10 @@ def main():
             lines.append("  %-32s host part (parse + entropy decode) %.1f   device part (upload, launches, read-back, wait) %.1f   records %.1f MB"
                          % (what + ":", statistics.median(host), statistics.median(dev), t["record_bytes"] / 1e6))
         lines.append("  per-kernel times: not split here (rocprofv3 --kernel-trace --stats in a run of its own)")
+        if hasattr(capi.lib(), "dvp_jpeg_set_entropy"):
+            lines += entropy_lines(capi, data)
+        else:
+            lines += wall_lines(capi, data, "this build has no --entropy-on")
     else:
         lines.append("device: not measured on the device (no GPU where this file was written)")
     text = "\n".join(lines) + "\n"

@@ -1,4 +1,4 @@
-// ORACLE — TEST INFRASTRUCTURE ONLY.  PARITY UNPINNED (see ora_common.h).
+// ORACLE — TEST INFRASTRUCTURE ONLY.  PINNED to the reference's device text (see ora_common.h).
 // C entry points (ctypes) + the launch emulation / kernel sequence of APD::RunPatchMatch
 // (APD.cu:4406-4532).  Kernels are pure functions of the pre-launch state (the strong update
 // reads neighbours from a snapshot), so rows are processed in parallel with OpenMP without

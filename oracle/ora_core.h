@@ -1,4 +1,4 @@
-// ORACLE — TEST INFRASTRUCTURE ONLY.  PARITY UNPINNED (see ora_common.h).
+// ORACLE — TEST INFRASTRUCTURE ONLY.  PINNED to the reference's device text (see ora_common.h).
 // Context, software sampler, small math helpers and the two NCC cost functions.
 #ifndef ORA_CORE_H_
 #define ORA_CORE_H_

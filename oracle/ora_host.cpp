@@ -1,4 +1,4 @@
-// ORACLE — TEST INFRASTRUCTURE ONLY.  PARITY UNPINNED (see ora_common.h).
+// ORACLE — TEST INFRASTRUCTURE ONLY.  host side: PARITY UNPINNED (see ora_common.h).
 // Sequential restatements of the HOST stages next to the hot path for the parity tests of
 // dvp-mvs_amd/host/: RunFusion (ETH variant, /root/reference/APD.cpp:1809-1960 with Get3DPointonWorld :500-523,
 // ProjectCamera :536-546, GetAngle :1797-1806) and the ratio-map half of the Depth-Anything prior

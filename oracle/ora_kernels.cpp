@@ -1,4 +1,4 @@
-// ORACLE — TEST INFRASTRUCTURE ONLY.  PARITY UNPINNED (see ora_common.h).
+// ORACLE — TEST INFRASTRUCTURE ONLY.  PINNED to the reference's device text (see ora_common.h).
 // Per-pixel kernel bodies of the strong path + post-processing: APD.cu:501-669, 1115-1383,
 // 2010-2141, 2462-2567, 2725-2737, 3127-3328, 3892-4139.
 #include "ora_core.h"

@@ -1,4 +1,4 @@
-// ORACLE — TEST INFRASTRUCTURE ONLY.  PARITY UNPINNED (see ora_common.h).
+// ORACLE — TEST INFRASTRUCTURE ONLY.  PINNED to the reference's device text (see ora_common.h).
 // Weak-pixel path: prior preparation, anchor search, RANSAC fit plane, weak update.
 // APD.cu:790-833, 1897-2008, 2739-3089, 3330-3890, 4159-4404.
 #include "ora_core.h"

@@ -1,4 +1,5 @@
-"""ORACLE — TEST INFRASTRUCTURE ONLY (ctypes wrapper around libdvp_oracle.so).  PARITY UNPINNED.
+"""ORACLE — TEST INFRASTRUCTURE ONLY (ctypes wrapper around libdvp_oracle.so).  Pinned to the reference's device text
+by tests/test_reference_pin.py (see ora_common.h).
 
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may import this module.
 """

@@ -1,0 +1,2 @@
+// REFERENCE PIN stand-in: see cuda_runtime.h
+#include "cuda_runtime.h"

@@ -1,0 +1,2 @@
+// REFERENCE PIN stand-in: see opencv2/core/core.hpp
+#include <opencv2/core/core.hpp>

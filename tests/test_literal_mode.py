@@ -4,7 +4,10 @@ ComputeHomography / ComputeCorrespondingPoint, the source's tap order with its p
 per tap, tex2D(x + 0.5f) with the add/subtract pair rounded, libm expf, the `complex` sigmoid in
 double — APD.cu:679-748, 1059-1089, 905-1000, 3844).
 
-The reference cannot be built here, so this is the available evidence for the
+The literal mode is no longer only this repository's reading: tests/test_reference_pin.py runs the reference's own
+device text on the host (oracle/make_ref.py) and requires the literal mode to equal it bit for bit, launch site by
+launch site, and gates the contract's per-launch distance from it.  What that leaves open is how one
+launch's ulp-level differences grow over a whole run, which is what this test measures, as evidence for the
 north_star's "within 1e-3 relative" clause: the same seeded inputs and the same counter-based RNG
 stream through both evaluations of a whole FIRST_INIT pass (3 iterations) followed by one REFINE_ITER
 pass with geometric consistency, WEAK pixels and priors.  PatchMatch amplifies ulp-level cost

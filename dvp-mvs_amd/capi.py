@@ -33,7 +33,7 @@ EXPORTS = ["dvp_ctx_create", "dvp_ctx_destroy", "dvp_ctx_reserve", "dvp_last_err
            "dvp_run_stage", "dvp_synchronize", "dvp_download_state", "dvp_download_maps", "dvp_download_maps_begin", "dvp_download_maps_finish", "dvp_buffer_bytes", "dvp_download_buffer",
            "dvp_upload_buffer", "dvp_weak_count", "dvp_get_timings", "dvp_reset_timings", "dvp_eval_cost_vectors",
            "dvp_bench_cost_kernel", "dvp_build_id",
-           "dvp_fuse_create", "dvp_fuse_destroy", "dvp_fuse_last_error", "dvp_fuse_set_view", "dvp_fuse_view", "dvp_fuse_view_graded", "dvp_fuse_count", "dvp_fuse_download", "dvp_fuse_last_rounds",
+           "dvp_fuse_create", "dvp_fuse_destroy", "dvp_fuse_last_error", "dvp_fuse_set_view", "dvp_fuse_view", "dvp_fuse_view_graded", "dvp_fuse_consistency", "dvp_fuse_count", "dvp_fuse_download", "dvp_fuse_last_rounds",
            "dvp_jpeg_bound", "dvp_jpeg_encode", "dvp_jpeg_last_error", "dvp_preview_begin", "dvp_preview_finish", "dvp_preview_pixels",
            "dvp_canny_edge_map", "dvp_edge_hysteresis", "dvp_edge_last_error", "dvp_edge_map_begin", "dvp_edge_map_finish",
            "dvp_clean_selected_views", "dvp_viewclean_last_error", "dvp_set_view_cleanup",
@@ -48,7 +48,9 @@ EXPORTS = ["dvp_ctx_create", "dvp_ctx_destroy", "dvp_ctx_reserve", "dvp_last_err
            "dvp_cloud_distances", "dvp_cloud_evaluate", "dvp_cloud_last_error",
            "dvp_cloud_prepare", "dvp_cloud_evaluate_prepared", "dvp_cloud_prep_last_error",
            "dvp_cloud_icp_step", "dvp_cloud_refine_alignment", "dvp_cloud_icp_last_error",
-           "dvp_cloud_scan_gaps", "dvp_cloud_evaluate_scans", "dvp_cloud_scan_last_error"]
+           "dvp_cloud_scan_gaps", "dvp_cloud_evaluate_scans", "dvp_cloud_scan_last_error",
+           "dvp_mesh_create", "dvp_mesh_destroy", "dvp_mesh_add_view", "dvp_mesh_build", "dvp_mesh_block_count", "dvp_mesh_vertex_count", "dvp_mesh_face_count",
+           "dvp_mesh_download", "dvp_mesh_download_volume", "dvp_mesh_set_table", "dvp_mesh_timings", "dvp_mesh_last_error"]
 # ... and the one whose name holds a digit (a scan of the header for [a-z_] names does not see it)
 EXPORTS_WITH_DIGITS = ["dvp_upload_images_u8"]
 PREVIEW_DEPTH, PREVIEW_NORMAL, PREVIEW_WEAK = 1, 2, 4
@@ -190,6 +192,20 @@ def lib():
         L.dvp_cloud_evaluate_scans.argtypes = [ci, vp, ll, vp, vp, ci, vp, ci, vp, ci, vp, vp, vp, vp, vp, vp, vp]
         L.dvp_cloud_scan_last_error.restype = ctypes.c_char_p
         L.dvp_cloud_scan_last_error.argtypes = []
+        L.dvp_fuse_consistency.argtypes = [vp, ci, vp, ci, ci, vp]
+        L.dvp_mesh_create.argtypes = [ci, ctypes.c_float, ctypes.c_float, ci, ctypes.POINTER(vp)]
+        L.dvp_mesh_destroy.argtypes = [vp]
+        L.dvp_mesh_add_view.argtypes = [vp, vp, ci, ci, vp, vp, vp]
+        L.dvp_mesh_build.argtypes = [vp]
+        for n in ("dvp_mesh_block_count", "dvp_mesh_vertex_count", "dvp_mesh_face_count"):
+            getattr(L, n).restype = ll
+            getattr(L, n).argtypes = [vp]
+        L.dvp_mesh_download.argtypes = [vp, vp, vp, vp]
+        L.dvp_mesh_download_volume.argtypes = [vp, vp, vp, vp, vp]
+        L.dvp_mesh_set_table.argtypes = [vp, ll]
+        L.dvp_mesh_timings.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ll), ctypes.POINTER(ll)]
+        L.dvp_mesh_last_error.restype = ctypes.c_char_p
+        L.dvp_mesh_last_error.argtypes = []
         _LIB = L
     return _LIB
 
@@ -1018,3 +1034,43 @@ def cloud_refine_alignment(recon, truth, stages, transform=None, crop=None, devi
     if L.dvp_cloud_refine_alignment(device, _p(r), len(r), _p(t), len(t), ctypes.byref(pr), ctypes.byref(pt), st, len(stages), _p(out), log, capacity, ctypes.byref(count)) != 0:
         raise DvpError(L.dvp_cloud_icp_last_error().decode())
     return dict(matrix=out, log=[(g.stage, g.step, g.n_src, g.n, g.rmse) for g in log[:min(count.value, capacity)]])
+
+
+def mesh_build(views, voxel, truncation=None, min_weight=2, device=0, table_slots=None, volume=False, timings=False):
+    """dict(vertices: (V, 3) float32, colours: (V, 3) uint8 b g r, faces: (F, 3) int32, blocks) of the TSDF volume and its surface nets
+    built on the GPU from views = [(camera record, depth (H, W) float32, mask (H, W) uint8, bgr (H, W, 3) uint8), ...]
+    (include/dvp_mvs.h dvp_mesh_*); truncation None = 4 voxels; table_slots = the block table's first size; volume=True adds keys, sf,
+    w, colour_sums; timings=True adds ms (allocation, integration, extraction), regrows, bytes"""
+    L = lib()
+    job = ctypes.c_void_p()
+    tau = 4.0 * float(voxel) if truncation is None else float(truncation)
+    if L.dvp_mesh_create(device, float(voxel), tau, int(min_weight), ctypes.byref(job)) != 0:
+        raise DvpError(L.dvp_mesh_last_error().decode())
+    try:
+        if table_slots is not None and L.dvp_mesh_set_table(job, int(table_slots)) != 0:
+            raise DvpError(L.dvp_mesh_last_error().decode())
+        for cam, depth, mask, bgr in views:
+            c = np.ascontiguousarray(cam).reshape(1)
+            d, m, b = np.ascontiguousarray(depth, np.float32), np.ascontiguousarray(mask, np.uint8), np.ascontiguousarray(bgr, np.uint8)
+            if c.itemsize != 112 or d.ndim != 2 or m.shape != d.shape or b.shape != d.shape + (3,):
+                raise ValueError("mesh_build: a view is (camera record, depth (H, W), mask (H, W), bgr (H, W, 3))")
+            if L.dvp_mesh_add_view(job, _p(c), d.shape[1], d.shape[0], _p(d), _p(m), _p(b)) != 0:
+                raise DvpError(L.dvp_mesh_last_error().decode())
+        if L.dvp_mesh_build(job) != 0:
+            raise DvpError(L.dvp_mesh_last_error().decode())
+        nv, nf, nb = L.dvp_mesh_vertex_count(job), L.dvp_mesh_face_count(job), L.dvp_mesh_block_count(job)
+        out = dict(vertices=np.empty((nv, 3), np.float32), colours=np.empty((nv, 3), np.uint8), faces=np.empty((nf, 3), np.int32), blocks=nb)
+        if L.dvp_mesh_download(job, _p(out["vertices"]), _p(out["colours"]), _p(out["faces"])) != 0:
+            raise DvpError(L.dvp_mesh_last_error().decode())
+        if volume:
+            out.update(keys=np.empty(nb, np.uint64), sf=np.empty((nb, 512), np.float32), w=np.empty((nb, 512), np.int32), colour_sums=np.empty((nb, 512, 4), np.uint32))
+            if L.dvp_mesh_download_volume(job, _p(out["keys"]), _p(out["sf"]), _p(out["w"]), _p(out["colour_sums"])) != 0:
+                raise DvpError(L.dvp_mesh_last_error().decode())
+        if timings:
+            ms, regrows, nbytes = (ctypes.c_double * 3)(), ctypes.c_longlong(0), ctypes.c_longlong(0)
+            if L.dvp_mesh_timings(job, ms, ctypes.byref(regrows), ctypes.byref(nbytes)) != 0:
+                raise DvpError(L.dvp_mesh_last_error().decode())
+            out.update(ms=list(ms), regrows=regrows.value, bytes=nbytes.value)
+        return out
+    finally:
+        L.dvp_mesh_destroy(job)

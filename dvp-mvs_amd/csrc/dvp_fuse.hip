@@ -133,6 +133,46 @@ __global__ void __launch_bounds__(256) fuse_gather(const GatherArgs a) {
 	a.count[p] = (signed char)n;
 }
 
+// The consistency mask of a view (dvp_fuse_consistency): 1 where the pixel is a reference pixel (depth > 0, block mask >= 128) and at
+// least min_views sources pass fuse_gather's three tests.  Claims are neither read nor written: a later scan is what it was.
+__global__ void __launch_bounds__(256) fuse_consistency(const FuseView* __restrict__ views, int ref, const int* __restrict__ src, int ns, int min_views, uint8_t* __restrict__ mask) {
+	const FuseView& R = views[ref];
+	const int W = R.cols, H = R.rows;
+	const size_t L = (size_t)W * H;
+	const size_t p = (size_t)blockIdx.x * 256 + threadIdx.x;
+	if (p >= L) return;
+	const int y = (int)(p / W), x = (int)(p - (size_t)y * W);
+	const float z = R.depth[p];
+	uint8_t keep = 0;
+	if (!(R.block && R.block[p] < 128) && z > 0.0f) {
+		int n = 0;
+		const f3 X = fuse_lift(R, x, y, z);
+		const float nr[3] = { R.normal[3 * p], R.normal[3 * p + 1], R.normal[3 * p + 2] };
+		for (int j = 0; j < ns; ++j) {
+			const FuseView& S = views[src[j]];
+			f2 q;
+			float zq;
+			fuse_project(X, S.cam, &q, &zq);
+			const int sx = fuse_round(q.x), sy = fuse_round(q.y);
+			if (sx < 0 || sx >= S.cols || sy < 0 || sy >= S.rows) continue;
+			const size_t sp = (size_t)sy * S.cols + sx;
+			const float zs = S.depth[sp];
+			if (zs <= 0.0f) continue;
+			f2 back;
+			float z_seen;
+			fuse_project(fuse_lift(S, sx, sy, zs), R.cam, &back, &z_seen);
+			const double ex = (double)(x - back.x), ey = (double)(y - back.y);
+			const float err = (float)sqrt(ex * ex + ey * ey);
+			const float rel = fabsf(z_seen - z) / z;
+			const float ns3[3] = { S.normal[3 * sp], S.normal[3 * sp + 1], S.normal[3 * sp + 2] };
+			const float ang = fuse_angle(nr, ns3);
+			n += err < 2.0f && rel < 0.01f && ang < 0.174533f;
+		}
+		keep = n >= min_views;
+	}
+	mask[p] = keep;
+}
+
 // pixels with at least one candidate -> the first undecided list (any order)
 __global__ void __launch_bounds__(256) fuse_first_list(const signed char* count, size_t L, unsigned* list, unsigned* n_list) {
 	const size_t p = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -505,6 +545,7 @@ struct dvp_fuse {
 	FuseGroup g_cap;
 	DevBlock g_rel, g_ang;                        // float
 	DevBlock g_last, g_block_last, g_block_carry; // int
+	DevBlock cons_src, cons_mask;                 // dvp_fuse_consistency's source list (int) and mask (uint8_t)
 	unsigned round_serial = 0, view_serial = 0;
 	// the cloud: one device block per fused view
 	struct Segment { DevBlock dev; long long n; };
@@ -798,6 +839,31 @@ int dvp_fuse_view_graded(dvp_fuse* f, int v, const int* src, int num_src, int ad
 	ge.views = ga.views; ge.ref = v; ge.ns = num_src; ge.advanced = ga.advanced; ge.src = ga.src; ge.last_idx = ga.last_idx; ge.f_pix = ga.f_pix;
 	ge.decision = ga.decision; ge.agree = ga.agree; ge.L = L;
 	return fuse_finish(f, "dvp_fuse_view_graded", L, graded_emit, ge);
+}
+
+// The consistency mask of view slot `v` against the source slots `src` (all with maps): see fuse_consistency.  It has scratch of its
+// own and touches no claim flag, so the cloud of the dvp_fuse_view calls around it is the same with or without it.
+int dvp_fuse_consistency(dvp_fuse* f, int v, const int* src, int num_src, int min_views, uint8_t* mask_out) {
+	if (!f) return 1;
+	auto fail = [f](const char* what) { f->error = std::string("dvp_fuse_consistency: ") + what; return 1; };
+	if (v < 0 || v >= f->num_views || !f->have[v] || num_src < 0 || (num_src > 0 && !src) || !mask_out) return fail("bad arguments");
+	for (int j = 0; j < num_src; ++j)
+		if (src[j] < 0 || src[j] >= f->num_views || !f->have[src[j]]) return fail("bad source slot");
+	FUSE_TRY(f, hipSetDevice(f->device));
+	if (f->views_dirty) {
+		FUSE_TRY(f, hipMemcpyAsync(f->views_dev.as<void>(), f->views.data(), sizeof(FuseView) * f->num_views, hipMemcpyHostToDevice, f->stream));
+		FUSE_TRY(f, hipStreamSynchronize(f->stream));
+		f->views_dirty = false;
+	}
+	const size_t L = (size_t)f->views[v].cols * f->views[v].rows;
+	if (f->cons_src.reserve((size_t)std::max(num_src, 1) * 4, f->stream) || f->cons_mask.reserve(L, f->stream)) return fail("out of device memory");
+	if (num_src > 0) FUSE_TRY(f, hipMemcpyAsync(f->cons_src.as<void>(), src, (size_t)num_src * 4, hipMemcpyHostToDevice, f->stream));
+	hipLaunchKernelGGL(fuse_consistency, dim3((unsigned)((L + 255) / 256)), dim3(256), 0, f->stream, f->views_dev.as<FuseView>(), v, f->cons_src.as<int>(), num_src, min_views,
+	                   f->cons_mask.as<uint8_t>());
+	FUSE_TRY(f, hipGetLastError());
+	FUSE_TRY(f, hipMemcpyAsync(mask_out, f->cons_mask.as<void>(), L, hipMemcpyDeviceToHost, f->stream));
+	FUSE_TRY(f, hipStreamSynchronize(f->stream));
+	return 0;
 }
 
 long long dvp_fuse_count(const dvp_fuse* f) { return f ? f->total : -1; }

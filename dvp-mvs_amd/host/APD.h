@@ -100,6 +100,11 @@ void RunFusion(const path& dense_folder, const std::vector<Problem>& problems); 
 void PrefetchFusionImages(const path& dense_folder, const std::vector<Problem>& problems);   // decode the views' colour images ahead of RunFusion (helper threads)
 void SetFusionOnHost(bool on);          // RunFusion on the host's cores instead (same points, same order, same bits)
 void SetFusionDevice(int device);       // the GPU RunFusion uses (default 0)
+// The serial twin of dvp_fuse_consistency (include/dvp_mvs.h), on plain arrays: mask_out[p] = 1 iff pixel p of views[ref] is a reference
+// pixel (depth > 0, block mask >= 128 where there is one) and at least min_views of the views `src` pass the three tests of the scan,
+// claims ignored.  depth [rows*cols], normal [rows*cols*3], block [rows*cols] or null; the cameras' intrinsics fit the maps' size.
+struct ConsistencyView { Camera cam; int cols, rows; const float* depth; const float* normal; const uint8_t* block; };
+void ConsistencyMaskHost(const std::vector<ConsistencyView>& views, int ref, const std::vector<int>& src, int min_views, uint8_t* mask_out);
 void ExportDepthImagePointCloud(const path& point_cloud_path, const path& image_path, const path& cam_path, Mat& depth, float depth_min, float depth_max);   // APD.cpp:2281-2314
 void RunFusion_TAT_Intermediate(const path& dense_folder, const std::vector<Problem>& problems);   // APD.cpp:1962-2130
 void RunFusion_TAT_advanced(const path& dense_folder, const std::vector<Problem>& problems);       // APD.cpp:2132-2279

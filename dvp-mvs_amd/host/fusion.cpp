@@ -427,6 +427,48 @@ static void RunFusionHost(const path& dense_folder, const std::vector<Problem>& 
 	std::cout << "  [fusion] read maps + images " << t_load << " s, fuse " << t_fuse << " s (of which the ordered step " << t_serial << " s), write " << seconds_since(t_write0) << " s, " << HostThreads() << " threads" << std::endl;
 }
 
+// The consistency mask of a view, the serial twin of the device's fuse_consistency (csrc/dvp_fuse.hip): the gather step above per
+// pixel and source — same lift, projection, rounding, residuals and thresholds, operator for operator — with the claims left out
+// and the passing sources counted instead of listed.  A reference pixel needs depth > 0 (a NaN depth is none).
+void ConsistencyMaskHost(const std::vector<ConsistencyView>& views, int ref, const std::vector<int>& src, int min_views, uint8_t* mask_out) {
+	std::vector<FusionView> fv(views.size());   // (cameras and centres only: lift() reads nothing else)
+	for (size_t v = 0; v < views.size(); ++v) { fv[v].cam = views[v].cam; fv[v].set_centre(); }
+	const ConsistencyView& R = views[ref];
+	const int W = R.cols, H = R.rows;
+	for (int y = 0; y < H; ++y)
+		for (int x = 0; x < W; ++x) {
+			const size_t p = (size_t)y * W + x;
+			mask_out[p] = 0;
+			if (R.block && R.block[p] < 128) continue;
+			const float z = R.depth[p];
+			if (!(z > 0.0f)) continue;
+			const float3 X = fv[ref].lift(x, y, z);
+			const float* n_ref = R.normal + 3 * p;
+			int n = 0;
+			for (int s : src) {
+				const ConsistencyView& S = views[s];
+				float2 q;
+				float zq;
+				ProjectCamera(X, S.cam, q, zq);
+				const float tx = q.x + 0.5f, ty = q.y + 0.5f;   // int(v + 0.5f); a value no int holds lands outside every image
+				if (!(tx > -2147483648.0f && tx < 2147483648.0f) || !(ty > -2147483648.0f && ty < 2147483648.0f)) continue;
+				const int sx = int(tx), sy = int(ty);
+				if (sx < 0 || sx >= S.cols || sy < 0 || sy >= S.rows) continue;
+				const size_t sp = (size_t)sy * S.cols + sx;
+				const float zs = S.depth[sp];
+				if (zs <= 0.0) continue;
+				float2 back;
+				float z_seen;
+				ProjectCamera(fv[s].lift(sx, sy, zs), R.cam, back, z_seen);
+				const float err = (float)std::sqrt(std::pow(x - back.x, 2) + std::pow(y - back.y, 2));
+				const float rel = std::fabs(z_seen - z) / z;
+				const float ang = dvp::fuse_angle(n_ref, S.normal + 3 * sp);
+				n += err < 2.0f && rel < 0.01f && ang < 0.174533f;
+			}
+			mask_out[p] = n >= min_views ? 1 : 0;
+		}
+}
+
 // ---- Tanks & Temples variants (RunFusion_TAT_Intermediate / _advanced, APD.cpp:1962-2279) ---------------------
 // Same witness geometry as RunFusion, different acceptance: a pixel needs k mutually consistent witnesses
 // for some k = 2..#sources, with thresholds that loosen with k (reprojection error < 0.25 k px, relative

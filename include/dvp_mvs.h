@@ -268,6 +268,11 @@ int dvp_fuse_view(dvp_fuse* job, int view, const int* src, int num_src);
 /* ... and of RunFusion_TAT_Intermediate (advanced = 0, APD.cpp:1962-2130) / RunFusion_TAT_advanced (advanced = 1,
  * APD.cpp:2132-2279): `src` holds ALL sources of the view in pair.txt order, -1 for a source without maps */
 int dvp_fuse_view_graded(dvp_fuse* job, int view, const int* src, int num_src, int advanced);
+/* the consistency mask of view slot `view`, what the mesher (dvp_mesh_*) integrates: mask_out[p] = 1 iff the pixel is a reference
+ * pixel (depth > 0, block mask >= 128) and at least min_views of the source slots `src` (all with maps, any number) pass the three
+ * tests of the scan (reprojection < 2 px, relative depth < 1 %, normals < 0.174533 rad), claims ignored; room for rows*cols bytes.  It
+ * reads no claim and writes none: the cloud of the dvp_fuse_view calls before and after it is what it is without the call. */
+int dvp_fuse_consistency(dvp_fuse* job, int view, const int* src, int num_src, int min_views, uint8_t* mask_out);
 long long dvp_fuse_count(const dvp_fuse* job);               /* points so far */
 /* dvp_fuse_count() records of six floats — x y z b g r, struct PointList (main.h:69-72) — in scan order */
 int dvp_fuse_download(dvp_fuse* job, float* points);
@@ -631,6 +636,38 @@ int dvp_cloud_evaluate_scans(int device, const float* recon_xyz, long long num_r
                              const dvp_cloud_prep* prep_truth, int cube_size, const float* tolerances, int num_tol, long long* within_recon, long long* within_truth,
                              long long* used, long long* free_space, long long* counts_out, float* d2_recon_out, float* gap_out);
 const char* dvp_cloud_scan_last_error(void);   /* the calling thread's last error of the two above */
+
+/* ---- a surface from the depth maps: a truncated signed distance volume over a hashed grid of 8 x 8 x 8 blocks and the surface nets of
+ * its zero level; the project's own definition (csrc/dvp_mesh.hpp, DESIGN.md 7 "Mesh"), pinned to no library ----------------------------
+ * voxel s: the lattice's edge in scene units, sample (i, j, k) at ((float)((double)i * s), ...), indices -2^20 ... 2^20 - 1; truncation
+ * tau >= s (at most 64 s); a sample counts from min_weight >= 1 views on.  A view: the camera with the intrinsics of the maps' size,
+ * depth [rows*cols], mask [rows*cols] (non-zero = the pixel is used, if its depth is positive), bgr [rows*cols*3]; host pointers, copied.
+ * dvp_mesh_build: blocks allocated around every masked pixel, every sample integrated over all views in add_view order, then vertices
+ * (one per active cell), their colours and the triangles, in the order of the definition: the bytes of the serial text.  A job may be
+ * given more views and built again.  Errors: a null pointer; a non-finite or non-positive voxel; a truncation below the voxel, not
+ * finite or beyond 64 voxels; min_weight < 1; a lattice index beyond 21 bits; more vertices than an int face index holds; out of device
+ * memory.  Jobs are independent: safe from several threads, one thread per job. */
+typedef struct dvp_mesh dvp_mesh;
+int dvp_mesh_create(int device, float voxel, float truncation, int min_weight, dvp_mesh** out);
+int dvp_mesh_destroy(dvp_mesh* job);
+int dvp_mesh_add_view(dvp_mesh* job, const DvpCamera* cam, int cols, int rows, const float* depth, const uint8_t* mask, const uint8_t* bgr);
+int dvp_mesh_build(dvp_mesh* job);
+/* of the last build, -1 without one */
+long long dvp_mesh_block_count(const dvp_mesh* job);
+long long dvp_mesh_vertex_count(const dvp_mesh* job);
+long long dvp_mesh_face_count(const dvp_mesh* job);
+/* vertices: 3 floats x y z each, colours: 3 bytes b g r each, faces: 3 vertex numbers each */
+int dvp_mesh_download(dvp_mesh* job, float* vertices, uint8_t* colours, int* faces);
+/* the volume behind the last build, every output may be NULL: the blocks' keys ascending, then per block 512 samples (local index
+ * lx * 64 + ly * 8 + lz) of SF, W, and the four integers b, g, r sums and their count */
+int dvp_mesh_download_volume(dvp_mesh* job, unsigned long long* keys, float* sf, int* w, unsigned* colour_sums);
+/* the block table's first size (a power of two, 4 ... 2^32; default: from the masked pixels): a table that fills is doubled and the
+ * allocation run again, which gives the same set */
+int dvp_mesh_set_table(dvp_mesh* job, long long slots);
+/* of the last build: ms[3] = allocation, integration, extraction (wall clock, each ends with a wait), the table's doublings, the
+ * job's device memory */
+int dvp_mesh_timings(const dvp_mesh* job, double* ms, long long* regrows, long long* bytes);
+const char* dvp_mesh_last_error(void);   /* the calling thread's last error of the above */
 
 #ifdef __cplusplus
 }

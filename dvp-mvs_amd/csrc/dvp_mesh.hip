@@ -9,6 +9,7 @@
 //   mesh_integrate  one work-group of 512 lanes per block, a lane per sample, views in add_view order: a gather, no atomics, the float
 //                   sum in a fixed order.  A view is skipped for the whole block — a work-group-uniform test of the block's bounding
 //                   sphere against the view's frustum and depth range — only when no sample of the block can see a masked pixel of it
+//                   (view_misses_block in dvp_mesh.hpp: tests/mesh_host runs that text on the host)
 //   mesh_cells      per block: F of the 9 x 9 x 9 samples the block's cells touch staged in LDS, active cells counted and ranked
 //                   (first pass), then vertex and colour written at the block's base + rank (second pass, after the scan)
 //   mesh_faces      per block: the quads owned by its samples counted, then written (the four cells' vertex numbers come from the
@@ -111,31 +112,6 @@ __global__ void __launch_bounds__(256) mesh_forward(const unsigned long long* __
 	forward[i] = s <= mask ? block_of_slot[s] : -1;
 }
 
-// true only when no sample within `radius` of C (world) can see a masked pixel of the view with sdf >= -tau.  Every bound carries
-// a margin far above the rounding of the per-sample arithmetic (half a pixel and more, a quarter of the radius, 1e-3 of the distance).
-__device__ inline bool view_misses_block(const DevView& dv, const float C[3], float radius, float tau) {
-	const View& v = dv.v;
-	if (!(v.depth_max > 0.0f)) return true;   // no masked pixel at all
-	if (!dv.cullable) return false;
-	const float* R = v.cam.R;
-	const float tx = R[0] * C[0] + R[1] * C[1] + R[2] * C[2] + v.cam.t[0];
-	const float ty = R[3] * C[0] + R[4] * C[1] + R[5] * C[2] + v.cam.t[1];
-	const float tz = R[6] * C[0] + R[7] * C[1] + R[8] * C[2] + v.cam.t[2];
-	const float r = radius * 1.25f + 1e-3f * (sqrtf(tx * tx + ty * ty + tz * tz) + radius);
-	if (!(r == r) || !(tz == tz)) return false;
-	if (tz + r <= 0.0f) return true;
-	if (tz - r > v.depth_max + tau) return true;
-	const float fx = v.cam.K[0], fy = v.cam.K[4], cx = v.cam.K[2], cy = v.cam.K[5];
-	// a visible sample q (camera frame, q.z > 0) has -1.5 < px < cols - 0.5 (int(px + 0.5f) truncates towards zero), py likewise:
-	// four half-spaces through the centre, at -2 and cols + 1
-	const float nx0 = cx + 2.0f, nx1 = (float)v.cols + 1.0f - cx, ny0 = cy + 2.0f, ny1 = (float)v.rows + 1.0f - cy;
-	if (fx * tx + nx0 * tz < -r * sqrtf(fx * fx + nx0 * nx0)) return true;
-	if (-fx * tx + nx1 * tz < -r * sqrtf(fx * fx + nx1 * nx1)) return true;
-	if (fy * ty + ny0 * tz < -r * sqrtf(fy * fy + ny0 * ny0)) return true;
-	if (-fy * ty + ny1 * tz < -r * sqrtf(fy * fy + ny1 * ny1)) return true;
-	return false;
-}
-
 __global__ void __launch_bounds__(512) mesh_integrate(const DevView* __restrict__ views, int num_views, const Params p, const unsigned long long* __restrict__ sorted,
                                                       float* __restrict__ sf, int* __restrict__ w, uint32_t* __restrict__ colour) {
 	const size_t b = blockIdx.x;
@@ -143,12 +119,11 @@ __global__ void __launch_bounds__(512) mesh_integrate(const DevView* __restrict_
 	int at[3];
 	key_block(sorted[b], at);
 	const float P[3] = { lattice(at[0] * 8 + (l >> 6), p.s), lattice(at[1] * 8 + ((l >> 3) & 7), p.s), lattice(at[2] * 8 + (l & 7), p.s) };
-	// the block's samples lie within half the diagonal of a 7 s cube of its centre
-	const float C[3] = { (float)(((double)at[0] * 8.0 + 3.5) * (double)p.s), (float)(((double)at[1] * 8.0 + 3.5) * (double)p.s), (float)(((double)at[2] * 8.0 + 3.5) * (double)p.s) };
-	const float radius = p.s * 6.0622f + fabsf(C[0]) * 1e-6f + fabsf(C[1]) * 1e-6f + fabsf(C[2]) * 1e-6f;   // 3.5 sqrt(3) = 6.06218
+	float C[3], radius;
+	block_sphere(at, p.s, C, &radius);
 	Sample a = { 0.0f, 0, 0u, 0u, 0u, 0u };
 	for (int n = 0; n < num_views; ++n) {
-		if (view_misses_block(views[n], C, radius, p.tau)) continue;
+		if (view_misses_block(views[n].v, views[n].cullable != 0, C, radius, p.tau)) continue;
 		integrate(views[n].v, p.tau, P, &a);
 	}
 	const size_t i = b * kBlockSamples + l;
@@ -327,15 +302,6 @@ static thread_local dvpmem::CallError t_mesh_error;
 static int mesh_fail(const char* who, const std::string& what) { return t_mesh_error.fail(who, what); }
 static int mesh_memory(const char* who, size_t bytes) { return mesh_fail(who, "out of device memory (" + std::to_string(bytes) + " bytes)"); }
 
-static bool orthonormal(const float* R) {
-	for (int i = 0; i < 3; ++i)
-		for (int j = 0; j < 3; ++j) {
-			const double d = (double)R[3 * i] * R[3 * j] + (double)R[3 * i + 1] * R[3 * j + 1] + (double)R[3 * i + 2] * R[3 * j + 2];
-			if (!(fabs(d - (i == j ? 1.0 : 0.0)) < 1e-4)) return false;
-		}
-	return true;
-}
-
 extern "C" {
 
 const char* dvp_mesh_last_error(void) { return t_mesh_error.c_str(); }
@@ -396,8 +362,7 @@ int dvp_mesh_add_view(dvp_mesh* job, const DvpCamera* cam, int cols, int rows, c
 	dv.v.depth_max = masked_depth_max(dv.v);
 	long long masked_here = 0;
 	for (size_t p = 0; p < L; ++p) masked_here += masked(dv.v, p);
-	const float* K = cam->K;
-	dv.cullable = K[6] == 0.0f && K[7] == 0.0f && K[8] == 1.0f && K[1] == 0.0f && K[3] == 0.0f && K[0] > 0.0f && K[4] > 0.0f && orthonormal(cam->R);
+	dv.cullable = cullable(*cam);
 	dvpmem::Carve carve;
 	const size_t o_depth = carve.take(L * 4), o_mask = carve.take(L), o_bgr = carve.take(L * 3);
 	DevBlock mem;

@@ -59,7 +59,7 @@ struct View {
 	const float* depth;     // [rows * cols]
 	const uint8_t* mask;    // [rows * cols]
 	const uint8_t* bgr;     // [rows * cols * 3]
-	float depth_max;        // the largest depth of a masked pixel, 0 without one (only the device's cull reads it)
+	float depth_max;        // the largest depth of a masked pixel, 0 without one (only the view cull reads it)
 };
 
 struct Params {
@@ -162,6 +162,54 @@ DVP_MHD void integrate(const View& v, float tau, const float P[3], Sample* a) {
 		a->r += v.bgr[3 * p + 2];
 		a->n += 1;
 	}
+}
+
+// ---- the view cull: which views a whole block may skip.  Not part of the definition (the serial text integrates every view); the device
+// calls these three and tests/mesh_host's `cull` mode runs the same text, so that its soundness is a host test.
+
+// the sphere around the samples of block `at`: they lie within half the diagonal of a 7 s cube of its centre
+DVP_MHD void block_sphere(const int at[3], float s, float C[3], float* radius) {
+	for (int a = 0; a < 3; ++a) C[a] = (float)(((double)at[a] * 8.0 + 3.5) * (double)s);
+	*radius = s * 6.0622f + fabsf(C[0]) * 1e-6f + fabsf(C[1]) * 1e-6f + fabsf(C[2]) * 1e-6f;   // 3.5 sqrt(3) = 6.06218
+}
+
+DVP_MHD bool orthonormal(const float* R) {
+	for (int i = 0; i < 3; ++i)
+		for (int j = 0; j < 3; ++j) {
+			const double d = (double)R[3 * i] * R[3 * j] + (double)R[3 * i + 1] * R[3 * j + 1] + (double)R[3 * i + 2] * R[3 * j + 2];
+			if (!(fabs(d - (i == j ? 1.0 : 0.0)) < 1e-4)) return false;
+		}
+	return true;
+}
+
+// the camera has K's last row 0 0 1, no skew and an orthonormal R: the sphere test of view_misses_block is valid
+DVP_MHD bool cullable(const DvpCamera& cam) {
+	const float* K = cam.K;
+	return K[6] == 0.0f && K[7] == 0.0f && K[8] == 1.0f && K[1] == 0.0f && K[3] == 0.0f && K[0] > 0.0f && K[4] > 0.0f && orthonormal(cam.R);
+}
+
+// true only when no sample within `radius` of C (world) can see a masked pixel of the view with sdf >= -tau.  Every bound carries
+// a margin far above the rounding of the per-sample arithmetic (half a pixel and more, a quarter of the radius, 1e-3 of the distance).
+DVP_MHD bool view_misses_block(const View& v, bool cullable, const float C[3], float radius, float tau) {
+	if (!(v.depth_max > 0.0f)) return true;   // no masked pixel at all
+	if (!cullable) return false;
+	const float* R = v.cam.R;
+	const float tx = R[0] * C[0] + R[1] * C[1] + R[2] * C[2] + v.cam.t[0];
+	const float ty = R[3] * C[0] + R[4] * C[1] + R[5] * C[2] + v.cam.t[1];
+	const float tz = R[6] * C[0] + R[7] * C[1] + R[8] * C[2] + v.cam.t[2];
+	const float r = radius * 1.25f + 1e-3f * (sqrtf(tx * tx + ty * ty + tz * tz) + radius);
+	if (!(r == r) || !(tz == tz)) return false;
+	if (tz + r <= 0.0f) return true;
+	if (tz - r > v.depth_max + tau) return true;
+	const float fx = v.cam.K[0], fy = v.cam.K[4], cx = v.cam.K[2], cy = v.cam.K[5];
+	// a visible sample q (camera frame, q.z > 0) has -1.5 < px < cols - 0.5 (int(px + 0.5f) truncates towards zero), py likewise:
+	// four half-spaces through the centre, at -2 and cols + 1
+	const float nx0 = cx + 2.0f, nx1 = (float)v.cols + 1.0f - cx, ny0 = cy + 2.0f, ny1 = (float)v.rows + 1.0f - cy;
+	if (fx * tx + nx0 * tz < -r * sqrtf(fx * fx + nx0 * nx0)) return true;
+	if (-fx * tx + nx1 * tz < -r * sqrtf(fx * fx + nx1 * nx1)) return true;
+	if (fy * ty + ny0 * tz < -r * sqrtf(fy * fy + ny0 * ny0)) return true;
+	if (-fy * ty + ny1 * tz < -r * sqrtf(fy * fy + ny1 * ny1)) return true;
+	return false;
 }
 
 // F of a valid sample, NaN of one that is not

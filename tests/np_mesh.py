@@ -229,6 +229,30 @@ def serial(views, s, tau, min_weight, tmp):
                                colours=load("colours", np.uint8).reshape(-1, 3), faces=load("faces", np.int32).reshape(-1, 3))
 
 
+def cull(views, s, tau, tmp):
+    """(cullable per view, skipped (blocks, views) bool in key order) of mesh_host cull: the device's view cull, run on the host"""
+    scene, out = os.path.join(str(tmp), "cull_scene.bin"), os.path.join(str(tmp), "cull.bin")
+    write_scene(views, scene)
+    got = run_program("cull", scene, repr(float(np.float32(s))), repr(float(np.float32(tau))), out)
+    assert got.returncode == 0, got.stderr
+    cullable = np.array([int(line.split()[3]) for line in got.stdout.splitlines() if line.startswith("view ")], bool)
+    assert len(cullable) == len(views)
+    return cullable, np.fromfile(out, np.uint8).reshape(-1, len(views)).astype(bool)
+
+
+PAIR_DTYPE = np.dtype([("view", np.int32), ("s", np.float32), ("tau", np.float32), ("at", np.int32, 3)])
+
+
+def cull_pairs(views, pairs, tmp):
+    """skipped per record of `pairs` (PAIR_DTYPE) of mesh_host cull_pairs"""
+    scene, file, out = os.path.join(str(tmp), "pairs_scene.bin"), os.path.join(str(tmp), "pairs.bin"), os.path.join(str(tmp), "pairs_out.bin")
+    write_scene(views, scene)
+    np.ascontiguousarray(pairs, PAIR_DTYPE).tofile(file)
+    got = run_program("cull_pairs", scene, file, out)
+    assert got.returncode == 0, got.stderr
+    return np.fromfile(out, np.uint8).astype(bool)
+
+
 STAGES = ("keys", "sf", "w", "colour_sums", "vertices", "colours", "faces")
 
 
@@ -292,6 +316,39 @@ def rays(cam, size):
     return -R.T @ t, d @ R
 
 
+def general_camera(eye, target, cols, rows, fx, fy=None, cx=None, cy=None, roll=0.0, skew=0.0, k_scale=1.0, r_scale=1.0, up=(0.0, 0.0, 1.0)):
+    """camera() without its symmetries: cols x rows pixels, fx, fy, cx, cy apart, rolled by `roll` radians about the optical axis, K[1] =
+    skew, the whole of K times k_scale (K[8] == k_scale), R and t times r_scale (the eye stays the point that maps to 0)"""
+    base = camera(eye, target, 1.0, 1, up)["R"].astype(np.float64).reshape(3, 3)
+    c, s = np.cos(roll), np.sin(roll)
+    R = np.stack([c * base[0] + s * base[1], -s * base[0] + c * base[1], base[2]]) * r_scale
+    cam = np.zeros((), CAMERA_DTYPE)
+    fy = fx if fy is None else fy
+    cx = (cols - 1) / 2.0 if cx is None else cx
+    cy = (rows - 1) / 2.0 if cy is None else cy
+    cam["K"] = np.array([fx, skew, cx, 0, fy, cy, 0, 0, 1], np.float64) * k_scale
+    cam["R"] = R.reshape(-1)
+    cam["t"] = -R @ np.asarray(eye, np.float64)
+    cam["c"] = eye
+    cam["height"], cam["width"] = rows, cols
+    return cam
+
+
+def general_rays(cam, cols, rows):
+    """the point that maps to 0 and the world directions (rows, cols, 3) of the pixel centres from K^-1 and R^-1, scaled so that the
+    parameter along a ray is the depth project() reports (K's last row times R X + t)"""
+    K, R, t = cam["K"].astype(np.float64).reshape(3, 3), cam["R"].astype(np.float64).reshape(3, 3), cam["t"].astype(np.float64)
+    y, x = np.mgrid[0:rows, 0:cols]
+    pixel = np.stack([x, y, np.ones_like(x)], -1).astype(np.float64)
+    Ri = np.linalg.inv(R)
+    return -Ri @ t, pixel @ np.linalg.inv(K).T @ Ri.T
+
+
+def _rays(cam, size):
+    """size: an int (the square, symmetric cameras of camera()) or (cols, rows)"""
+    return rays(cam, size) if np.isscalar(size) else general_rays(cam, *size)
+
+
 def paint(depth):
     """a b g r picture that differs from pixel to pixel"""
     H, W = depth.shape
@@ -302,11 +359,11 @@ def paint(depth):
 def view_of_sphere(cam, size, centre, radius, max_incidence=90.0):
     """the sphere's depth map; the mask leaves out the pixels whose ray meets the surface at more than max_incidence degrees from its
     normal, as a consistency mask leaves out grazing pixels"""
-    o, d = rays(cam, size)
+    o, d = _rays(cam, size)
     oc = o - np.asarray(centre, np.float64)
     a, b, c = (d * d).sum(-1), 2 * (d @ oc), oc @ oc - radius * radius
     disc = b * b - 4 * a * c
-    z = np.where(disc > 0, (-b - np.sqrt(np.maximum(disc, 0))) / (2 * a), 0.0)   # d has unit z: the parameter is the depth
+    z = np.where(disc > 0, (-b - np.sqrt(np.maximum(disc, 0))) / (2 * a), 0.0)   # d has unit depth: the parameter is the depth
     depth = np.where(z > 0, z, 0).astype(np.float32)
     normal = (oc + z[..., None] * d) / radius
     cos = -(normal * d).sum(-1) / np.sqrt(a)
@@ -314,13 +371,18 @@ def view_of_sphere(cam, size, centre, radius, max_incidence=90.0):
     return cam, depth, mask.astype(np.uint8), paint(depth)
 
 
-def view_of_plane(cam, size, point, normal):
-    o, d = rays(cam, size)
+def view_of_plane(cam, size, point, normal, within=None):
+    """the plane's depth map; within = (lo, hi): only the pixels whose ray meets the plane inside that world box are masked"""
+    o, d = _rays(cam, size)
     n = np.asarray(normal, np.float64)
     den = d @ n
     z = np.where(np.abs(den) > 1e-9, ((np.asarray(point, np.float64) - o) @ n) / np.where(np.abs(den) > 1e-9, den, 1), 0.0)
     depth = np.where(z > 0, z, 0).astype(np.float32)
-    return cam, depth, (depth > 0).astype(np.uint8), paint(depth)
+    mask = depth > 0
+    if within is not None:
+        hit = o + z[..., None] * d
+        mask &= np.all((hit >= np.asarray(within[0], np.float64) - 1e-9) & (hit <= np.asarray(within[1], np.float64) + 1e-9), -1)
+    return cam, depth, mask.astype(np.uint8), paint(depth)
 
 
 SIX = [(1, 0, 0), (-1, 0, 0), (0, 1, 0), (0, -1, 0), (0, 0, 1), (0, 0, -1)]
@@ -357,6 +419,57 @@ def block_count_views(n, s):
     return out
 
 
+OBLIQUE = (40, 28)
+
+
+def oblique_views(centre, s, variants=()):
+    """five 40 x 28 views of a sphere of 6 voxels along seeded random directions, 60 to 140 voxels away, rolled by 0.4 k, fy = 1.3 fx,
+    the principal point at (0.37 W, 0.61 H), aimed up to 3 voxels off the centre so that the border cuts the sphere.  variants: view
+    number -> "skew" (K[1] = 0.05 fx), "k2" (K times 2) or "r" (R times 1 + 5e-4): the cameras the cull must leave alone"""
+    rng = np.random.default_rng(20240607)
+    centre = np.asarray(centre, np.float64)
+    cols, rows = OBLIQUE
+    out = []
+    for k in range(5):
+        direction = rng.normal(size=3)
+        direction /= np.linalg.norm(direction)
+        distance = rng.uniform(60.0, 140.0)
+        aim = rng.normal(size=3)
+        aim *= rng.uniform(1.0, 3.0) / np.linalg.norm(aim)
+        fx = 2.0 * distance                                                        # the sphere is 12 pixels wide and 15.6 high
+        kind = dict(variants).get(k)
+        cam = general_camera(centre + direction * distance * s, centre + aim * s, cols, rows, fx, 1.3 * fx, 0.37 * cols, 0.61 * rows, roll=0.4 * k,
+                             skew=0.05 * fx if kind == "skew" else 0.0, k_scale=2.0 if kind == "k2" else 1.0, r_scale=1.0 + 5e-4 if kind == "r" else 1.0)
+        out.append(view_of_sphere(cam, OBLIQUE, centre, 6.0 * s))
+    return out
+
+
+UNCULLABLE = {1: "skew", 2: "k2", 3: "r"}
+WIDE = dict(height=160.3, eye=(0.0, 200.0, 0.0))      # (voxels) the wide plane z = 160.3 under a camera at `eye` looking along +z
+
+
+def wide_plane(s, size, half):
+    """a size x size view whose pixels spread over +-half voxels of the plane: (2 ceil(half * 1.025 / 8))^2 columns of two blocks each"""
+    eye = np.asarray(WIDE["eye"]) * s
+    return plane_view(s, size, WIDE["height"] * s, focal=WIDE["height"] * (size - 1) / (2.0 * half), eye=eye)
+
+
+def cull_faces_views(s):
+    """the 96 x 96 wide plane and three views whose frusta pass through its blocks (voxel coordinates below, relative to the plane's middle):
+    1  20 x 12, rolled, off-centre, 40 voxels in front of the plane: it sees a middle part, blocks lie beyond all four sides;
+    2  32 x 20 from inside the slab of blocks, looking along it at a grazing angle: blocks behind it, across z = 0 and in front;
+    3  16 x 16 looking at a patch 30 voxels away that hides the plane: the plane's blocks lie beyond depth_max + tau in its frustum"""
+    mid = np.array([WIDE["eye"][0], WIDE["eye"][1], WIDE["height"]])
+    at = lambda *v: (mid + np.asarray(v, np.float64)) * s
+    box = (at(-54, -54, -1), at(54, 54, 1))
+    plane = ([0, 0, WIDE["height"] * s], [0, 0, 1])
+    close = general_camera(at(5, -3, -40), at(8, 4, 0), 20, 12, 20.0, 26.0, 0.37 * 20, 0.61 * 12, roll=0.5, up=(0.0, 1.0, 0.0))
+    along = general_camera(at(-20, 3, -4.3), at(30, 5, 0), 32, 20, 24.0, 24.0 * 1.3, 0.37 * 32, 0.61 * 20, roll=0.2)
+    hidden = general_camera(at(10, -10, -60), at(10, -10, 0), 16, 16, 14.0, 14.0 * 1.3, 0.37 * 16, 0.61 * 16, roll=0.3, up=(0.0, 1.0, 0.0))
+    return [wide_plane(s, 96, 54.0), view_of_plane(close, (20, 12), *plane, within=box), view_of_plane(along, (32, 20), *plane, within=box),
+            view_of_plane(hidden, (16, 16), at(0, 0, -30), [0, 0, 1])]
+
+
 def cases():
     """name -> dict(views, s, tau, min_weight, closed, table, centre).  The closed spheres are centred on lattice points: six views
     along the axes see the directions (+-1, +-1, +-1) at 54.7 degrees at best, and a cell there whose outer corner lies 1.7 voxels
@@ -389,4 +502,12 @@ def cases():
     C["table_regrows"]["centre"] = off
     add("min_weight_above_views", sphere_views(off, s), mw=7)
     add("views_33", sphere_views(off, s, size=24, count=33), mw=2)
+    add("oblique_sphere", oblique_views(off, s))
+    C["oblique_sphere"]["centre"] = off
+    add("uncullable_views", oblique_views(off, s, UNCULLABLE))
+    add("cull_faces", cull_faces_views(s))
+    wide = wide_plane(s, 96, 54.0)                                                 # 14 x 14 x 2 = 392 blocks
+    for n in (511, 512, 513):
+        add("blocks_%d" % n, [wide] + block_count_views(n - 392, s), tau=s)
+    add("blocks_968", [wide_plane(s, 128, 84.0)])                                  # 22 x 22 x 2
     return C

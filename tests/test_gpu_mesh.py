@@ -1,7 +1,8 @@
 """The mesher on the device: dvp_mesh_build equals the serial text of csrc/dvp_mesh.hpp (tests/mesh_host) bit for bit at every stage
 the ABI hands out - block keys, SF, W, colour sums, vertices, colours, faces - over the case table of tests/np_mesh.py (the serial text
-has no cull: a view culled wrongly for a block shows in SF and W); a table that starts with 4 slots regrows to the same mesh; two
-threads build at once; out of device memory is an error or changes nothing; the refusals carry their messages."""
+has no cull: a view culled wrongly for a block shows in SF and W); a table that starts with 4 slots regrows to the same mesh, with
+general cameras and past 512 blocks too; two threads build at once, a general camera among them; out of device memory is an error or
+changes nothing; the refusals carry their messages."""
 import ctypes
 import os
 import threading
@@ -60,8 +61,18 @@ def test_a_table_of_four_slots_regrows_to_the_same_mesh(capi, serial_of):
     assert M.same(small, roomy) == "" and M.same(small, serial_of("table_regrows")) == ""
 
 
+@pytest.mark.parametrize("case", ["oblique_sphere", "blocks_513"])
+def test_general_cameras_and_a_second_scan_chunk_regrow_to_the_same_mesh(capi, serial_of, case):
+    """(blocks_513: 4 slots double eight times before 513 blocks fill at most half of them)"""
+    c = CASES[case]
+    small = capi.mesh_build(c["views"], c["s"], c["tau"], c["min_weight"], table_slots=4, volume=True, timings=True)
+    roomy = capi.mesh_build(c["views"], c["s"], c["tau"], c["min_weight"], table_slots=1 << 16, volume=True, timings=True)
+    assert small["regrows"] >= 4 and roomy["regrows"] == 0
+    assert M.same(small, roomy) == "" and M.same(small, serial_of(case)) == ""
+
+
 def test_two_threads_build_at_once(capi, serial_of):
-    names, got = ["sphere", "sphere_at_origin"], {}
+    names, got = ["sphere", "sphere_at_origin", "oblique_sphere"], {}
 
     def work(name):
         try:
